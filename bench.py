@@ -14,7 +14,10 @@ One process per GPU: `python bench.py --gpus N` spawns the N ranks itself (or ru
 `python -m torch.distributed.run`); frames are independent, so there is no data-path collective -- torch.distributed (gloo)
 carries only the barrier around the timed region and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0.  Beyond the contract's keys:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the line: the contract's keys,
+the configuration, and what the timed region itself measured (device time per frame, host CPU time per step, the whole path
+against its HBM ceiling).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs()).  With --full the
+line further holds the legs below, each of which takes runs of its own after the timed region:
   parity        the label maps and Cluster blocks of the LAST timed step, compared with the oracle after the timed region
   roofline      the dominant kernel of the benched configuration (the fused assign+update launch, 10 per group), HIP-event
                 timed on its own stream with the GPU to itself; sub-objects: the same launches inside the timed region
@@ -296,6 +299,33 @@ class Workload(object):
         return round(self.H * self.W * self.n * steps / el / 1e6, 1), tot
 
 
+DUMP_LABEL_BYTES = 48 << 20     # float32 label maps beyond this are sampled, index included (the Cluster blocks come on top: < 2 MB)
+CLUSTER_DUMP_TYPES = {"y": np.float32, "x": np.float32, "r": np.float32, "g": np.float32, "b": np.float32, "a": np.float32,
+                      "number": np.float64, "is_active": np.float64, "is_updatable": np.float64, "num_members": np.float64}
+
+
+def dump_outputs(wl, j, out_dir):
+    """What the timed path hands its caller for submission j (the last timed step), as .npy files in out_dir:
+      labels.npy             the label maps of its frames (int16 in HBM) as float32 [frames, H, W]
+      cluster_<field>.npy    the Cluster blocks written back on the host, one array per field, [frames, K]
+    Label maps that would take more than DUMP_LABEL_BYTES are sampled at the same pixels of every frame, drawn with a fixed
+    seed: labels.npy is then [frames, m] and labels_index.npy holds the m flat pixel indices (float64, ascending); the two
+    together stay within DUMP_LABEL_BYTES."""
+    os.makedirs(out_dir, exist_ok=True)
+    d_lab, cls, _, _ = wl.sets[j]
+    n, hw = len(d_lab), wl.H * wl.W
+    labels = np.stack([t.cpu().numpy() for t in d_lab]).reshape(n, hw)
+    if n * hw * 4 > DUMP_LABEL_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(hw, DUMP_LABEL_BYTES // (4 * n + 8), replace=False))
+        np.save(os.path.join(out_dir, "labels_index.npy"), idx.astype(np.float64))
+        labels = labels[:, idx]
+    else:
+        labels = labels.reshape(n, wl.H, wl.W)
+    np.save(os.path.join(out_dir, "labels.npy"), labels.astype(np.float32))
+    for field, dt in CLUSTER_DUMP_TYPES.items():
+        np.save(os.path.join(out_dir, "cluster_%s.npy" % field), cls[field].astype(dt))
+
+
 def parity_of(wl, j):
     """The label maps and Cluster blocks of submission j against the oracle (bit-exact; SURVEY.md 8d 'parity gate')."""
     from oracle import oracle as orc
@@ -376,12 +406,12 @@ def single_frame_latency(eng, wl, reps=24):
 
 def end_to_end_ref_binding(H, W, K, budget_s=3.0, threads=4):
     """The same through the drop-in itself: the REFERENCE's Cython binding with the arch "hip/gfx950" patched in
-    (integration/_build, built by integration/build_ref_binding.sh): cfast_slic.SlicModel(K, "hip/gfx950") driven the way
+    (oracle/_ref/integration, built by integration/build_ref_binding.sh): cfast_slic.SlicModel(K, "hip/gfx950") driven the way
     fast_slic/base_slic.py:18-52 drives it (only the compiled extension travels to the GPU box, not the reference's Python
-    package).  Runs in a separate interpreter (the patched module links libfslic_hip.so itself).  None when integration/_build is absent."""
+    package).  Runs in a separate interpreter (the patched module links libfslic_hip.so itself).  None when oracle/_ref/integration is absent."""
     import glob
     import subprocess
-    build = os.path.join(ROOT, "integration", "_build")
+    build = os.path.join(ROOT, "oracle", "_ref", "integration")
     if not glob.glob(os.path.join(build, "cfast_slic*.so")):
         return None
     code = r"""
@@ -486,10 +516,16 @@ def main():
                          "most two submissions per group (every merged form is a buffer set and a recorded graph per slot: small --frames-per-gpu "
                          "would otherwise multiply the setup); given explicitly, as many submissions as fit")
     ap.add_argument("--no-batching", action="store_true", help="one submission per launch group (no dynamic batching in the pipeline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-4k", action="store_true", help="skip the 4K, K=6000, LSC and end-to-end sub-objects")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--timed-only", action="store_true", help="the timed region and nothing else (profiling runs: no roofline / parity / baseline legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs that take runs of their own: parity against the oracle, rooflines, "
+                         "4K / K=6000 / LSC operating points, single-frame latency, end-to-end, CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (label maps, Cluster blocks; rank 0's frames) as DIR/<name>.npy "
+                         "(see dump_outputs())")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-4k", action="store_true", help="with --full: skip the 4K, K=6000, LSC and end-to-end sub-objects")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity gates")
+    ap.add_argument("--timed-only", action="store_true", help="the timed region and nothing else, even with --full (profiling runs)")
     ap.add_argument("--share-device", action="store_true",
                     help="every rank of an N > 1 launch uses GPU 0: the host side of an N-rank launch (submit loops, slot threads, pinned "
                          "blocks, rendezvous) measured on a one-GPU box; the line then says so and is NOT a scaling point")
@@ -497,6 +533,8 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 1000 if args.workload == "720p" else 200
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     group_limit = int(os.environ.get("FSLIC_BENCH_MAX_GROUP", "16"))      # the library's group limit (FSLIC_MAX_GROUP of its build)
     if args.launch_frames is not None and not 1 <= args.launch_frames <= group_limit:
         ap.error("--launch-frames must be in 1..%d (the library's group limit, FSLIC_MAX_GROUP)" % group_limit)
@@ -631,7 +669,9 @@ def main():
                 out["config"]["share_device"] = "all %d ranks on GPU 0: a host-side load test, not a scaling point" % world
             out["per_rank_ms"] = {"min": round(min(per_rank) * 1e3, 3), "max": round(max(per_rank) * 1e3, 3), "all": [round(t * 1e3, 3) for t in per_rank]}
             out["per_rank_megapixels_per_sec"] = [round(float(H) * W * fpg * args.steps / t / 1e6, 1) for t in per_rank]
-    if rank == 0 and args.timed_only:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl, first + args.steps - 1, args.dump_outputs)
+    if rank == 0 and (args.timed_only or not args.full):
         print(json.dumps(out))
         sys.stdout.flush()
     elif rank == 0:

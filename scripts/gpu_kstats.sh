@@ -18,7 +18,7 @@ for cfg in "${CFGS[@]}"; do
 done
 if [ "${KSTATS_BENCH:-0}" = "1" ]; then
   rm -rf $OUT/p
-  timeout 600 rocprofv3 --kernel-trace -d $OUT/p -o b -- python $R/bench.py --steps 30 --warmup 12 --no-cpu-baseline --no-4k --no-parity > $OUT/bench_profiled.json 2>$OUT/bench_profiled.err
+  timeout 600 rocprofv3 --kernel-trace -d $OUT/p -o b -- python $R/bench.py --steps 30 --warmup 12 --full --no-cpu-baseline --no-4k --no-parity > $OUT/bench_profiled.json 2>$OUT/bench_profiled.err
   DB=$(find $OUT/p -name '*_results.db' | head -1)
   python $R/scripts/rocpd_stats.py overlap $DB 0.4 > $OUT/bench_stream_overlap.txt
   cat $OUT/bench_stream_overlap.txt

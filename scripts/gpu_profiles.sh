@@ -11,8 +11,8 @@ cd $R
 echo "${BUILD_COMMIT:-unrecorded}" > $OUT/build_commit.txt
 rocminfo 2>/dev/null | grep -E 'Marketing Name|Compute Unit|Max Clock' | head -8 > $OUT/rocminfo.txt
 nproc >> $OUT/rocminfo.txt; grep -m1 'model name' /proc/cpuinfo >> $OUT/rocminfo.txt
-timeout 900 python bench.py 2> $OUT/bench.err > $OUT/bench.json; echo "bench rc=$?"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/bench_driver_cmdline.err > $OUT/bench_driver_cmdline.json; echo "bench (driver command line) rc=$?"
+timeout 900 python bench.py --full 2> $OUT/bench.err > $OUT/bench.json; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $OUT/bench_driver_cmdline.err > $OUT/bench_driver_cmdline.json; echo "bench (driver command line) rc=$?"
 cd /tmp && export TMPDIR=/tmp
 # 1. the pipelined timed region under rocprofv3: per-kernel statistics and how the streams overlap
 rm -rf $OUT/p

@@ -13,7 +13,7 @@
 #     TRIP_PMC=1              instruction mix of every kernel of one group (scripts/gpu_pmc_group.sh; PMC_* select the group)
 #   TRIP_SELECT="lab1.so .."  in-kernel time stamps of k_cca_select per frame (lab build 1), per library
 #   TRIP_STAMPS4="lab4.so .." phase stamps of the block assign kernel (lab build 4, scripts/lab_assign_phases.py), per library
-#   TRIP_BENCH=1            the complete bench line of the product build (python bench.py, all legs) -> gpurun_out/trip/bench_full.json
+#   TRIP_BENCH=1            the complete bench line of the product build (python bench.py --full, all legs) -> $OUT/bench_full.json
 #   TRIP_BENCH_DRIVER=1     ... and the driver's command line with all legs -> bench_driver_cmdline.json
 #   TRIP_OVERLAP=1          rocprofv3 kernel trace of the pipelined region: stream overlap + per-kernel share (scripts/gpu_kstats.sh KSTATS_BENCH)
 #   TRIP_EXTRA="cmd"        anything else, run last from the repository root
@@ -75,11 +75,11 @@ done
 
 if [ "${TRIP_BENCH:-0}" = "1" ]; then
   echo "######## bench line (all legs)"
-  timeout 900 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?"; cut -c1-1500 $OUT/bench_full.json
+  timeout 900 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?"; cut -c1-1500 $OUT/bench_full.json
 fi
 if [ "${TRIP_BENCH_DRIVER:-0}" = "1" ]; then
   echo "######## bench line, the driver's command"
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmdline.json 2> $OUT/bench_driver_cmdline.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench_driver_cmdline.json
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmdline.json 2> $OUT/bench_driver_cmdline.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench_driver_cmdline.json
 fi
 if [ "${TRIP_OVERLAP:-0}" = "1" ]; then
   echo "######## stream overlap of the pipelined region"
