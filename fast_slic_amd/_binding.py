@@ -45,6 +45,16 @@ EXPORTS = [
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
     "fslic_hip_separate_pass_redos", "fslic_hip_copy_bandwidth",
+    # SimpleCRF (fast_slic_amd/crf.py)
+    "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
+    "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
+    "fslic_hip_crf_last_time", "fslic_hip_crf_num_frames", "fslic_hip_crf_pop_frame", "fslic_hip_crf_push_frame", "fslic_hip_crf_frame",
+    "fslic_hip_crf_frame_time", "fslic_hip_crf_frame_set_clusters", "fslic_hip_crf_frame_get_clusters",
+    "fslic_hip_crf_frame_set_connectivity", "fslic_hip_crf_frame_set_connectivity_csr", "fslic_hip_crf_frame_get_connectivity",
+    "fslic_hip_crf_frame_set_mask", "fslic_hip_crf_frame_set_proba", "fslic_hip_crf_frame_set_unbiased", "fslic_hip_crf_frame_set_unary",
+    "fslic_hip_crf_frame_get_unary", "fslic_hip_crf_frame_spatial_energy", "fslic_hip_crf_frame_temporal_energy",
+    "fslic_hip_crf_frame_get_inferred", "fslic_hip_crf_frame_reset_inferred", "fslic_hip_crf_initialize", "fslic_hip_crf_inference",
+    "fslic_hip_crf_expf_host", "fslic_hip_crf_expf_device",
 ]
 
 _lib = None
@@ -133,8 +143,34 @@ def load_library():
         lib.fslic_hip_knn_connectivity.argtypes = [i32, i32, i32, vp, C.c_size_t, vp, vp]
         lib.fslic_hip_get_mask_density.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
         lib.fslic_hip_cluster_density_to_mask.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+        if hasattr(lib, "fslic_hip_crf_new"):
+            _declare_crf(lib)
         _lib = lib
         return lib
+
+
+def _declare_crf(lib):
+    """Signatures of the SimpleCRF entry points (include/fslic_hip.h)."""
+    vp, i32, sz, f32 = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+    for name, args in [
+        ("new", [sz, sz, C.POINTER(vp)]), ("copy", [vp, C.POINTER(vp)]), ("get_params", [vp, vp]), ("set_params", [vp, vp]),
+        ("set_compat", [vp, i32, f32]), ("get_compat", [vp, i32, C.POINTER(f32)]), ("num_classes", [vp, C.POINTER(sz), C.POINTER(sz)]),
+        ("first_time", [vp]), ("last_time", [vp]), ("pop_frame", [vp]), ("push_frame", [vp, C.POINTER(vp)]),
+        ("frame", [vp, i32, C.POINTER(vp)]), ("frame_time", [vp]), ("frame_set_clusters", [vp, vp]), ("frame_get_clusters", [vp, vp]),
+        ("frame_set_connectivity", [vp, i32, vp, vp, sz]), ("frame_set_connectivity_csr", [vp, i32, vp, vp]),
+        ("frame_get_connectivity", [vp, vp, vp]), ("frame_set_mask", [vp, vp, f32]), ("frame_set_proba", [vp, vp]),
+        ("frame_set_unbiased", [vp]), ("frame_set_unary", [vp, vp]), ("frame_get_unary", [vp, vp]),
+        ("frame_spatial_energy", [vp, i32, i32, C.POINTER(f32)]), ("frame_temporal_energy", [vp, vp, i32, C.POINTER(f32)]),
+        ("frame_get_inferred", [vp, vp]), ("frame_reset_inferred", [vp]), ("initialize", [vp]), ("inference", [vp, vp, sz]),
+        ("expf_host", [vp, vp, sz, i32]), ("expf_device", [vp, vp, vp, sz]),
+    ]:
+        f = getattr(lib, "fslic_hip_crf_" + name)
+        f.argtypes = args
+        f.restype = i32
+    lib.fslic_hip_crf_free.argtypes = [vp]
+    lib.fslic_hip_crf_free.restype = None
+    lib.fslic_hip_crf_num_frames.argtypes = [vp]
+    lib.fslic_hip_crf_num_frames.restype = sz
 
 
 def _raise(rc):

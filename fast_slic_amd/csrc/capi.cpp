@@ -2,11 +2,13 @@
 // (The asynchronous forms live in pipeline.cpp, the O(K) host functions and stage entry points in host_utils.cpp.)
 // Part of the host engine, see engine_internal.h.
 #include "engine_internal.h"
+#include "crf.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 using namespace fslic;
 
@@ -297,6 +299,340 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot) {
     if (!e || slot < 0 || slot >= (int)e->slots.size()) return -1;
     return __atomic_load_n(&e->slots[slot].n_separate_redo, __ATOMIC_RELAXED);
 }
+
+// ---- SimpleCRF (src/simple-crf.{h,hpp,cpp}): host state and bookkeeping here, inference in crf.hip --------------------------------
+// Every entry holds the CRF's mutex (a frame's: its parent's) for its duration; the numerics of the setters are the reference's
+// expressions (host libm logf, crf_expf for expf).
+#define CRF_LOCK(crf) std::lock_guard<std::mutex> crf_lock__((crf)->mu)
+
+static fslic_crf_frame* crf_frame_at(fslic_crf* crf, int time) {
+    if (crf->frames.empty()) return nullptr;
+    const long long d = (long long)time - crf->frames.front()->time;          // the window holds consecutive times
+    if (d < 0 || d >= (long long)crf->frames.size()) return nullptr;
+    return crf->frames[(size_t)d].get();
+}
+// Unaries or q are about to be replaced on the host, or read there.
+static void crf_touch_unary(fslic_crf_frame* f) { f->dirty_unary = true; }
+static void crf_touch_q(fslic_crf_frame* f) { f->q_on_device = false; f->dirty_q = true; }
+
+int fslic_hip_crf_new(size_t num_classes, size_t num_nodes, fslic_crf** out) {
+    if (!out) return fail(FSLIC_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (num_classes == 0 || num_nodes == 0) return fail(FSLIC_E_INVALID, "num_classes and num_nodes must be positive");
+    if (num_classes >= (1ull << 31) || num_nodes >= (1ull << 31) || (unsigned long long)num_classes * num_nodes >= (1ull << 31))
+        return fail(FSLIC_E_INVALID, "num_classes * num_nodes must be below 2^31");
+    fslic_crf* crf = new fslic_crf();
+    crf->C = num_classes;
+    crf->K = num_nodes;
+    crf->compat.assign(num_classes, 1.0f);                       // simple-crf.hpp:79-89
+    crf->params.spatial_w = 10; crf->params.temporal_w = 10;
+    crf->params.spatial_srgb = 13; crf->params.temporal_srgb = 13;
+    crf->params.spatial_sxy = 80;
+    crf->params.spatial_smooth_w = 0; crf->params.spatial_smooth_sxy = 3;
+    *out = crf;
+    return FSLIC_OK;
+}
+
+void fslic_hip_crf_free(fslic_crf* crf) {
+    if (!crf) return;
+    crf_release_device(crf);
+    delete crf;
+}
+
+int fslic_hip_crf_copy(fslic_crf* crf, fslic_crf** out) {
+    if (!crf || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    *out = nullptr;
+    CRF_LOCK(crf);
+    for (auto& f : crf->frames) {
+        int rc = crf_pull_q(crf, f.get());
+        if (rc) return rc;
+    }
+    fslic_crf* c = new fslic_crf();
+    c->C = crf->C; c->K = crf->K; c->next_time = crf->next_time; c->compat = crf->compat; c->params = crf->params;
+    for (auto& f : crf->frames) {
+        std::unique_ptr<fslic_crf_frame> g(new fslic_crf_frame());
+        g->parent = c; g->time = f->time; g->clusters = f->clusters; g->edges = f->edges; g->unaries = f->unaries; g->q = f->q;
+        c->frames.push_back(std::move(g));
+    }
+    *out = c;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_get_params(fslic_crf* crf, fslic_crf_params* out) {
+    if (!crf || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    *out = crf->params;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_set_params(fslic_crf* crf, const fslic_crf_params* params) {
+    if (!crf || !params) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    crf->params = *params;                                       // (the edge kernel reads them at every inference)
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_set_compat(fslic_crf* crf, int cls, float compat_value) {
+    if (!crf) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    if (cls < 0 || (size_t)cls >= crf->C) return fail(FSLIC_E_INVALID, "class out of range");
+    crf->compat[(size_t)cls] = compat_value;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_get_compat(fslic_crf* crf, int cls, float* out) {
+    if (!crf || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    if (cls < 0 || (size_t)cls >= crf->C) return fail(FSLIC_E_INVALID, "class out of range");
+    *out = crf->compat[(size_t)cls];
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_num_classes(fslic_crf* crf, size_t* num_classes, size_t* num_nodes) {
+    if (!crf) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    if (num_classes) *num_classes = crf->C;
+    if (num_nodes) *num_nodes = crf->K;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_first_time(fslic_crf* crf) {
+    if (!crf) return -1;
+    CRF_LOCK(crf);
+    return crf->frames.empty() ? -1 : crf->frames.front()->time;
+}
+
+int fslic_hip_crf_last_time(fslic_crf* crf) {
+    if (!crf) return -1;
+    CRF_LOCK(crf);
+    return crf->frames.empty() ? -1 : crf->frames.back()->time;
+}
+
+size_t fslic_hip_crf_num_frames(fslic_crf* crf) {
+    if (!crf) return 0;
+    CRF_LOCK(crf);
+    return crf->frames.size();
+}
+
+int fslic_hip_crf_pop_frame(fslic_crf* crf) {
+    if (!crf) return -1;
+    CRF_LOCK(crf);
+    if (crf->frames.empty()) return -1;
+    const int t = crf->frames.front()->time;
+    crf->frames.pop_front();                 // the others keep their device slices until the next inference moves them
+    return t;
+}
+
+int fslic_hip_crf_push_frame(fslic_crf* crf, fslic_crf_frame** out) {
+    if (!crf || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    *out = nullptr;
+    CRF_LOCK(crf);
+    if (crf->next_time == INT32_MAX) return fail(FSLIC_E_INVALID, "frame times exhausted");
+    std::unique_ptr<fslic_crf_frame> f(new fslic_crf_frame());     // SimpleCRFFrame ctor, simple-crf.hpp:29-34
+    f->parent = crf;
+    f->time = crf->next_time++;
+    fslic_cluster one{};
+    one.num_members = 1;
+    f->clusters.assign(crf->K, one);
+    f->edges.resize(crf->K);
+    f->unaries.assign(crf->C * crf->K, 0.0f);
+    f->q.assign(crf->C * crf->K, 0.0f);
+    *out = f.get();
+    crf->frames.push_back(std::move(f));
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame(fslic_crf* crf, int time, fslic_crf_frame** out) {
+    if (!crf || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    *out = crf_frame_at(crf, time);
+    if (!*out) return fail(FSLIC_E_INVALID, "Time out of range");            // simple-crf.hpp:111-115
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_time(fslic_crf_frame* frame) { return frame ? frame->time : -1; }
+
+int fslic_hip_crf_frame_set_clusters(fslic_crf_frame* frame, const fslic_cluster* clusters) {
+    if (!frame || !clusters) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    std::copy(clusters, clusters + frame->clusters.size(), frame->clusters.begin());
+    frame->dirty_graph = true;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_get_clusters(fslic_crf_frame* frame, fslic_cluster* clusters) {
+    if (!frame || !clusters) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    std::copy(frame->clusters.begin(), frame->clusters.end(), clusters);
+    return FSLIC_OK;
+}
+
+// Both forms validate every row before they change one (simple-crf.cpp:11-19 replaces rows 0 .. conn->num_nodes-1).
+int fslic_hip_crf_frame_set_connectivity(fslic_crf_frame* frame, int num_rows, const int* num_neighbors, const uint32_t* neighbors,
+                                         size_t stride) {
+    if (!frame || (num_rows > 0 && !num_neighbors)) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    const size_t K = frame->clusters.size();
+    if (num_rows < 0 || (size_t)num_rows > K) return fail(FSLIC_E_INVALID, "more rows than nodes");
+    for (int i = 0; i < num_rows; i++) {
+        if (num_neighbors[i] < 0 || (size_t)num_neighbors[i] > stride) return fail(FSLIC_E_INVALID, "num_neighbors out of range");
+        if (num_neighbors[i] > 0 && !neighbors) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+        for (int k = 0; k < num_neighbors[i]; k++)
+            if (neighbors[(size_t)i * stride + k] >= K) return fail(FSLIC_E_INVALID, "neighbour index out of range");
+    }
+    for (int i = 0; i < num_rows; i++) {
+        const uint32_t* row = neighbors ? neighbors + (size_t)i * stride : nullptr;
+        frame->edges[(size_t)i].assign(row, row + num_neighbors[i]);
+    }
+    frame->dirty_graph = true;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_set_connectivity_csr(fslic_crf_frame* frame, int num_rows, const int64_t* offsets, const uint32_t* indices) {
+    if (!frame || (num_rows > 0 && !offsets)) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    const size_t K = frame->clusters.size();
+    if (num_rows < 0 || (size_t)num_rows > K) return fail(FSLIC_E_INVALID, "more rows than nodes");
+    if (num_rows > 0 && offsets[0] < 0) return fail(FSLIC_E_INVALID, "offsets must not decrease");
+    for (int i = 0; i < num_rows; i++) {
+        if (offsets[i + 1] < offsets[i]) return fail(FSLIC_E_INVALID, "offsets must not decrease");
+        if (offsets[i + 1] > offsets[i] && !indices) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++)
+            if (indices[k] >= K) return fail(FSLIC_E_INVALID, "neighbour index out of range");
+    }
+    for (int i = 0; i < num_rows; i++) {
+        if (offsets[i + 1] > offsets[i]) frame->edges[(size_t)i].assign(indices + offsets[i], indices + offsets[i + 1]);
+        else frame->edges[(size_t)i].clear();
+    }
+    frame->dirty_graph = true;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_get_connectivity(fslic_crf_frame* frame, int64_t* offsets, uint32_t* indices) {
+    if (!frame || !offsets) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    int64_t o = 0;
+    offsets[0] = 0;
+    for (size_t i = 0; i < frame->edges.size(); i++) {
+        const auto& l = frame->edges[i];
+        if (indices) std::copy(l.begin(), l.end(), indices + o);
+        o += (int64_t)l.size();
+        offsets[i + 1] = o;
+    }
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_set_mask(fslic_crf_frame* frame, const int32_t* classes, float confidence) {
+    if (!frame || !classes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    const size_t C = frame->parent->C, K = frame->parent->K;
+    for (size_t i = 0; i < K; i++)
+        if (classes[i] < 0 || (size_t)classes[i] >= C) return fail(FSLIC_E_INVALID, "class out of range");
+    // simple-crf.cpp:39-53, float expressions as the reference build evaluates them (num_classes is a size_t; GCC fuses the product
+    // of active_proba into its sum, see crf.h)
+    const float lowest_proba = 1.0f / (float)C;
+    const float active_proba = crf_fmaf(1 - lowest_proba, confidence, lowest_proba);
+    const float inactive_proba = (1 - active_proba) / (float)(C - 1);
+    const float active_unary = -logf(active_proba), inactive_unary = -logf(inactive_proba);
+    std::fill(frame->unaries.begin(), frame->unaries.end(), inactive_unary);
+    for (size_t i = 0; i < K; i++) frame->unaries[K * (size_t)classes[i] + i] = active_unary;
+    crf_touch_unary(frame);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_set_proba(fslic_crf_frame* frame, const float* probas) {
+    if (!frame || !probas) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    for (size_t k = 0; k < frame->unaries.size(); k++) frame->unaries[k] = -logf(probas[k]);     // simple-crf.cpp:53-55
+    crf_touch_unary(frame);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_set_unbiased(fslic_crf_frame* frame) {
+    if (!frame) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    std::fill(frame->unaries.begin(), frame->unaries.end(), logf((float)frame->parent->C));     // simple-crf.cpp:34-37
+    crf_touch_unary(frame);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_set_unary(fslic_crf_frame* frame, const float* unary_energies) {
+    if (!frame || !unary_energies) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    std::copy(unary_energies, unary_energies + frame->unaries.size(), frame->unaries.begin());
+    crf_touch_unary(frame);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_get_unary(fslic_crf_frame* frame, float* unary_energies) {
+    if (!frame || !unary_energies) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    std::copy(frame->unaries.begin(), frame->unaries.end(), unary_energies);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_spatial_energy(fslic_crf_frame* frame, int node_i, int node_j, float* out) {
+    if (!frame || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    const size_t K = frame->clusters.size();
+    if (node_i < 0 || node_j < 0 || (size_t)node_i >= K || (size_t)node_j >= K) return fail(FSLIC_E_INVALID, "node number is out of range");
+    *out = node_i == node_j ? 0.0f : crf_spatial_energy(frame->parent->params, frame->clusters[(size_t)node_i], frame->clusters[(size_t)node_j]);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_temporal_energy(fslic_crf_frame* frame, fslic_crf_frame* other_frame, int node_i, float* out) {
+    if (!frame || !other_frame || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    std::unique_lock<std::mutex> a(frame->parent->mu, std::defer_lock), b(other_frame->parent->mu, std::defer_lock);
+    if (frame->parent == other_frame->parent) a.lock();
+    else std::lock(a, b);
+    if (node_i < 0 || (size_t)node_i >= frame->clusters.size() || (size_t)node_i >= other_frame->clusters.size())
+        return fail(FSLIC_E_INVALID, "node number is out of range");
+    *out = frame == other_frame ? 0.0f
+                                : crf_temporal_energy(frame->parent->params, frame->clusters[(size_t)node_i], other_frame->clusters[(size_t)node_i]);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_frame_get_inferred(fslic_crf_frame* frame, float* probas) {
+    if (!frame || !probas) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    int rc = crf_pull_q(frame->parent, frame);
+    if (rc) return rc;
+    std::copy(frame->q.begin(), frame->q.end(), probas);
+    return FSLIC_OK;
+}
+
+static void crf_reset_inferred(fslic_crf_frame* f) {          // simple-crf.cpp:57-59
+    for (size_t k = 0; k < f->q.size(); k++) f->q[k] = crf_expf(-f->unaries[k]);
+    crf_touch_q(f);
+}
+
+int fslic_hip_crf_frame_reset_inferred(fslic_crf_frame* frame) {
+    if (!frame) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(frame->parent);
+    crf_reset_inferred(frame);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_initialize(fslic_crf* crf) {
+    if (!crf) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    for (auto& f : crf->frames) crf_reset_inferred(f.get());    // simple-crf.cpp:153-157
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_inference(fslic_crf* crf, fslic_engine* e, size_t max_iter) {
+    if (!crf) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    CRF_LOCK(crf);
+    return crf_inference(crf, e, max_iter);
+}
+
+int fslic_hip_crf_expf_host(const float* in, float* out, size_t n, int use_libm) {
+    if (n && (!in || !out)) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    if (use_libm) for (size_t k = 0; k < n; k++) out[k] = expf(in[k]);
+    else for (size_t k = 0; k < n; k++) out[k] = crf_expf(in[k]);
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n) { return crf_expf_device(e, in, out, n); }
 
 #ifdef FSLIC_LAB
 // lab build only: the 16 status words of frame `frame` of the last group on `slot` as the export left them in pinned memory

@@ -241,6 +241,76 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot);
  * the specification.  Allocates and frees 2 x `bytes` of device memory. */
 int fslic_hip_copy_bandwidth(fslic_engine* e, size_t bytes, int reps, double* gb_per_s);
 
+/* ---- SimpleCRF (src/simple-crf.h, src/simple-crf.{hpp,cpp}; Python: csimple_crf.pyx, fast_slic/crf.py) ----
+ * Mean-field inference of a Potts CRF over the superpixel graph: spatial edges inside a frame (the neighbour lists, typically from
+ * fslic_hip_get_connectivity) and temporal edges between consecutive frames (node i of frame t to node i of t-1 and t+1).  The
+ * state lives on the host (every entry but fslic_hip_crf_inference and fslic_hip_crf_expf_device works without a GPU); inference
+ * runs on the engine's GPU and leaves q there until it is read.  Results are bit-identical to the reference's.
+ * Handles: a frame handle stays valid until its frame is popped or its CRF freed.  Every entry point may be called from any thread;
+ * calls on one CRF (and its frames) are serialised by the CRF, fslic_hip_crf_inference takes one engine slot.
+ * Deliberate differences, each refused with FSLIC_E_INVALID where the reference has undefined behaviour:
+ *   - num_classes or num_nodes 0, num_classes * num_nodes >= 2^31 (new); frames * classes * nodes or the total number of
+ *     neighbour entries of the window >= 2^31 (inference);
+ *   - neighbour indices >= num_nodes (set_connectivity: the reference indexes q with them unchecked), more rows than nodes;
+ *   - a class outside [0, num_classes) (set_mask, get/set_compat), a node outside [0, num_nodes) (the energies);
+ *   - inference with max_iter > 0 and no frame (the reference dereferences a missing frame);
+ *   - a missing time (fslic_hip_crf_frame; the reference throws std::out_of_range through its C API).
+ * copy is a deep copy (the reference's copy constructor shares its frames' time map and parent with the original). */
+typedef struct fslic_crf fslic_crf;
+typedef struct fslic_crf_frame fslic_crf_frame;
+typedef struct fslic_crf_params {  /* SimpleCRFParams, src/simple-crf.h:11-19; defaults src/simple-crf.hpp:81-87 */
+    float spatial_w, temporal_w, spatial_srgb, temporal_srgb, spatial_sxy, spatial_smooth_w, spatial_smooth_sxy;
+} fslic_crf_params;
+
+int fslic_hip_crf_new(size_t num_classes, size_t num_nodes, fslic_crf** out);          /* simple_crf_new,  simple-crf.h:29 */
+void fslic_hip_crf_free(fslic_crf* crf);                                               /* simple_crf_free, simple-crf.h:31 */
+int fslic_hip_crf_copy(fslic_crf* crf, fslic_crf** out);                               /* simple_crf_copy, simple-crf.h:97 */
+int fslic_hip_crf_get_params(fslic_crf* crf, fslic_crf_params* out);                   /* simple-crf.h:33 */
+int fslic_hip_crf_set_params(fslic_crf* crf, const fslic_crf_params* params);          /* simple-crf.h:34 */
+int fslic_hip_crf_set_compat(fslic_crf* crf, int cls, float compat_value);             /* simple-crf.h:35 */
+int fslic_hip_crf_get_compat(fslic_crf* crf, int cls, float* out);                     /* simple-crf.h:36 */
+int fslic_hip_crf_num_classes(fslic_crf* crf, size_t* num_classes, size_t* num_nodes);  /* the sizes given to new */
+/* Times: -1 when there is no frame (simple-crf.h:38-39); pop returns the popped time or -1 (:41). */
+int fslic_hip_crf_first_time(fslic_crf* crf);
+int fslic_hip_crf_last_time(fslic_crf* crf);
+size_t fslic_hip_crf_num_frames(fslic_crf* crf);                                       /* simple-crf.h:40 */
+int fslic_hip_crf_pop_frame(fslic_crf* crf);
+int fslic_hip_crf_push_frame(fslic_crf* crf, fslic_crf_frame** out);                   /* simple-crf.h:42 */
+int fslic_hip_crf_frame(fslic_crf* crf, int time, fslic_crf_frame** out);              /* simple-crf.h:43 */
+int fslic_hip_crf_frame_time(fslic_crf_frame* frame);                                  /* simple-crf.h:44 */
+/* clusters: num_nodes fslic_cluster (simple-crf.h:51); get returns them as set (no counterpart in the C API: the pyx reads them). */
+int fslic_hip_crf_frame_set_clusters(fslic_crf_frame* frame, const fslic_cluster* clusters);
+int fslic_hip_crf_frame_get_clusters(fslic_crf_frame* frame, fslic_cluster* clusters);
+/* Neighbour lists (simple-crf.h:52, Connectivity of src/fast-slic-common.h:25-29): rows [0, num_rows) are replaced, others kept.
+ * Table form: row i is neighbors[i * stride + k], k < num_neighbors[i] (what fslic_hip_get_connectivity writes, stride 12);
+ * CSR form: row i is indices[offsets[i] .. offsets[i+1]).  Lists may be empty, longer than 12, hold duplicates and self-loops. */
+int fslic_hip_crf_frame_set_connectivity(fslic_crf_frame* frame, int num_rows, const int* num_neighbors, const uint32_t* neighbors,
+                                         size_t stride);
+int fslic_hip_crf_frame_set_connectivity_csr(fslic_crf_frame* frame, int num_rows, const int64_t* offsets, const uint32_t* indices);
+/* The lists as CSR: offsets[num_nodes + 1]; indices may be NULL to ask for the size only (offsets[num_nodes]). */
+int fslic_hip_crf_frame_get_connectivity(fslic_crf_frame* frame, int64_t* offsets, uint32_t* indices);
+/* Unaries, [num_classes][num_nodes] float (simple-crf.h:59-66). */
+int fslic_hip_crf_frame_set_mask(fslic_crf_frame* frame, const int32_t* classes, float confidence);
+int fslic_hip_crf_frame_set_proba(fslic_crf_frame* frame, const float* probas);
+int fslic_hip_crf_frame_set_unbiased(fslic_crf_frame* frame);
+int fslic_hip_crf_frame_set_unary(fslic_crf_frame* frame, const float* unary_energies);
+int fslic_hip_crf_frame_get_unary(fslic_crf_frame* frame, float* unary_energies);
+/* simple-crf.h:77-78.  The temporal energy is taken towards `other_frame` (any frame, of any CRF; 0 for the frame itself) as
+ * SimpleCRFFrame::calc_temporal_pairwise_energy does -- the reference's C wrapper passes the frame itself instead (always 0). */
+int fslic_hip_crf_frame_spatial_energy(fslic_crf_frame* frame, int node_i, int node_j, float* out);
+int fslic_hip_crf_frame_temporal_energy(fslic_crf_frame* frame, fslic_crf_frame* other_frame, int node_i, float* out);
+/* q, [num_classes][num_nodes] float (simple-crf.h:84-85); initialize resets every frame (simple-crf.h:30). */
+int fslic_hip_crf_frame_get_inferred(fslic_crf_frame* frame, float* probas);
+int fslic_hip_crf_frame_reset_inferred(fslic_crf_frame* frame);
+int fslic_hip_crf_initialize(fslic_crf* crf);
+/* simple_crf_inference (simple-crf.h:92): max_iter Jacobi sweeps over every frame, on the engine's GPU (one slot).  max_iter == 0
+ * does nothing and needs no engine.  A CRF keeps its device buffers on the engine of its last inference. */
+int fslic_hip_crf_inference(fslic_crf* crf, fslic_engine* e, size_t max_iter);
+/* Testing aids: the exponential the CRF uses (a copy of the host libm's expf, crf.h) over a batch of host floats, on the host
+ * (use_libm != 0: the host libm's expf itself, for comparison) or on the engine's GPU. */
+int fslic_hip_crf_expf_host(const float* in, float* out, size_t n, int use_libm);
+int fslic_hip_crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 

@@ -1,0 +1,248 @@
+"""SimpleCRF cases shared by the fixture maker (tests/golden/make_golden_crf.py, against the reference) and the tests (against this
+package): the case list, the deterministic inputs of a case, and one replay of a case against either implementation."""
+import json
+
+import numpy as np
+
+PARAM_NAMES = ("spatial_w", "temporal_w", "spatial_srgb", "temporal_srgb", "spatial_sxy", "spatial_smooth_w", "spatial_smooth_sxy")
+
+CHAIN_H, CHAIN_W, CHAIN_K = 120, 160, 100
+CHAIN_VARIANTS = ("A", "B", "C", "D")
+
+# graph: "none" (no neighbours), "small" (self-loops, duplicates), "random" (<= 12 random neighbours), "long" (up to 20 with
+# duplicates, empty lists, clusters with num_members 0), "slic150" / "slic300" (graph_cases.npz's reference clusters and
+# connectivity), "chain" (Slic on four frames, see make_golden_crf.chain_inputs)
+CASES = [
+    dict(name="k1_c2_t1", C=2, K=1, T=1, iters=[3], graph="none", umode=["unary"], init="initialize"),
+    dict(name="k3_c3_t2", C=3, K=3, T=2, iters=[10], graph="small", umode=["mask", "proba"], init="initialize"),
+    dict(name="k3_c2_t2_iter0", C=2, K=3, T=2, iters=[0], graph="small", umode=["unary"], init="initialize"),
+    dict(name="k150_c21_t4", C=21, K=150, T=4, iters=[10], graph="random", umode=["proba"], init="initialize"),
+    dict(name="k150_c3_t2_smooth", C=3, K=150, T=2, iters=[1], graph="random", umode=["unary"], init="initialize",
+         params=[3.5, 7.25, 9.0, 17.0, 31.0, 2.5, 4.5], compat=[0.5, 1.75, 1.0]),
+    dict(name="k1600_c2_t4_long", C=2, K=1600, T=4, iters=[3], graph="long", umode=["unary", "mask"], init="reset"),
+    dict(name="k150_c3_t3_slide", C=3, K=150, T=3, iters=[3, 3], graph="random", umode=["mask", "unbiased", "unary"],
+         init="initialize", slide=True),
+    dict(name="slic150_c21_t2", C=21, K=150, T=2, iters=[10], graph="slic150", umode=["mask"], init="initialize"),
+    dict(name="slic300_c3_t4", C=3, K=300, T=4, iters=[10], graph="slic300", umode=["unary"], init="initialize",
+         compat=[1.0, 0.25, 2.0]),
+    dict(name="chain_k100_c3_t4", C=3, K=CHAIN_K, T=4, iters=[10], graph="chain", umode=["mask"], init="initialize"),
+]
+CASE_NAMES = [c["name"] for c in CASES]
+CASE_BY_NAME = {c["name"]: c for c in CASES}
+
+
+def _csr(lists):
+    off = np.zeros(len(lists) + 1, np.int64)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    idx = np.array([v for l in lists for v in l], np.uint32)
+    return off, idx
+
+
+def make_inputs(case, rng, graph_npz=None, chain=None):
+    """Deterministic inputs of a case: one dict per pushed frame (clusters, off, idx, umode, udata, conf)."""
+    from fast_slic_amd._binding import CLUSTER_DTYPE
+    C, K, T = case["C"], case["K"], case["T"]
+    nframes = T + (1 if case.get("slide") else 0)
+    g = case["graph"]
+    chain_frames = chain() if g == "chain" else None
+    base = None
+    if g in ("slic150", "slic300"):
+        key = {"slic150": "slic_150x201_k150", "slic300": "slic_240x320_k300"}[g]
+        base = np.ascontiguousarray(graph_npz[key + "/clusters"]).view(CLUSTER_DTYPE).reshape(-1)
+        num, nb = graph_npz[key + "/conn_num"], graph_npz[key + "/conn_nb"]
+        base_lists = [list(nb[i, :num[i]]) for i in range(K)]
+    frames = []
+    for j in range(nframes):
+        if g == "chain":
+            cl, num, nb = chain_frames[j]
+            lists = [list(nb[i, :num[i]]) for i in range(K)]
+        elif base is not None:
+            cl = base.copy()
+            if j:
+                for ch in ("r", "g", "b"):            # the same superpixels with drifting colours
+                    cl[ch] = cl[ch] + rng.integers(-6, 7, K).astype(np.float32)
+            lists = base_lists
+        else:
+            cl = np.zeros(K, CLUSTER_DTYPE)
+            cl["y"] = rng.integers(0, 720, K).astype(np.float32) + rng.integers(0, 4, K) * np.float32(0.25)
+            cl["x"] = rng.integers(0, 1280, K).astype(np.float32) + rng.integers(0, 8, K) * np.float32(0.125)
+            for ch in ("r", "g", "b"):
+                cl[ch] = rng.integers(0, 256, K).astype(np.float32)
+            cl["number"] = np.arange(K)
+            cl["num_members"] = rng.integers(1, 900, K)
+            if g == "long":
+                cl["num_members"][rng.random(K) < 0.1] = 0
+            if g == "none":
+                lists = [[] for _ in range(K)]
+            elif g == "small":
+                lists = [[0, 1, 1], [1, 2, 0, 2], []] if K == 3 else [[i] for i in range(K)]
+            elif g == "random":
+                lists = [list(rng.choice(K, int(rng.integers(0, 13)), replace=False)) for _ in range(K)]
+            else:   # long
+                lists = []
+                for i in range(K):
+                    n = int(rng.integers(0, 21)) if rng.random() > 0.1 else 0
+                    l = list(rng.integers(0, K, n))
+                    if n > 2:
+                        l[1] = l[0]                   # a duplicate
+                        l[-1] = i                     # a self-loop
+                    lists.append(l)
+        off, idx = _csr(lists)
+        umode = case["umode"][j % len(case["umode"])]
+        conf = 0.0
+        if umode == "unary":
+            udata = rng.uniform(0.0, 4.0, (C, K)).astype(np.float32)
+        elif umode == "proba":
+            p = rng.uniform(0.01, 1.0, (C, K)).astype(np.float32)
+            udata = (p / p.sum(0, keepdims=True)).astype(np.float32)
+        elif umode == "mask":
+            udata = rng.integers(0, C, K).astype(np.int32)
+            conf = float(np.float32(rng.uniform(0.2, 0.9)))
+        else:
+            udata = np.zeros(0, np.float32)
+        frames.append(dict(clusters=np.ascontiguousarray(cl), off=off, idx=idx, umode=umode, udata=udata, conf=conf))
+    return frames
+
+
+def _fill(crf, f, fr):
+    crf.set_clusters(f, fr["clusters"])
+    crf.set_connectivity(f, fr["off"], fr["idx"])
+    crf.set_unary(f, fr["umode"], fr["udata"], fr["conf"])
+
+
+def replay(crf, case, frames, host_only=False):
+    """Run a case against `crf` (RefCRF of the maker or PkgCRF below); returns what the fixtures record.  host_only: stop before
+    the first inference with max_iter > 0 (what needs no GPU)."""
+    C, K, T = case["C"], case["K"], case["T"]
+    if case.get("params"):
+        crf.set_params(case["params"])
+    for cls, v in enumerate(case.get("compat") or []):
+        crf.set_compat(cls, v)
+    handles = []
+    for j in range(T):
+        f = crf.push()
+        _fill(crf, f, frames[j])
+        handles.append(f)
+    rec = {"unaries": [crf.unaries(f) for f in handles]}
+    f0 = handles[0]
+    fr0 = frames[0]
+    rec["spatial"] = np.array([crf.spatial(f0, int(fr0["idx"][k]), i) for i in range(K)
+                               for k in range(fr0["off"][i], fr0["off"][i + 1])], np.float32)
+    if T > 1:
+        rec["temporal"] = np.array([[crf.temporal(handles[0], handles[1], i) for i in range(K)],
+                                    [crf.temporal(handles[1], handles[0], i) for i in range(K)]], np.float32)
+    if case["init"] == "initialize":
+        crf.initialize()
+    else:
+        for f in handles[::2]:
+            crf.reset_inferred(f)
+    rec["q0"] = [crf.inferred(f) for f in handles]
+    if host_only and case["iters"][0] > 0:
+        return rec
+    crf.inference(case["iters"][0])
+    rec["steps"] = [[crf.inferred(f) for f in handles]]
+    if case.get("slide"):
+        crf.pop()
+        handles.pop(0)
+        f = crf.push()
+        _fill(crf, f, frames[T])
+        rec["unaries"].append(crf.unaries(f))
+        handles.append(f)
+        crf.inference(case["iters"][1])
+        rec["steps"].append([crf.inferred(f) for f in handles])
+    return rec
+
+
+def pack(case, frames, rec):
+    out = {"meta": np.array(json.dumps({k: v for k, v in case.items()}))}
+    for j, fr in enumerate(frames):
+        out["f%d/clusters" % j] = fr["clusters"].view(np.uint8).reshape(-1, 32)
+        out["f%d/off" % j] = fr["off"]
+        out["f%d/idx" % j] = fr["idx"]
+        out["f%d/udata" % j] = fr["udata"]
+        out["f%d/conf" % j] = np.float32(fr["conf"])
+        if fr["umode"] != "unary":
+            out["f%d/unaries" % j] = rec["unaries"][j]
+    out["spatial"] = rec["spatial"]
+    if "temporal" in rec:
+        out["temporal"] = rec["temporal"]
+    for j, q in enumerate(rec["q0"]):
+        out["q0/%d" % j] = q
+    for s, qs in enumerate(rec["steps"]):
+        for j, q in enumerate(qs):
+            out["step%d/%d" % (s, j)] = q
+    return out
+
+
+def unpack_frames(npz, name):
+    """The inputs of a case as make_inputs produced them (from the fixture; no reference needed)."""
+    from fast_slic_amd._binding import CLUSTER_DTYPE
+    case = json.loads(str(npz[name + "/meta"]))
+    frames = []
+    j = 0
+    while (name + "/f%d/off" % j) in npz.files:
+        frames.append(dict(clusters=np.ascontiguousarray(npz[name + "/f%d/clusters" % j]).view(CLUSTER_DTYPE).reshape(-1),
+                           off=npz[name + "/f%d/off" % j], idx=npz[name + "/f%d/idx" % j],
+                           umode=case["umode"][j % len(case["umode"])], udata=npz[name + "/f%d/udata" % j],
+                           conf=float(npz[name + "/f%d/conf" % j])))
+        j += 1
+    return case, frames
+
+
+class PkgCRF(object):
+    """fast_slic_amd.crf.SimpleCRF with the interface replay() drives."""
+
+    def __init__(self, C, K, device=0):
+        from fast_slic_amd.crf import SimpleCRF
+        self.crf = SimpleCRF(C, K, device=device)
+        self.C, self.K = C, K
+
+    def set_params(self, values):
+        for n, v in zip(PARAM_NAMES, values):
+            setattr(self.crf, n, v)
+
+    def set_compat(self, cls, v):
+        self.crf.set_compat(cls, v)
+
+    def push(self):
+        return self.crf.push_frame()
+
+    def pop(self):
+        return self.crf.pop_frame()
+
+    def set_clusters(self, f, cl):
+        f.set_clusters(cl)
+
+    def set_connectivity(self, f, off, idx):
+        f.set_connectivity([list(idx[off[i]:off[i + 1]]) for i in range(self.K)])
+
+    def set_unary(self, f, mode, data, conf):
+        if mode == "unary":
+            f.unaries = np.asarray(data, np.float32)
+        elif mode == "proba":
+            f.set_proba(np.asarray(data, np.float32))
+        elif mode == "mask":
+            f.set_mask(np.asarray(data, np.int32), conf)
+        else:
+            f.set_unbiased()
+
+    def unaries(self, f):
+        return f.unaries
+
+    def inferred(self, f):
+        return f.get_inferred()
+
+    def spatial(self, f, i, j):
+        return np.float32(f.spatial_pairwise_energy(i, j))
+
+    def temporal(self, f, other, i):
+        return np.float32(f.temporal_pairwise_energy(i, other))
+
+    def reset_inferred(self, f):
+        f.reset_inferred()
+
+    def initialize(self):
+        self.crf.initialize()
+
+    def inference(self, n):
+        self.crf.inference(n)
