@@ -44,7 +44,7 @@ EXPORTS = [
     "fslic_hip_last_device_times", "fslic_hip_set_launch_timing", "fslic_hip_last_assign_loop", "fslic_hip_last_group_frames", "fslic_hip_last_path", "fslic_hip_last_launch_mode", "fslic_hip_group_done", "fslic_hip_last_error", "fslic_hip_version",
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
-    "fslic_hip_separate_pass_redos", "fslic_hip_copy_bandwidth",
+    "fslic_hip_separate_pass_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
     # SimpleCRF (fast_slic_amd/crf.py)
     "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
     "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
@@ -129,6 +129,8 @@ def load_library():
         lib.fslic_hip_last_prelabels.argtypes = [vp, i32, vp]
         lib.fslic_hip_last_timing_report.argtypes = [vp]
         lib.fslic_hip_last_timing_report.restype = C.c_char_p
+        if hasattr(lib, "fslic_hip_last_recorder_report"):
+            lib.fslic_hip_last_recorder_report.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
         lib.fslic_hip_last_device_times.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.fslic_hip_set_launch_timing.argtypes = [vp, i32]
         lib.fslic_hip_last_assign_loop.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -345,6 +347,13 @@ class Engine(object):
 
     def last_timing_report(self):
         return load_library().fslic_hip_last_timing_report(self._h).decode("utf-8")
+
+    def last_recorder_report(self):
+        """The calling thread's last iterate() / iterate_device() recorder report as bytes (src/recorder.h's JSON): every snapshot
+        with params.debug_mode set, the header alone otherwise."""
+        p, n = C.c_char_p(), C.c_size_t()
+        _check(load_library().fslic_hip_last_recorder_report(self._h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value) if n.value else b""
 
     def last_device_times(self, slot=0):
         t, f = C.c_float(), C.c_float()
@@ -574,6 +583,7 @@ class SlicModel(object):
                         self.num_threads, self.debug_mode, variant)
         labels = self._engine.iterate(image, self._clusters, p)
         self.last_timing_report = self._engine.last_timing_report()
+        self.last_recorder_report = self._engine.last_recorder_report()     # bytes, after every call (pyx:196, :256)
         # pyx:258-260 makes an int16 copy and turns 0xFFFF into -1; the int16 VIEW of the same bytes is that array (0xFFFF is -1
         # already), without three passes over the map (250 us at 1280x720, more than the device-side work)
         return labels.view(np.int16)

@@ -14,6 +14,7 @@ void free_slot(Slot& s) {
     s.graphs.clear();
     if (s.arena) hipFree(s.arena);
     if (s.lsc_arena) hipFree(s.lsc_arena);
+    if (s.d_rec) hipFree(s.d_rec);
     if (s.h_lsc_lut) hipHostFree(s.h_lsc_lut);
     if (s.h_patchf) hipHostFree(s.h_patchf);
     if (s.h_clf) hipHostFree(s.h_clf);

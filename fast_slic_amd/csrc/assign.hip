@@ -1470,8 +1470,10 @@ static __device__ __forceinline__ void generic_test(const ClusterRec& rec, int y
     best = key < best ? key : best;
 }
 
-template <bool FUSE>
-__global__ __launch_bounds__(256) void k_assign_generic(FrameDev f, int rem, int stride, int Hv, int buf, int sbuf) {
+// REC (debug_mode, group.cpp "recording path"): also the pixel's minimum distance into `dist` (the reference's uint16
+// min_dists, src/context.cpp:199-205 / :289-294): the winning candidate's, or 0xFFFF where no window reaches the pixel.
+template <bool FUSE, bool REC>
+static __device__ __forceinline__ void assign_generic_body(FrameDev& f, int rem, int stride, int Hv, uint16_t* __restrict__ dist) {
     f.select(blockIdx.y);
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)Hv * f.W) return;
@@ -1495,19 +1497,30 @@ __global__ __launch_bounds__(256) void k_assign_generic(FrameDev f, int rem, int
     uint32_t lbl;
     if (best != ~0ull) { lbl = (uint32_t)(best & 0xFFFFull); f.labels[p] = (uint16_t)lbl; }
     else lbl = f.labels[p];
+    if (REC) dist[p] = best != ~0ull ? (uint16_t)(best >> 32) : (uint16_t)0xFFFFu;
     // preemptive mode: only pixels of active (2S x 2S) cells take part in the update unless every cluster is active
     // (src/context.cpp:304-343)
     if (FUSE && lbl != 0xFFFFu && (!f.cell_act || f.pre_flags[0] || f.cell_act[(y / (2 * S)) * f.pre_cw + x / (2 * S)]))
         global_accumulate(f.sums[0], lbl, (uint32_t)y, (uint32_t)x, pix);
 }
 
-void launch_assign_generic(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st) {
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_assign_generic(FrameDev f, int rem, int stride, int Hv, int buf, int sbuf) {
+    assign_generic_body<FUSE, false>(f, rem, stride, Hv, nullptr);
+}
+// the recording form (one frame per launch: `dist` is frame 0's plane)
+__global__ __launch_bounds__(256) void k_assign_generic_rec(FrameDev f, int rem, int stride, int Hv, uint16_t* dist) {
+    assign_generic_body<true, true>(f, rem, stride, Hv, dist);
+}
+
+void launch_assign_generic(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, uint16_t* rec_dist) {
     const FrameDev f = rotated(f_, buf, sbuf);
     const int Hv = (f.H - rem + stride - 1) / stride;
     if (Hv <= 0) return;
     const size_t n = (size_t)Hv * f.W;
     const int blocks = (int)((n + 255) / 256);
-    if (fuse_update) launch(k_assign_generic<true>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
+    if (rec_dist) launch(k_assign_generic_rec, dim3(blocks, 1), dim3(256), 0, st, f, rem, stride, Hv, rec_dist);
+    else if (fuse_update) launch(k_assign_generic<true>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
     else launch(k_assign_generic<false>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
 }
 

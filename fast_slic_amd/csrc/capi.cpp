@@ -82,8 +82,10 @@ int fslic_hip_iterate_device(fslic_engine* e, int slot, const fslic_params* p, i
     if (rc) return rc;
     Slot& s = e->slots[slot];
     s.launch_timing = e->launch_timing;
-    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_labels);
+    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_labels, p && p->debug_mode != 0);
     if (rc == FSLIC_OK) rc = group_finish(e, s);
+    std::string report;
+    if (rc == FSLIC_OK) rc = make_recorder_report(s, report);
     if (rc != FSLIC_OK) {            // a failure after a partial enqueue: nothing may still touch the caller's buffers on return
         const std::string msg = last_error();
         (void)hipStreamSynchronize(s.st);
@@ -92,6 +94,7 @@ int fslic_hip_iterate_device(fslic_engine* e, int slot, const fslic_params* p, i
         return rc;
     }
     set_thread_timing_report(make_timing_report(s));
+    set_thread_recorder_report(std::move(report));
     return rc;
 }
 
@@ -122,9 +125,11 @@ int fslic_hip_iterate(fslic_engine* e, const fslic_params* p, int H, int W, int 
     HIPCHK(hipMemcpyAsync(s.d_rgb_stage, rgb, N * 3, hipMemcpyHostToDevice, s.st));
     const double t1 = knobs().host_timing ? now_us() : 0.0;
     s.launch_timing = e->launch_timing;
-    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_out);
+    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_out, p->debug_mode != 0);
     const double t2 = knobs().host_timing ? now_us() : 0.0;
     if (rc == FSLIC_OK) rc = group_finish(e, s);
+    std::string report;
+    if (rc == FSLIC_OK) rc = make_recorder_report(s, report);
     if (rc != FSLIC_OK) {            // a failure after a partial enqueue: nothing may still run on the slot's stage buffers when the slot is released
         const std::string msg = last_error();
         (void)hipStreamSynchronize(s.st);
@@ -139,6 +144,18 @@ int fslic_hip_iterate(fslic_engine* e, const fslic_params* p, int H, int W, int 
         fprintf(stderr, "[fslic host] iterate: frame in %.1f us, group begin %.1f, group finish (wait + write-back) %.1f, labels out %.1f (device %.1f us)\n",
                 t1 - t0, t2 - t1, t3 - t2, now_us() - t3, s.total_ms * 1e3);
     set_thread_timing_report(make_timing_report(s));
+    set_thread_recorder_report(std::move(report));
+    return FSLIC_OK;
+}
+
+// The calling thread's recorder report (thread-local like the timing report: SlicModels on other threads sharing the engine do not
+// overwrite it).  Empty before the thread's first successful call.
+int fslic_hip_last_recorder_report(fslic_engine* e, const char** report, size_t* length) {
+    (void)e;
+    if (!report || !length) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const std::string& r = thread_recorder_report();
+    *report = r.c_str();
+    *length = r.size();
     return FSLIC_OK;
 }
 

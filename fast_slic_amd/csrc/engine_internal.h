@@ -202,6 +202,11 @@ struct Slot {
     bool sp_valid = false, sp_tiled_ok = false, sp_manhattan = true, sp_patch_uploaded = false;
     int sp_S = 0, sp_shift = 0, sp_stride = 0;
     float sp_compactness = 0.0f;
+    // debug_mode (group.cpp, "the recording path"): the snapshot ring of the current call (RecLayout), grown on demand and kept
+    bool recording = false;          // the current group is a recording one-frame call
+    char* d_rec = nullptr;
+    size_t d_rec_cap = 0;
+    std::vector<fslic_cluster> rec_clusters;   // the caller's Cluster block as it came in (snapshot -1, the unmoved positions)
 
     template <class T> T* at(T* p, int frame) const { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + (size_t)frame * frame_bytes); }
 };
@@ -269,12 +274,18 @@ int upload_ptrs(Slot& s, int n, const uint8_t* const* d_rgb, uint16_t* const* d_
 CcaDev cca_view(const Slot& s, int i0, const uint16_t* d_in0, size_t in_stride, int K, int min_threshold);
 void cca_enqueue(Slot& s, const CcaDev& c, int i0, int n, const ExportDev* ex = nullptr);
 int cca_finish_group(Slot& s, int first, int n, const uint16_t* d_in0, size_t in_stride, int K, int thres);
+// record: the recording path of debug_mode (one frame; only fslic_hip_iterate / fslic_hip_iterate_device ask for it)
 int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K, int n,
-                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out);
+                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out, bool record = false);
 int group_finish(fslic_engine* e, Slot& s);
 std::string make_timing_report(const Slot& s);
 void set_thread_timing_report(const std::string& json);
 const std::string& thread_timing_report();
+// The recorder report of a completed call (src/recorder.h): the ring of a recording call read back and formatted, the header
+// alone otherwise.  Kept per calling thread like the timing report.
+int make_recorder_report(Slot& s, std::string& out);
+void set_thread_recorder_report(std::string&& json);
+const std::string& thread_recorder_report();
 
 // ---- pipeline.cpp ----
 // Synchronous calls take a slot for their duration (they wait while every slot is taken; a slot with an uncollected

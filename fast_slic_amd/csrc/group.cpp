@@ -7,6 +7,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <charconv>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -206,6 +207,32 @@ static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, 
     return fuse_wanted && !separate_cluster_pass && plain_slic && !generic && every_pass_has_rows && assign_fuses_cluster_pass(f, stride);
 }
 
+// ---- debug_mode: the recording path ----
+// A call with debug_mode set (fslic_hip_iterate / fslic_hip_iterate_device; one frame) is enqueued directly, never as a graph, on the
+// generic / unfused kernels with the label plane reset eagerly, and records what src/context.cpp:155-174 hands to its Recorder
+// (src/recorder.h): snapshot -1 after the colour fetch, then one after every assign + update.  The assign launches of the loop take
+// their recording forms, which write every visited pixel's minimum distance straight into the snapshot's distance plane (filled
+// with the type's maximum beforehand: the reference resets min_dists over the whole frame in every assign(), src/context.cpp:199-205;
+// snapshot -1's plane is the zeroed allocation of the reference, src/simd-helper.hpp:62-70).  After every cluster pass async copies
+// put the label plane and the cluster state into the ring; the host reads the ring back once and formats the JSON.
+// Ring: labels[nsnap][N] u16 | dists[nsnap][N] (u16 for Slic, f32 for the variants) | cluster state[nsnap][kRecWords * K] u32, the
+// state as SoA: [0,K) position, [K,2K) colour, [2K,3K) num_members, [3K,4K) moved, [4K,5K) is_updatable, [5K,6K) is_active (preemptive
+// mode), [6K,14K) the float centroids ('noq').
+constexpr int kRecWords = 16;
+struct RecLayout {
+    size_t N, K, nsnap, dsize, dist_off, cl_off, bytes;
+};
+static RecLayout rec_layout(const Slot& s) {
+    RecLayout L{};
+    L.N = (size_t)s.H * s.W; L.K = (size_t)s.K; L.nsnap = (size_t)s.p.max_iter + 1;
+    L.dsize = s.p.variant == FSLIC_VARIANT_SLIC ? 2 : 4;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    L.dist_off = up(L.nsnap * L.N * 2);
+    L.cl_off = L.dist_off + up(L.nsnap * L.N * L.dsize);
+    L.bytes = L.cl_off + up(L.nsnap * kRecWords * L.K * 4);
+    return L;
+}
+
 // Device half: everything of iterate() for frames [i0, i0+n) of the slot's current group, enqueued asynchronously on
 // the slot's stream: LAB, the first cluster pass (reads the staged centres), the assign/update loop, full assign,
 // connectivity, export of the cluster state.  Pure
@@ -281,6 +308,37 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         HIPCHK(clear_rows(s.lsc_zero + (size_t)i0 * s.lsc_frame_bytes, s.lsc_frame_bytes, s.lsc_zero_bytes, (size_t)n, s.st));
         launch_lsc_prepare(f, l, n, s.st);                        // before_iteration, src/lsc.cpp:12-15
     }
+    // debug_mode: snapshot `idx` (iteration idx - 1) of the label plane and the cluster state into the ring; `dist(idx)` is the
+    // snapshot's distance plane, which the recording assign kernels write
+    const bool rec = s.recording && n == 1;
+    const RecLayout rl = rec ? rec_layout(s) : RecLayout{};
+    auto rec_dist = [&](int idx) -> void* { return rec ? s.d_rec + rl.dist_off + (size_t)idx * rl.N * rl.dsize : nullptr; };
+    auto snapshot = [&](int idx, const uint32_t* yx) -> int {
+        HIPCHK(hipMemcpyAsync(s.d_rec + (size_t)idx * rl.N * 2, f.labels, rl.N * 2, hipMemcpyDeviceToDevice, s.st));
+        uint32_t* c = reinterpret_cast<uint32_t*>(s.d_rec + rl.cl_off) + (size_t)idx * kRecWords * K;
+        const size_t kb = sizeof(uint32_t) * (size_t)K;
+        HIPCHK(hipMemcpyAsync(c, yx, kb, hipMemcpyDeviceToDevice, s.st));
+        HIPCHK(hipMemcpyAsync(c + K, f.cl_lab, kb, hipMemcpyDeviceToDevice, s.st));
+        HIPCHK(hipMemcpyAsync(c + 2 * (size_t)K, f.cl_n, kb, hipMemcpyDeviceToDevice, s.st));
+        HIPCHK(hipMemcpyAsync(c + 3 * (size_t)K, f.cl_moved, kb, hipMemcpyDeviceToDevice, s.st));
+        if (pre) {
+            HIPCHK(hipMemcpyAsync(c + 4 * (size_t)K, f.cl_upd, kb, hipMemcpyDeviceToDevice, s.st));
+            HIPCHK(hipMemcpyAsync(c + 5 * (size_t)K, f.cl_act, kb, hipMemcpyDeviceToDevice, s.st));
+        }
+        if (noq) HIPCHK(hipMemcpyAsync(c + 6 * (size_t)K, f.cl_f, 8 * kb, hipMemcpyDeviceToDevice, s.st));
+        return FSLIC_OK;
+    };
+    if (rec) {
+        // distance planes: -1 zero, 0 .. max_iter-1 the type's maximum; cluster state zero
+        HIPCHK(hipMemsetAsync(s.d_rec + rl.dist_off, 0, rl.N * rl.dsize, s.st));
+        if (p->max_iter > 0) {
+            if (rl.dsize == 2) HIPCHK(hipMemsetAsync(rec_dist(1), 0xFF, (size_t)p->max_iter * rl.N * 2, s.st));
+            else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)rec_dist(1), 0x7F7FFFFFu, (size_t)p->max_iter * rl.N, s.st));     // FLT_MAX
+        }
+        HIPCHK(hipMemsetAsync(s.d_rec + rl.cl_off, 0, rl.nsnap * kRecWords * rl.K * 4, s.st));
+        const int rc = snapshot(0, yx_up);              // after the colour fetch, the label reset and before_iteration()
+        if (rc) return rc;
+    }
     const bool rd = p->variant == FSLIC_VARIANT_REALDIST || p->variant == FSLIC_VARIANT_REALDIST_L2 || noq;
     const bool rd_l2 = p->variant == FSLIC_VARIANT_REALDIST_L2;
     float noq_coef = 1.0f / ((float)S / p->compactness);        // src/context.cpp:463-464
@@ -291,8 +349,9 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
         f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
-        if (noq) launch_noq_assign(f, noq_coef, noq_manhattan, n, rem, stride, it & 1, it & 1, true, s.st);
-        else launch_rd_assign(f, s.d_patchf, rd_l2, n, rem, stride, it & 1, it & 1, true, s.st);
+        float* const dist = static_cast<float*>(rec_dist(it + 1));
+        if (noq) launch_noq_assign(f, noq_coef, noq_manhattan, n, rem, stride, it & 1, it & 1, true, s.st, dist);
+        else launch_rd_assign(f, s.d_patchf, rd_l2, n, rem, stride, it & 1, it & 1, true, s.st, dist);
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
         launch_member_sums(f, n, rem, stride, it & 1, noq ? 1 : 0, s.st);
         f.gen_off++;
@@ -300,13 +359,14 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         if (pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, pre_l1_thres, s.st);      // update() + set_new_clusters(), src/context.cpp:356-387
         else launch_bin_clusters(f, n, 1, (it + 1) & 1, it & 1, pg, s.st);
         yx_cur = f.cl_yx_out;
+        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
         rem = (rem + 1) % stride;
     }
     for (int it = 0; lsc && it < p->max_iter; it++) {           // src/context.cpp:158-175 with ContextLSC's hooks
         const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
         f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
-        launch_lsc_assign(f, l, n, rem, stride, it & 1, it & 1, !pre, s.st);      // (preemptive: the assignment alone, the sums follow)
+        launch_lsc_assign(f, l, n, rem, stride, it & 1, it & 1, !pre, s.st, static_cast<float*>(rec_dist(it + 1)));      // (preemptive: the assignment alone, the sums follow)
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
         if (pre) {
             // update() under the activity state the pass started with, set_new_clusters(), then after_update() under the new one
@@ -321,6 +381,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
             launch_bin_clusters_lsc(f, l, n, (it + 1) & 1, it & 1, s.st);   // update() sums + after_update(), re-binning: one launch
         }
         yx_cur = f.cl_yx_out;
+        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
         rem = (rem + 1) % stride;
     }
     // The cluster pass between two assign passes (centroids from the sums, re-binning) is done by the assign kernel itself where
@@ -353,7 +414,8 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         // (preemptive mode: the block kernel on the bins of the active clusters where the geometry takes it, round 5; until then the
         // generic kernel served every preemptive frame)
         f.fv_mod = lazy_labels && it < stride ? 1 : 0; f.fv_from = 0;
-        if (generic || (pre && !launch_assign_pre(f, n, rem, stride, it & 1, it & 1, s.st))) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st);
+        if (rec) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st, static_cast<uint16_t*>(rec_dist(it + 1)));     // (rec: generic)
+        else if (generic || (pre && !launch_assign_pre(f, n, rem, stride, it & 1, it & 1, s.st))) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st);
         else if (!pre) pg = launch_assign(f, n, rem, stride, it & 1, it & 1, true, s.st);
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
         f.gen_off++;
@@ -361,6 +423,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         if (pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, pre_l1_thres, s.st);     // update() + set_new_clusters()
         else launch_bin_clusters(f, n, 1, (it + 1) & 1, it & 1, pg, s.st);
         yx_cur = f.cl_yx_out;
+        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
         rem = (rem + 1) % stride;
     }
     int full_buf = p->max_iter & 1;
@@ -423,6 +486,8 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
     }
     // Per-launch timing wants real event records between the launches; events replayed inside a graph keep the time
     // stamps of an earlier execution.  Timed groups therefore take the direct path.
+    // (debug_mode: the recording path, always direct)
+    if (s.recording) return enqueue_frames(e, s, 0, n, s.generic, true, true);
     if (!knobs().use_graphs || s.launch_timing) return enqueue_frames(e, s, 0, n, s.generic, true);
     // everything a launch argument can depend on
     std::vector<unsigned char> key;
@@ -471,12 +536,14 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
 }
 
 int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K, int n,
-                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out) {
+                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out, bool record) {
     const double t_begin = now_us();
     int S = 0;
+    s.recording = false;
     int rc = validate(p, H, W, K, S);
     if (rc) return rc;
     if (n < 1 || n > kMaxGroup) return fail(FSLIC_E_INTERNAL, "bad group size");
+    if (record && n != 1) return fail(FSLIC_E_INTERNAL, "a recording group holds one frame");
     for (int i = 0; i < n; i++)
         if (!clusters[i] || !d_rgb[i] || !d_out[i]) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     rc = ensure_prepared(e, s, H, W, K, S, n);           // (carves for at least the engine's batching reserve)
@@ -502,7 +569,22 @@ int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, i
     }
     rc = upload_ptrs(s, n, d_rgb, d_out);
     if (rc) return rc;
-    s.generic = p->variant == FSLIC_VARIANT_SLIC && (e->lab_force_generic.load() != 0 || !s.sp_tiled_ok);
+    if (record) {
+        s.rec_clusters.assign(clusters[0], clusters[0] + K);
+        s.recording = true;       // (before rec_layout: it reads s.H, s.W, s.K, s.p)
+        const size_t need = rec_layout(s).bytes;
+        if (s.d_rec_cap < need) {
+            if (s.d_rec) HIPCHK(hipFree(s.d_rec));
+            s.d_rec = nullptr; s.d_rec_cap = 0;
+            if (hipMalloc((void**)&s.d_rec, need) != hipSuccess) {
+                (void)hipGetLastError();
+                s.recording = false;
+                return fail(FSLIC_E_HIP, "debug_mode: hipMalloc of the snapshot ring (" + std::to_string(need) + " bytes) failed");
+            }
+            s.d_rec_cap = need;
+        }
+    }
+    s.generic = p->variant == FSLIC_VARIANT_SLIC && (e->lab_force_generic.load() != 0 || !s.sp_tiled_ok || record);
     if (p->preemptive && s.h_upd_words < (size_t)s.cap_frames * K) {
         if (s.h_upd) hipHostFree(s.h_upd);
         s.h_upd = nullptr; s.h_upd_words = 0;
@@ -657,8 +739,105 @@ std::string make_timing_report(const Slot& s) {
 
 namespace {
 thread_local std::string t_timing;
+thread_local std::string t_recorder;
+
+// Numbers as std::stringstream << prints them (src/recorder.h): integers in decimal, floats as printf's %g at precision 6 (what
+// to_chars does with chars_format::general and a precision).  Every call has room for the longest form.
+inline char* put_u(char* o, uint64_t v) { return std::to_chars(o, o + 24, v).ptr; }
+inline char* put_i(char* o, int64_t v) { return std::to_chars(o, o + 24, v).ptr; }
+inline char* put_f(char* o, float v) { return std::to_chars(o, o + 32, (double)v, std::chars_format::general, 6).ptr; }
+inline char* put_s(char* o, const char* s) { const size_t n = strlen(s); memcpy(o, s, n); return o + n; }
+inline char* header(char* o, int H, int W) {
+    o = put_s(o, "{\"height\": "); o = put_i(o, H);
+    o = put_s(o, ", \"width\": "); o = put_i(o, W);
+    return put_s(o, ", \"snapshots\": [");
 }
+}  // namespace
+
 void set_thread_timing_report(const std::string& json) { t_timing = json; }
 const std::string& thread_timing_report() { return t_timing; }
+void set_thread_recorder_report(std::string&& json) { t_recorder = std::move(json); }
+const std::string& thread_recorder_report() { return t_recorder; }
+
+// RecorderSnapshot::gen / Recorder::gen (src/recorder.h) over the ring of the slot's last call, after group_finish.  The Cluster view of
+// a snapshot is the reference's Cluster[K] at that moment: snapshot -1 holds the caller's block with the fetched colours and
+// is_updatable = cooldown (PreemptiveGrid::initialize, src/preemptive.h:59-66); after an update a cluster that has moved (an update
+// with members) sits at its centroid, one that has not at the caller's position clamped by assign()'s safeguard (src/context.cpp:208-211).
+int make_recorder_report(Slot& s, std::string& out) {
+    const int H = s.H, W = s.W, K = s.K;
+    if (!s.recording) {
+        char buf[96];
+        char* o = header(buf, H, W);
+        o = put_s(o, "]}");
+        out.assign(buf, o);
+        return FSLIC_OK;
+    }
+    const RecLayout L = rec_layout(s);
+    std::vector<char> ring(L.bytes);
+    HIPCHK(hipMemcpyAsync(ring.data(), s.d_rec, L.bytes, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(hipStreamSynchronize(s.st));
+    const bool pre = s.p.preemptive != 0, noq = s.p.variant == FSLIC_VARIANT_REALDIST_NOQ;
+    const size_t per_dist = L.dsize == 2 ? 6 : 16;       // ",65535" / ",3.40282e+38"
+    out.resize(96 + L.nsnap * (96 + L.K * 320 + L.N * (6 + per_dist)));
+    char* const o0 = &out[0];
+    char* o = header(o0, H, W);
+    const fslic_cluster* const cin = s.rec_clusters.data();
+    for (size_t i = 0; i < L.nsnap; i++) {
+        if (i) *o++ = ',';
+        o = put_s(o, "{\"iteration\": "); o = put_i(o, (int64_t)i - 1);
+        o = put_s(o, ", \"clusters\": [");
+        const uint32_t* c = reinterpret_cast<const uint32_t*>(ring.data() + L.cl_off) + i * kRecWords * L.K;
+        for (int k = 0; k < K; k++) {
+            const fslic_cluster& a = cin[k];
+            const uint32_t lab = c[K + k];
+            float y = a.y, x = a.x, r = (float)(lab & 255u), g = (float)((lab >> 8) & 255u), b = (float)((lab >> 16) & 255u);
+            uint32_t upd = 2, act = a.is_active, nm = a.num_members;
+            if (i > 0) {
+                if (c[3 * (size_t)K + k] && noq) {
+                    const float* cf = reinterpret_cast<const float*>(c + 6 * (size_t)K) + 8 * (size_t)k;
+                    y = cf[0]; x = cf[1]; r = cf[2]; g = cf[3]; b = cf[4];
+                } else if (c[3 * (size_t)K + k]) {
+                    y = (float)(c[k] >> 16); x = (float)(c[k] & 0xFFFFu);
+                } else {
+                    x = clampf(a.x, 0.0f, (float)(W - 1)); y = clampf(a.y, 0.0f, (float)(H - 1));
+                }
+                nm = c[2 * (size_t)K + k];
+                if (pre) { upd = c[4 * (size_t)K + k]; act = c[5 * (size_t)K + k]; }
+            }
+            if (k) *o++ = ',';
+            o = put_s(o, "{\"yx\": ["); o = put_f(o, y); *o++ = ','; o = put_f(o, x);
+            o = put_s(o, "], \"color\": ["); o = put_f(o, r); *o++ = ','; o = put_f(o, g); *o++ = ','; o = put_f(o, b);
+            o = put_s(o, "], \"is_updatable\": "); o = put_u(o, (uint8_t)upd);
+            o = put_s(o, ", \"is_active\": "); o = put_u(o, (uint8_t)act);
+            o = put_s(o, ", \"number\": "); o = put_u(o, a.number);
+            o = put_s(o, ", \"num_members\": "); o = put_u(o, nm);
+            *o++ = '}';
+        }
+        o = put_s(o, "], \"assignment\": [");
+        const uint16_t* lb = reinterpret_cast<const uint16_t*>(ring.data()) + i * L.N;
+        for (size_t q = 0; q < L.N; q++) {
+            if (q) *o++ = ',';
+            o = put_u(o, lb[q]);
+        }
+        o = put_s(o, "], \"min_dists\": [");
+        if (L.dsize == 2) {
+            const uint16_t* d = reinterpret_cast<const uint16_t*>(ring.data() + L.dist_off) + i * L.N;
+            for (size_t q = 0; q < L.N; q++) {
+                if (q) *o++ = ',';
+                o = put_u(o, d[q]);
+            }
+        } else {
+            const float* d = reinterpret_cast<const float*>(ring.data() + L.dist_off) + i * L.N;
+            for (size_t q = 0; q < L.N; q++) {
+                if (q) *o++ = ',';
+                o = put_f(o, d[q]);
+            }
+        }
+        o = put_s(o, "]}");
+    }
+    o = put_s(o, "]}");
+    out.resize((size_t)(o - o0));
+    return FSLIC_OK;
+}
 
 }  // namespace fslic

@@ -281,27 +281,35 @@ PassGeom launch_assign(const FrameDev& f, int nframes, int rem, int stride, int 
 // geometries assign_fuses_cluster_pass() accepts; positions live in FrameDev::cl_yx (updated in place).
 bool assign_fuses_cluster_pass(const FrameDev& f, int stride);
 void launch_assign_fused_bin(const FrameDev& f, int nframes, int rem, int stride, int it, hipStream_t st);
-void launch_assign_generic(const FrameDev& f, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st);
+// rec_dist != nullptr (debug_mode, one frame, fuse_update): the recording kernel, which also writes every visited pixel's
+// minimum distance (uint16, 0xFFFF where no window reaches it) into that plane -- the reference's min_dists
+void launch_assign_generic(const FrameDev& f, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st,
+                           uint16_t* rec_dist = nullptr);
 // preemptive mode (src/preemptive.h), Slic variant: the fused pass of the block kernel on the bins of the ACTIVE clusters, sums of the
 // pixels of active cells into FrameDev::sums (global atomics per block and cluster); false: geometry outside the block kernel
 bool launch_assign_pre(const FrameDev& f, int nframes, int rem, int stride, int buf, int sbuf, hipStream_t st);
 // LSC variant (lsc.hip).  prepare: feature means + seed centroids (src/lsc.cpp:12-15), after LAB and the mode-0 cluster pass.
 void launch_lsc_prepare(const FrameDev& f, const LscDev& l, int nframes, hipStream_t st);
 // 10-D assignment of rows == rem (mod stride) (src/lsc.cpp:197-224); stale_sums: an update follows
-void launch_lsc_assign(const FrameDev& f, const LscDev& l, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st);
+// (rec_dist: as for launch_assign_generic, an f32 plane)
+void launch_lsc_assign(const FrameDev& f, const LscDev& l, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st,
+                       float* rec_dist = nullptr);
 // per-cluster gather of the integer sums (into FrameDev::sums) and the weighted feature means (src/lsc.cpp:226-307)
 // LSC in preemptive mode (lsc.hip): the integer sums of update() over the visited pixels of the active cells (before
 // launch_preempt_update); the weighted feature sums and the centroids of after_update() under the NEW activity state (after it)
 void launch_lsc_pre_sums(const FrameDev& f, int nframes, int rem, int stride, int sbuf, hipStream_t st);
 void launch_lsc_pre_feats(const FrameDev& f, const LscDev& l, int nframes, int rem, int stride, hipStream_t st);
 // Float-distance variants (realdist.hip): patchf = (2S+1)^2 f32 spatial patch; l2: squared colour / spatial terms
-void launch_rd_assign(const FrameDev& f, const float* patchf, bool l2, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st);
+// (rec_dist: as for launch_assign_generic, an f32 plane; the same for launch_noq_assign)
+void launch_rd_assign(const FrameDev& f, const float* patchf, bool l2, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st,
+                      float* rec_dist = nullptr);
 // integer member sums per cluster (gather over the cluster window) into FrameDev::sums, for the variants whose assign
 // kernel does not accumulate them itself
 // margin: the window scanned is (2(S+margin)+1)^2 (the assign kernel's out-of-window rule must use the same margin)
 void launch_member_sums(const FrameDev& f, int nframes, int rem, int stride, int sbuf, int margin, hipStream_t st);
 // 'noq' variant (ContextRealDistNoQ, src/context.cpp:449-499): distances from float centroids (FrameDev::cl_f)
-void launch_noq_assign(const FrameDev& f, float coef, bool manhattan, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st);
+void launch_noq_assign(const FrameDev& f, float coef, bool manhattan, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st,
+                       float* rec_dist = nullptr);
 // preemptive mode (preempt.hip): centroid update of the updatable clusters, activity marking, bins of the active clusters;
 // rebin_all: bins of ALL clusters at their current positions (before the full assignment, src/preemptive.h:69-74)
 void launch_preempt_update(const FrameDev& f, int nframes, int buf, int sbuf, bool rebin_all, float l1_thres, hipStream_t st);

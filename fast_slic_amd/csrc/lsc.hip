@@ -220,8 +220,10 @@ __global__ __launch_bounds__(256) void k_lsc_seed(FrameDev f, LscDev l) {
 #else
 #define LSC_STAMP(i_, cond_) do { } while (0)
 #endif
-template <bool stale_sums>
-static __device__ __forceinline__ void lsc_assign_body(FrameDev& f, LscDev& l, int rem, int stride, int Hv) {
+// REC (debug_mode, group.cpp "recording path"): also every visited pixel's minimum distance into `dist` (f32, FLT_MAX where no window
+// reaches the pixel; one frame per launch)
+template <bool stale_sums, bool REC = false>
+static __device__ __forceinline__ void lsc_assign_body(FrameDev& f, LscDev& l, int rem, int stride, int Hv, float* __restrict__ dist = nullptr) {
     f.select(blockIdx.z);
     l.select(blockIdx.z);
     __shared__ uint32_t s_yx[64], s_k[64];
@@ -538,6 +540,7 @@ static __device__ __forceinline__ void lsc_assign_body(FrameDev& f, LscDev& l, i
             if (!xok || vw + r >= Hv) continue;
             const uint32_t bk = u ? bk1 : bk0;
             const size_t p = (size_t)yr[r] * W + x;
+            if (REC) dist[p] = best[u];
             if (best[u] < FLT_MAX) {
                 lbl[u] = listed ? s_k[bk] : bk;
                 st_stream(f.labels + p, (uint16_t)lbl[u]);
@@ -699,6 +702,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_lsc_assign_sums(FrameDev f, LscDev l, int rem, int stride, int Hv) {
     lsc_assign_body<true>(f, l, rem, stride, Hv);
 }
+// the recording forms of the two
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_lsc_assign_rec(FrameDev f, LscDev l, int rem, int stride, int Hv, float* dist) {
+    lsc_assign_body<false, true>(f, l, rem, stride, Hv, dist);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_lsc_assign_sums_rec(FrameDev f, LscDev l, int rem, int stride, int Hv, float* dist) {
+    lsc_assign_body<true, true>(f, l, rem, stride, Hv, dist);
+}
 
 // ---- preemptive mode (src/preemptive.h with ContextLSC's hooks) ------------------------------------------------------------------
 // The reference's update() sums the visited pixels of the ACTIVE cells as they stood before the pass (src/context.cpp:304-343), then
@@ -782,12 +792,17 @@ void launch_lsc_prepare(const FrameDev& f, const LscDev& l, int nframes, hipStre
     launch(k_lsc_seed, dim3((f.K + 3) / 4, nframes), dim3(256), 0, st, f, l);
 }
 
-void launch_lsc_assign(const FrameDev& f_, const LscDev& l, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st) {
+void launch_lsc_assign(const FrameDev& f_, const LscDev& l, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st,
+                       float* rec_dist) {
     const FrameDev f = rotated(f_, buf, sbuf);
     const int Hv = (f.H - rem + stride - 1) / stride;
     if (Hv <= 0) return;
     const dim3 grid((f.W + 63) / 64, (Hv + kLscBH - 1) / kLscBH, nframes);
-    if (stale_sums) launch(k_lsc_assign_sums, grid, dim3(256), 0, st, f, l, rem, stride, Hv);
+    if (rec_dist) {
+        const dim3 grid1(grid.x, grid.y, 1);
+        if (stale_sums) launch(k_lsc_assign_sums_rec, grid1, dim3(256), 0, st, f, l, rem, stride, Hv, rec_dist);
+        else launch(k_lsc_assign_rec, grid1, dim3(256), 0, st, f, l, rem, stride, Hv, rec_dist);
+    } else if (stale_sums) launch(k_lsc_assign_sums, grid, dim3(256), 0, st, f, l, rem, stride, Hv);
     else launch(k_lsc_assign, grid, dim3(256), 0, st, f, l, rem, stride, Hv);
 }
 

@@ -59,7 +59,8 @@ typedef struct fslic_params {
     int32_t preemptive;            /* src/context.h:32, src/preemptive.h; every variant (BaseContext<DistType>::iterate, src/context.cpp:152-181) */
     float preemptive_thres;        /* src/context.h:33; ignored while preemptive == 0 */
     int32_t num_threads;           /* src/context.h:27; ignored on the GPU */
-    int32_t debug_mode;            /* src/context.h:36; ignored (no recorder report) */
+    int32_t debug_mode;            /* src/context.h:36; fslic_hip_iterate / fslic_hip_iterate_device record the reference's per-iteration
+                                    * report (fslic_hip_last_recorder_report); the group and pipeline entries ignore it */
     int32_t abi;                   /* must be FSLIC_PARAMS_ABI: the layout of this struct has changed between library versions (a testing
                                     * flag lived in this slot in 0.2 and `variant` in the header of 0.2+); a caller built against
                                     * another layout is refused with FSLIC_E_INVALID instead of being misread */
@@ -199,6 +200,15 @@ int fslic_hip_last_prelabels(fslic_engine* e, int slot, uint16_t* prelabels);
  * fslic_hip_iterate* / fslic_hip_wait_group (thread-local like the reference's timer, src/timer.cpp:45).  Pointer
  * valid until that thread's next call. */
 const char* fslic_hip_last_timing_report(fslic_engine* e);
+
+/* Replaces BaseContext::get_recorder_report (src/context.h; the JSON of src/recorder.h, as cfast_slic.pyx:196 / :256 store it in
+ * SlicModel.last_recorder_report): the report of the CALLING THREAD's last successful fslic_hip_iterate / fslic_hip_iterate_device.
+ * With fslic_params.debug_mode set it holds snapshot -1 and one snapshot per iteration (labels before connectivity, min_dists, the
+ * Cluster[K] block of that moment), byte for byte what the reference prints; otherwise the header alone,
+ * {"height": H, "width": W, "snapshots": []}.  Such a call runs the recording path (one frame, direct launches, the generic / unfused
+ * kernels; same results, slower).  fslic_hip_iterate_batch, fslic_hip_submit_group and fslic_hip_pipeline_submit ignore debug_mode
+ * and leave the report alone.  *report is NUL-terminated, *length its size; it stays valid until the thread's next iterate call. */
+int fslic_hip_last_recorder_report(fslic_engine* e, const char** report, size_t* length);
 
 /* Device time (ms, HIP events on the slot's stream) of the last frame GROUP on `slot`: whole pipeline, and
  * the full-assign launch alone (the roofline kernel; it covers every frame of the group).  */
