@@ -55,6 +55,8 @@ EXPORTS = [
     "fslic_hip_crf_frame_get_unary", "fslic_hip_crf_frame_spatial_energy", "fslic_hip_crf_frame_temporal_energy",
     "fslic_hip_crf_frame_get_inferred", "fslic_hip_crf_frame_reset_inferred", "fslic_hip_crf_initialize", "fslic_hip_crf_inference",
     "fslic_hip_crf_expf_host", "fslic_hip_crf_expf_device",
+    # superpixel pooling (fast_slic_amd/pool.py)
+    "fslic_hip_pool_workspace_size", "fslic_hip_pool", "fslic_hip_pool_finalize", "fslic_hip_unpool",
 ]
 
 _lib = None
@@ -147,6 +149,8 @@ def load_library():
         lib.fslic_hip_cluster_density_to_mask.argtypes = [vp, i32, i32, i32, vp, vp, vp]
         if hasattr(lib, "fslic_hip_crf_new"):
             _declare_crf(lib)
+        if hasattr(lib, "fslic_hip_pool"):
+            _declare_pool(lib)
         _lib = lib
         return lib
 
@@ -173,6 +177,17 @@ def _declare_crf(lib):
     lib.fslic_hip_crf_free.restype = None
     lib.fslic_hip_crf_num_frames.argtypes = [vp]
     lib.fslic_hip_crf_num_frames.restype = sz
+
+
+def _declare_pool(lib):
+    """Signatures of the superpixel pooling entry points (include/fslic_hip.h)."""
+    vp, i32 = C.c_void_p, C.c_int
+    lib.fslic_hip_pool_workspace_size.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]
+    lib.fslic_hip_pool.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, C.c_size_t]
+    lib.fslic_hip_pool_finalize.argtypes = [i32, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.fslic_hip_unpool.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, C.c_float, vp]
+    for name in ("pool_workspace_size", "pool", "pool_finalize", "unpool"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _raise(rc):

@@ -321,6 +321,33 @@ int fslic_hip_crf_inference(fslic_crf* crf, fslic_engine* e, size_t max_iter);
 int fslic_hip_crf_expf_host(const float* in, float* out, size_t n, int use_libm);
 int fslic_hip_crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n);
 
+/* ---- Superpixel pooling (NEW surface, no counterpart in the reference; Python: fast_slic_amd/pool.py) ----
+ * Pooling of float feature planes over a label map, and the inverse broadcast, on device memory the caller owns.  No engine: each
+ * entry takes a device index and a stream (a hipStream_t; NULL is the default stream), enqueues its work on that stream and returns
+ * without synchronising and without allocating.  The calling thread's current device is restored.  Every argument is checked before
+ * the first HIP call (FSLIC_E_INVALID).
+ *   features : float [N][C][H][W], contiguous          labels : [N][H][W] of label_type; values outside [0, K) belong to no segment
+ *   values   : float [N][C][K]                          counts : int32 [N][K]              argmax : int32 [N][C][K]
+ * Results are bitwise reproducible: per-tile float partials in a fixed order, combined exactly in a fixed-point accumulator with
+ * integer atomics and rounded once (sum within 4e-6 of the sum of |x|; exact when every partial sum is exact in f32).
+ * The workspace holds N * C * K * 56 bytes (sum, mean) or N * C * K * 8 bytes (max), plus N * K * 4 bytes of counts (rounded up to 8). */
+enum { FSLIC_POOL_SUM = 0, FSLIC_POOL_MEAN = 1, FSLIC_POOL_MAX = 2 };
+enum { FSLIC_LABEL_U16 = 0 /* the int16 map of iterate(), -1 = 0xFFFF */, FSLIC_LABEL_I32 = 1, FSLIC_LABEL_I64 = 2 };
+int fslic_hip_pool_workspace_size(int N, int C, int K, int reduce, size_t* bytes);
+/* Clears the workspace and accumulates into it (K in 1 .. 65534). */
+int fslic_hip_pool(int device, void* stream, int N, int C, int H, int W, int K, int reduce, const float* features,
+                   const void* labels, int label_type, void* workspace, size_t workspace_bytes);
+/* The workspace of a completed fslic_hip_pool (same stream, same N, C, K, reduce) -> values: the sum; the sum / count (0 for an empty
+ * segment); the maximum (-0.0 below +0.0; 0 for an empty segment).  counts (optional) the pixels per segment; argmax (optional, max
+ * only) the lowest flat index h * W + w holding the maximum, -1 for an empty segment.  NaN / Inf in a segment leave that segment's
+ * entries unspecified. */
+int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int reduce, const void* workspace, size_t workspace_bytes,
+                            float* values, int32_t* counts, int32_t* argmax);
+/* out[n][c][p] = values[n][c][labels[n][p]], `fill` where the label is not in [0, K).  With argmax (the max backward):
+ * out[n][c][p] = values[n][c][l] where argmax[n][c][l] == p, `fill` everywhere else. */
+int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
+                     int label_type, const int32_t* argmax, float fill, float* out);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 
