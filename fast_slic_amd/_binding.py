@@ -40,7 +40,7 @@ EXPORTS = [
     "fslic_hip_device_count", "fslic_hip_create", "fslic_hip_destroy", "fslic_hip_initialize_clusters",
     "fslic_hip_iterate", "fslic_hip_iterate_device", "fslic_hip_iterate_batch", "fslic_hip_submit_group",
     "fslic_hip_wait_group", "fslic_hip_rgb_to_lab",
-    "fslic_hip_enforce_connectivity", "fslic_hip_last_prelabels", "fslic_hip_last_timing_report",
+    "fslic_hip_enforce_connectivity", "fslic_hip_enforce_connectivity_nodes", "fslic_hip_last_prelabels", "fslic_hip_last_timing_report",
     "fslic_hip_last_device_times", "fslic_hip_set_launch_timing", "fslic_hip_last_assign_loop", "fslic_hip_last_group_frames", "fslic_hip_last_path", "fslic_hip_last_launch_mode", "fslic_hip_group_done", "fslic_hip_last_error", "fslic_hip_version",
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
@@ -128,6 +128,8 @@ def load_library():
         lib.fslic_hip_group_done.argtypes = [vp, i32]
         lib.fslic_hip_rgb_to_lab.argtypes = [vp, i32, i32, vp, i32, vp]
         lib.fslic_hip_enforce_connectivity.argtypes = [vp, vp, i32, i32, i32, i32]
+        if hasattr(lib, "fslic_hip_enforce_connectivity_nodes"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
+            lib.fslic_hip_enforce_connectivity_nodes.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_uint32)]
         lib.fslic_hip_last_prelabels.argtypes = [vp, i32, vp]
         lib.fslic_hip_last_timing_report.argtypes = [vp]
         lib.fslic_hip_last_timing_report.restype = C.c_char_p
@@ -241,6 +243,14 @@ class Engine(object):
         H, W = out.shape
         _check(load_library().fslic_hip_enforce_connectivity(self._h, out.ctypes.data, H, W, int(K), int(min_threshold)))
         return out
+
+    def enforce_connectivity_nodes(self, labels_u16, K, min_threshold):
+        """enforce_connectivity, and the number of union-find nodes the device pass kept for the frame."""
+        out = np.ascontiguousarray(labels_u16, dtype=np.uint16).copy()
+        H, W = out.shape
+        n = C.c_uint32(0)
+        _check(load_library().fslic_hip_enforce_connectivity_nodes(self._h, out.ctypes.data, H, W, int(K), int(min_threshold), C.byref(n)))
+        return out, int(n.value)
 
     # ---- superpixel-graph utilities (src/fast-slic.cpp); labels / mask / result: numpy arrays or raw device pointers (int) ----
     @staticmethod

@@ -12,6 +12,12 @@ namespace fslic {
 // component lives in NODE arrays indexed by tile * 2048 + that number: a tile's nodes are contiguous, so the passes over
 // the components read and write dense memory (until this layout every component was addressed by the raster index of its
 // first pixel in N-entry planes: one 64-byte sector fetched or rewritten per component and access).
+// Not every component of a tile is a node.  A CLOSED SMALL one -- no pixel on a tile edge with a tile across it (so it is a
+// whole component of the frame), area below the threshold (never a candidate), not the holder of pixel 0 -- only ever takes the
+// final label of the component left of (column 0: above) its first pixel, which lies in the same tile: its pixels carry the
+// number of the node that adoption resolves to inside the tile, and the passes over the nodes never see it (four fifths of
+// the tile components of a SLIC label map are such fragments, scripts/cca_closed_small.py).  Areas, leaders, candidates and
+// the top-K step see exactly the other components.
 //   k_cca_local    64x32 tiles resolved entirely in LDS (row runs by ballot, vertical unions by LDS
 //                  atomicMin), writes lid[p], the tile's nodes (leader, area, parent = self) and appends them
 //                  to the frame's dense node list
@@ -113,9 +119,10 @@ static __device__ __forceinline__ void ldsb_union(uint32_t* par, uint32_t a, uin
 //     round trip
 //  B  the three strip seams inside the tile are merged in LDS
 //  C  flatten: every run -> tile-local root, run lengths added to the root's area (one LDS atomic per run end: + position of the
-//     last pixel + 1 at the end, - position of the first at the start), the roots ranked by ballot
-//  D  the tile-local roots become the tile's nodes (numbered, appended to the frame's node list: one returning global atomic per
-//     tile), every pixel gets its root's number
+//     last pixel + 1 at the end, - position of the first at the start; the same atomic marks the component as open when the run
+//     lies on a tile edge with a tile across it); the closed small roots are dropped, the others ranked by ballot
+//  D  the tile-local roots that stay become the tile's nodes (numbered, appended to the frame's node list: one returning global
+//     atomic per tile), every pixel gets its root's number -- or, where its root was dropped, the number of the node that root adopts from
 #if defined(FSLIC_LAB) && FSLIC_LAB == 2      // lab build 2: time stamps of the tile kernel (100 MHz ticks since the block's start), 8 words per block at the end of the (idle) candidate array
 #define LOC_STAMP(i_) do { __syncthreads(); if (threadIdx.x == 0) c.cand_leader[(size_t)c.N - 8 * (size_t)(blockIdx.z * gridDim.y + blockIdx.y + 1) + (i_)] = (int32_t)((uint32_t)__builtin_amdgcn_s_memrealtime() - loc_t); } while (0)
 #else
@@ -143,6 +150,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_cc
     __shared__ uint32_t s_par[T * TH];
     __shared__ uint32_t s_area[T * TH];
     __shared__ uint32_t s_nroots, s_base;
+    __shared__ uint32_t s_up0[4];           // tile-local root of lane 0 in every strip's last row (the pixel above the next strip's first pixel)
     if (threadIdx.x == 0) s_nroots = 0;        // (three barriers lie between this and its first use)
     const int lane = LANE();
     const int wave = (int)rfl((uint32_t)(threadIdx.x >> 6));
@@ -242,24 +250,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_cc
         for (int i = 0; i < RW; ++i) { moved |= ballot(nx[i] != root[i]); root[i] = nx[i]; }
         if (!moved) break;
     }
-    // run lengths -> the root's area; and, in the same sweep, this wavefront's tile-local roots: their positions inside the
-    // wavefront's share of the root list come from ballots alone (running count in a scalar register)
-    uint32_t pos[RW];
-    uint32_t wcount = 0;
-    const uint32_t lane_p1 = (uint32_t)lane + 1u;
+    // run lengths -> the root's area.  With them, in the same atomic, the OPEN mark of the component: a run on a tile edge that has a
+    // neighbouring tile across it adds 0x10000 (at most 192 such runs per component; an area is at most 2048).
+    // A tile-local root is DROPPED -- it gets no node -- when its component is closed (no open mark: it is a whole component of the
+    // frame), smaller than the threshold (it can never be a candidate, src/cca.cpp:213-217) and does not hold pixel 0
+    // (src/cca.cpp:238): its final label is that of the component left of (image column 0: above) its first pixel
+    // (src/cca.cpp:240-254), and that pixel lies in this tile.  Its pixels take the number of the node that neighbour resolves to.
+    const uint32_t thr_c = (uint32_t)min(max(c.min_threshold, 0), 0x10000);       // area word < thr_c: closed and small
+    const bool may_drop = thr_c > 1u;                                             // (threshold 0 or 1 drops nothing: none of the extra steps run)
+    const bool open_l = may_drop && tile_x > 0, open_r = may_drop && tile_x + 1 < (int)gridDim.y;
+    const bool open_t = may_drop && wave == 0 && tile_y > 0, open_b = may_drop && wave == 3 && tile_y + 1 < (int)gridDim.z;
+    // (lane 0 starts a run and lane 63 ends one in every row: the marks of the tile's left and right edge ride in the two lanes'
+    // position terms; the first and the last row of the tile mark every run, where they start)
+    const uint32_t lane_p1 = (uint32_t)lane + 1u + ((open_r && lane == 63) ? 0x10000u : 0u);
+    const uint32_t lane_m = (uint32_t)lane - ((open_l && lane == 0) ? 0x10000u : 0u);
 #pragma unroll
     for (int i = 0; i < RW; ++i) {
         const u64 ok = ROW_MASK(i);
         const uint32_t l = lbl[i];
         const u64 m = ballot(l != lane_left0(l)) | 1ull;                        // (as in A: two instructions, cheaper than keeping eight masks)
         const u64 e = (m >> 1) | (1ull << 63);                                  // last pixels of the runs
-        const uint32_t len_part = (lanes(e) ? lane_p1 : 0u) - (lanes(m) ? (uint32_t)lane : 0u);
+        uint32_t len_part = (lanes(e) ? lane_p1 : 0u) - (lanes(m) ? lane_m : 0u);
+        if ((i == 0 && open_t) || (i == RW - 1 && open_b)) len_part += lanes(m) ? 0x10000u : 0u;
 #if !(FSLIC_EXP & 512)     // (knock-out build 512: no run-length atomics; every node then reports the area 2048 and no adopted neighbour, which the later passes survive)
         if (lanes((m | e) & ok)) atomicAdd(lds_at(s_area, root[i]), len_part);
 #endif
-        const u64 mr = m & ok & ballot(root[i] == nodev[i]);                    // the first pixel of a root run
-        pos[i] = lanes(mr) ? wcount + rank_in(mr) : 0xFFFFFFFFu;
-        wcount += (uint32_t)__popcll(mr);
+    }
+    // A root's area word is complete once every wavefront has added its runs (a component may span the four strips)
+    uint32_t ar[RW];
+    if (may_drop) {
+        if (lanes(1ull)) lds_st(&s_up0[wave], root[RW - 1]);
+        lds_barrier();
+#pragma unroll
+        for (int i = 0; i < RW; ++i) ar[i] = lds_ld(lds_at(s_area, root[i]));
+    }
+    // this wavefront's tile-local roots that stay: their positions inside the wavefront's share of the root list come from ballots
+    // alone (running count in a scalar register).  pos: the position; 0xFFFFFFFE at the first pixel of a dropped root; 0xFFFFFFFF elsewhere
+    uint32_t pos[RW];
+    uint32_t wcount = 0;
+#pragma unroll
+    for (int i = 0; i < RW; ++i) {
+        const uint32_t l = lbl[i];
+        const u64 m = ballot(l != lane_left0(l)) | 1ull;
+        const u64 mr = m & ROW_MASK(i) & ballot(root[i] == nodev[i]);           // the first pixel of a root run
+        u64 dr = 0;
+        // (lane 0 of the tile's first row is pixel 0 of the frame, or lies on an open edge)
+        if (may_drop) dr = mr & ballot(ar[i] < thr_c) & ~((wave == 0 && i == 0) ? 1ull : 0ull);
+        const u64 mk = mr & ~dr;
+        pos[i] = lanes(mk) ? wcount + rank_in(mk) : (lanes(dr) ? 0xFFFFFFFEu : 0xFFFFFFFFu);
+        wcount += (uint32_t)__popcll(mk);
     }
     LOC_STAMP(3);
     // ---- D ---- tile-local roots -> the frame's dense root list.  One LDS atomic per wavefront places its roots inside
@@ -285,12 +324,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_cc
         lds_st(&s_base, base);
     }
     // the component numbers inside the tile: a root publishes its number where the pixels of its component look for
-    // their root (s_par is dead: every wavefront has flattened, barrier above)
+    // their root (s_par is dead: every wavefront has flattened, barrier above).  A dropped root publishes the tile-local root of
+    // the pixel left of its first pixel instead (lane 0: above it -- only image column 0 gets here, every other lane 0 lies on an
+    // open edge --, which for the strip's first row is the last row of the strip above); numbers carry bit 31, names do not.
+    const uint32_t wflag = wbase | (may_drop ? 0x80000000u : 0u);
+    uint32_t up0 = 0;
+    if (may_drop && wave > 0) up0 = lds_ld(&s_up0[wave - 1]);
 #pragma unroll
-    for (int i = 0; i < RW; ++i)
-        if (pos[i] != 0xFFFFFFFFu) lds_st(lds_at(s_par, root[i]), wbase + pos[i]);
+    for (int i = 0; i < RW; ++i) {
+        if (pos[i] < 0xFFFFFFFEu) lds_st(lds_at(s_par, root[i]), wflag + pos[i]);
+        if (may_drop) {
+            const uint32_t nb = lane_left_or(i == 0 ? up0 : root[i > 0 ? i - 1 : 0], root[i]);
+            if (pos[i] == 0xFFFFFFFEu) lds_st(lds_at(s_par, root[i]), nb);
+        }
+    }
     lds_barrier();
     LOC_STAMP(5);
+    // every pixel's number: its root's, or -- a dropped root's pixels -- the number of the node the root resolves to: the adoption is
+    // followed while it lands on dropped roots.  Names strictly decrease along the walk (a neighbour's component starts earlier in
+    // raster order) and it never leaves the tile, so it ends at a root that stays.  A pixel outside the image is a root that
+    // published nothing: it would read its own name for ever, so it is given a number by hand (tiles on the image's right and lower edge
+    // only).  (Bit 31 stays on the numbers: every use below takes the low 16 bits or shifts it out.)
+    uint32_t idv[RW];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) idv[i] = lds_ld(lds_at(s_par, root[i]));
+    if (may_drop) {
+        if (ncols < T || nrows < RW) {
+#pragma unroll
+            for (int i = 0; i < RW; ++i) idv[i] = lanes(ROW_MASK(i)) ? idv[i] : 0x80000000u;
+        }
+        for (;;) {
+            u64 walking = 0;
+#pragma unroll
+            for (int i = 0; i < RW; ++i) {
+                const u64 un = ballot((int32_t)idv[i] >= 0);
+                walking |= un;
+                if (lanes(un)) idv[i] = lds_ld(lds_at(s_par, idv[i]));
+            }
+            if (!walking) break;
+        }
+    }
     const uint32_t nbase = (uint32_t)(tile_y * (int)gridDim.y + tile_x) * (uint32_t)kCcaTilePx;
     const uint32_t gbase = s_base + wbase;
     // The outputs are organised for few instructions of either pipe: a node is ONE 16-byte record in memory; what a root lane knows
@@ -303,9 +376,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_cc
     // of s_area (8 rows x 64 words: one word per pixel, so every node fits; the areas of its roots are read into registers first;
     // no other wavefront's roots live in the strip).
     //   staged word: bits 0-8 row * 64 + lane of the first pixel, 9-19 area - 1, 20-31 number of the node to adopt from (0xFFF: none)
-    uint32_t ar[RW];
+    if (!may_drop) {
 #pragma unroll
-    for (int i = 0; i < RW; ++i) ar[i] = lds_ld(lds_at(s_area, root[i]));     // (a root lane's root is its own run)
+        for (int i = 0; i < RW; ++i) ar[i] = lds_ld(lds_at(s_area, root[i]));     // (a root lane's root is its own run)
+    }
     wave_lds_sync();
     uint32_t* const stage = s_area + ly0 * T;
     uint32_t* const s_edge = &s_last[wave][lane ? 1 : 0];     // this wavefront's 2 * RW edge words: (row, side) at 2 * row + side (s_last is dead since phase B)
@@ -317,13 +391,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_cc
 #pragma unroll
     for (int i = 0; i < RW; ++i) {
         const uint32_t y = (uint32_t)(ty0 + ly0 + i);
-        const uint32_t id = lds_ld(lds_at(s_par, root[i]));
+        const uint32_t id = idv[i];
         const uint32_t left_id = lane_left_or(tile_x == 0 ? up_id : 0xFFFu, id);
         if (lanes(ROW_MASK(i))) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)id, lr, lane * 2, (int)((y * (uint32_t)c.W + (uint32_t)tx0) * 2u), 16 /* sc1 */);
         // the tile's first and last column, row by row: what the pass over the vertical tile seams reads (a column of the
         // label plane is one 64-byte sector per pixel)
         if (lanes(0x8000000000000001ull)) lds_st(s_edge + 2 * i, lbl[i] | (id << 16));
-        if (pos[i] != 0xFFFFFFFFu) lds_st(stage + pos[i], (uint32_t)(i * T + lane) | ((ar[i] - 1u) << 9) | (left_id << 20));
+        if (pos[i] < 0xFFFFFFFEu) lds_st(stage + pos[i], (uint32_t)(i * T + lane) | (((ar[i] & 0xFFFFu) - 1u) << 9) | (left_id << 20));
         up_id = id;
     }
     wave_lds_sync();
@@ -1057,10 +1131,11 @@ __global__ __launch_bounds__(1024) void k_cca_select(CcaDev c, int cap) {
     if (tid == 0) c.counters[3] = 0u;
 }
 
-// Grid of a pass over the roots: one root per thread for up to N / 12 roots (a structured frame has fewer: 57 k of 922 k
-// pixels at 1280x720), more trips for noise; at least one block.
+// Grid of a pass over the nodes: one node per thread for up to N / 48 nodes (a structured frame has fewer once the closed small
+// components are gone: 13.5 k of 922 k pixels at 1280x720, 62 - 80 k of 8.3 M at 3840x2160, profiles/r07_cca_closed_small.txt),
+// more trips for noise or a threshold below 2; at least one block.
 static int root_pass_blocks(const CcaDev& c) {
-    const int b = (c.N / 12 + 255) / 256;
+    const int b = (c.N / 48 + 255) / 256;
     return b < 1 ? 1 : b;
 }
 
@@ -1135,6 +1210,8 @@ static __device__ __forceinline__ uint32_t chase_final(const CcaDev& c, uint32_t
         uint32_t a = n_adopt(c, g);
         if (a == kNoAdopt) {                            // the neighbour lies in another tile (or another wavefront's rows)
             const uint32_t t = (cur % W > 0) ? cur - 1 : cur - W;   // src/cca.cpp:243-248
+            // (t may be a pixel of a closed small component, which has no node: its number names the node it resolved to inside
+            // its tile, k_cca_local, which has the same final label; that node's component starts before t, so leaders still decrease)
             a = node_of(c, t);
         }
         g = *n_parent(c, a);

@@ -82,7 +82,8 @@ int fslic_hip_rgb_to_lab(fslic_engine* e, int H, int W, const uint8_t* rgb, int 
     return FSLIC_OK;
 }
 
-int fslic_hip_enforce_connectivity(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold) {
+static int enforce_connectivity_impl(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold, uint32_t* n_nodes) {
+    if (n_nodes) *n_nodes = 0;
     if (!e || !labels) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (H <= 0 || W <= 0 || (long long)H * W >= (1ll << 31)) return fail(FSLIC_E_INVALID, "bad image size");
     if (K <= 0) return FSLIC_OK;   // src/context.cpp:16
@@ -111,11 +112,20 @@ int fslic_hip_enforce_connectivity(fslic_engine* e, uint16_t* labels, int H, int
     cca_enqueue(s, c, 0, 1);
     HIPCHK(hipMemcpyAsync(s.h_misc, s.d_misc, 64, hipMemcpyDeviceToHost, s.st));
     HIPCHK(hipStreamSynchronize(s.st));
+    if (n_nodes) *n_nodes = s.h_misc[4];      // CcaDev::counters[0]
     rc = cca_finish_group(s, 0, 1, s.d_out_stage, 0, K, min_threshold);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(labels, s.d_out_stage, N * 2, hipMemcpyDeviceToHost, s.st));
     HIPCHK(hipStreamSynchronize(s.st));
     return FSLIC_OK;
+}
+
+int fslic_hip_enforce_connectivity(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold) {
+    return enforce_connectivity_impl(e, labels, H, W, K, min_threshold, nullptr);
+}
+int fslic_hip_enforce_connectivity_nodes(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold, uint32_t* n_nodes) {
+    if (!n_nodes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    return enforce_connectivity_impl(e, labels, H, W, K, min_threshold, n_nodes);
 }
 
 // ---- superpixel-graph utilities on a finished label map (src/fast-slic.cpp) ----

@@ -162,6 +162,9 @@ int fslic_hip_rgb_to_lab(fslic_engine* e, int H, int W, const uint8_t* rgb, int 
 /* cca::ConnectivityEnforcer(labels,H,W,K,min_threshold).execute(labels), src/cca.cpp:178-265, as
  * exposed by cfast_slic.enforce_connectivity (cfast_slic.pyx:371-396).  In place, host pointer. */
 int fslic_hip_enforce_connectivity(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold);
+/* The same pass; *n_nodes receives the number of union-find nodes the device pass kept for the frame (the components of
+ * the 64x32 tiles minus the closed small ones): a testing aid, the tests restate the count on the CPU. */
+int fslic_hip_enforce_connectivity_nodes(fslic_engine* e, uint16_t* labels, int H, int W, int K, int min_threshold, uint32_t* n_nodes);
 
 /* ---- Superpixel-graph utilities on a finished label map (src/fast-slic.h:13-17, src/fast-slic.cpp; reached from
  * SlicModel.get_connectivity / get_knn_connectivity / get_mask_density / broadcast_density_to_mask,
