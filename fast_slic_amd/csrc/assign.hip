@@ -1297,10 +1297,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_wav
     assign_blk2_body<R, true, STRIDE, VT, false, true>(f, rem, Hv, bm);
 }
 
+// the launch's FrameDev with the table of the subsampled stride selected (the fused passes; the full pass reads `tab` as it is)
+static FrameDev with_subsampled_table(FrameDev f) {
+    f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad;
+    return f;
+}
+
 template <int R, bool FUSE, int STRIDE>
 static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    FrameDev f = f_;
-    if (FUSE) { f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad; }   // table of the subsampled stride
+    FrameDev f = FUSE ? with_subsampled_table(f_) : f_;
     if (FUSE && R == 16 && !f.tab_vmode) { f.tab = f.tabs16; f.tab_words = f.tabs16_words; f.tab_dyoff = f.tabs16_dyoff; f.tab_nrpad = f.tabs16_nrpad; }
     // row-vector mode, full pass with at most 16 rows per wavefront: the shorter stride-1 table (48 entries = 768 bytes of LDS per block less)
     if (!FUSE && R <= 16 && f.tab_vmode && f.tabv16_words > 0) { f.tab = f.tabv16; f.tab_words = f.tabv16_words; f.tab_dyoff = f.tabv16_dyoff; }
@@ -1323,8 +1328,7 @@ static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv
 
 template <int R, int STRIDE>
 static void launch_assign_bin_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    FrameDev f = f_;
-    f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad;     // table of the subsampled stride
+    const FrameDev f = with_subsampled_table(f_);
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
     if constexpr (R == 16) {
@@ -1339,19 +1343,22 @@ static void launch_assign_bin_t(const FrameDev& f_, int nframes, int rem, int Hv
 
 template <int STRIDE>
 static void launch_assign_pre_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    FrameDev f = f_;
-    f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad;     // table of the subsampled stride
+    const FrameDev f = with_subsampled_table(f_);
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8), nframes);
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
     if (f.tab_vmode) launch((k_assign_pre<8, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     else launch((k_assign_pre<8, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
 }
+bool blk_kernel_applies(const FrameDev& f, int stride) {
+    return f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull;
+}
+
 // preemptive mode: the fused pass of the block kernel on the bins of the active clusters (see assign_blk2_body, PRE); false: the
 // geometry does not take the block kernel (the caller uses the generic kernel)
 bool launch_assign_pre(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, hipStream_t st) {
     const FrameDev f = rotated(f_, buf, sbuf);
-    const int Hv = (f.H - rem + stride - 1) / stride;
-    if (!(f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull)) return false;
+    const int Hv = visited_rows(f.H, rem, stride);
+    if (!blk_kernel_applies(f, stride)) return false;
     if (Hv <= 0) return true;
     if (stride == 1) launch_assign_pre_t<1>(f, nframes, rem, Hv, st);
     else if (stride == 2) launch_assign_pre_t<2>(f, nframes, rem, Hv, st);
@@ -1359,18 +1366,11 @@ bool launch_assign_pre(const FrameDev& f_, int nframes, int rem, int stride, int
     return true;
 }
 
-static bool blk_kernel_applies(const FrameDev& f, int stride) {
-    return f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull;
-}
-
-bool assign_fuses_cluster_pass(const FrameDev& f, int stride) { return blk_kernel_applies(f, stride); }
-
 void launch_assign_fused_bin(const FrameDev& f_, int nframes, int rem, int stride, int it, hipStream_t st) {
     const FrameDev f = rotated(f_, it & 1, it & 1, it % 3);
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     if (Hv <= 0) return;
-    const int tiles_x = (f.W + kTileW - 1) / kTileW;
-    const int blocks8 = nframes * tiles_x * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8));
+    const int blocks8 = assign_blocks8(f.W, Hv, nframes);
     const bool r16 = f.tab_vmode && blocks8 > 3072;      // as launch_assign
     // Launches that leave most of the chip idle even with 8-row wavefronts (one or two 1280x720 frames: 160 blocks each on 256
     // CUs): 4 rows per wavefront.  A wavefront alone on its SIMD issues a dependent instruction every 8 - 10 clocks, so a
@@ -1390,8 +1390,7 @@ void launch_assign_fused_bin(const FrameDev& f_, int nframes, int rem, int strid
 }
 
 static int assign_rows_per_wave(const FrameDev& f, int nframes, int Hv, bool fuse_update) {
-    const int tiles_x = (f.W + kTileW - 1) / kTileW;
-    const int blocks8 = nframes * tiles_x * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8));
+    const int blocks8 = assign_blocks8(f.W, Hv, nframes);
     // 32 rows (row-vector table only): launches that keep the chip busy for three rounds of 16-row blocks and more -- the block
     // prologue and the per-candidate fetch are then paid once per 8192 pixels instead of 4096
     if (!fuse_update && f.tab_vmode && f.tab_rows32 && blocks8 > 4 * 6144) return 32;
@@ -1413,11 +1412,11 @@ static void launch_assign_r(const FrameDev& f, int nframes, int rem, int stride,
 
 PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf) {
     const FrameDev f = rotated(f_, buf, sbuf, obuf);
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     PassGeom pg;
     pg.rem = rem; pg.stride = stride; pg.Hv = Hv; pg.BH = kWavesPerBlock * 8; pg.use_slots = 0;
     if (Hv <= 0) return pg;
-    if (f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull) {       // block-level packed kernel (its buffer loads address a plane with 31-bit byte offsets; larger planes take the 32-bit kernel)
+    if (blk_kernel_applies(f, stride)) {       // block-level packed kernel
         if (!fuse_update && stride == 1) {
             const int rpw = assign_rows_per_wave(f, nframes, Hv, false);
             if (rpw == 32) launch_assign_blk_t<32, false, 1>(f, nframes, rem, Hv, st);
@@ -1431,8 +1430,7 @@ PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int
             // visited rows per block -- the block prologue (candidate list, table) is paid once per 4096 pixels instead of
             // 2048.  Small launches keep 8 rows (more, shorter-lived blocks fill the chip better); so does the 2-D table,
             // whose LDS footprint grows with the rows a wavefront spans.
-            const int tiles_x = (f.W + kTileW - 1) / kTileW;
-            const int fblocks8 = nframes * tiles_x * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8));
+            const int fblocks8 = assign_blocks8(f.W, Hv, nframes);
             // (2-D table: 16 rows from 2048 eight-row blocks on -- the launch then is one round of blocks instead of one and a bit)
             const bool r16 = (f.tab_vmode && fblocks8 > 3072) || (!f.tab_vmode && f.tabs16_words > 0 && fblocks8 > 2048);
             if (r16) {
@@ -1515,7 +1513,7 @@ __global__ __launch_bounds__(256) void k_assign_generic_rec(FrameDev f, int rem,
 
 void launch_assign_generic(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, uint16_t* rec_dist) {
     const FrameDev f = rotated(f_, buf, sbuf);
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     if (Hv <= 0) return;
     const size_t n = (size_t)Hv * f.W;
     const int blocks = (int)((n + 255) / 256);

@@ -180,7 +180,7 @@ void stage_group(fslic_engine* e, Slot& s, int i0, int n, bool timed) {
         int rem = 0;
         for (int it = 0; it < s.p.max_iter && s.launch_timing && it < Slot::kMaxTimedIters; it++) {
             s.n_timed_iters = it + 1;
-            s.assign_loop_px += (double)((H - rem + stride - 1) / stride) * W * n;
+            s.assign_loop_px += (double)visited_rows(H, rem, stride) * W * n;
             rem = (rem + 1) % stride;
         }
     }
@@ -190,7 +190,7 @@ void stage_group(fslic_engine* e, Slot& s, int i0, int n, bool timed) {
 // SLIC path on the block kernel, launches that do not fill the chip (FSLIC_FUSEBIN=1, the default) or all of them (=2).
 static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, int W, int H, bool generic, bool separate_cluster_pass) {
     const int stride = p.subsample_stride;
-    const int assign_blocks = n * ((W + kTileW - 1) / kTileW) * (((H + stride - 1) / stride + 31) / 32);
+    const int assign_blocks = assign_blocks8(W, visited_rows(H, 0, stride), n);      // (the first pass's: launch_assign_fused_bin's own count)
 #if defined(FSLIC_LAB) && FSLIC_LAB == 3
     // lab build 3 turns st_stream into plain stores; the fused cluster pass hands partial sums from block to block through
     // written-through (sc1) stores and agent-scope loads and would read stale lines of another XCD's L2: never fused there
@@ -204,8 +204,11 @@ static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, 
     // for them: every cluster's num_members becomes 0, positions stay; a cluster pass that rides on the assign blocks would not happen.
     // Found on a 71x1 frame, tests/fuzz_parity.py FUZZ_SHAPES=tiny seed 5 case 3100.)
     const bool every_pass_has_rows = H >= stride;
-    return fuse_wanted && !separate_cluster_pass && plain_slic && !generic && every_pass_has_rows && assign_fuses_cluster_pass(f, stride);
+    return fuse_wanted && !separate_cluster_pass && plain_slic && !generic && every_pass_has_rows && blk_kernel_applies(f, stride);
 }
+
+// enforce_connectivity's minimum component size of the slot's current call, src/context.cpp:14-20
+static int min_size_threshold(const Slot& s) { return (int)round((double)(s.S * s.S) * (double)s.p.min_size_factor); }
 
 // ---- debug_mode: the recording path ----
 // A call with debug_mode set (fslic_hip_iterate / fslic_hip_iterate_device; one frame) is enqueued directly, never as a graph, on the
@@ -250,7 +253,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // copies the graph recorder has no node for (launch.h): such a group is always enqueued directly
     // the (2S+1)^2 patch of the generic kernel: also where a preemptive Slic group falls back to that kernel for its subsampled passes
     // (geometries outside the block kernel: launch_assign_pre returns false)
-    const bool need_patch = generic || (p->preemptive != 0 && p->variant == FSLIC_VARIANT_SLIC && !assign_fuses_cluster_pass(f, p->subsample_stride));
+    const bool need_patch = generic || (p->preemptive != 0 && p->variant == FSLIC_VARIANT_SLIC && !blk_kernel_applies(f, p->subsample_stride));
     if ((p->preemptive != 0 || p->variant == FSLIC_VARIANT_REALDIST_NOQ || (need_patch && !s.sp_patch_uploaded)) && recording_unsupported()) return FSLIC_OK;
     if (need_patch && !s.sp_patch_uploaded) {
         HIPCHK(hipMemcpyAsync(s.d_patch, s.h_patch, (size_t)(2 * S + 1) * (2 * S + 1) * sizeof(uint16_t), hipMemcpyHostToDevice, s.st));
@@ -285,8 +288,8 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // there every block drains its label stores before it counts itself in, and stores into a plane the LAB kernel has just written
     // find their lines in the memory-side cache -- without the fill each of the ten launches of a one-frame group takes 0.35 us longer
     // (8.54 against 8.18 us, same-box A/B, profiles/r06_experiments.txt) for the 0.6 us the LAB kernel saves once.
-    const bool lazy_labels = p->variant == FSLIC_VARIANT_SLIC && !generic && p->preemptive == 0 &&
-                             !cluster_pass_fused(f, *p, n, s.W, s.H, generic, separate_cluster_pass);
+    const bool fusebin = cluster_pass_fused(f, *p, n, s.W, s.H, generic, separate_cluster_pass);      // (see the fused loop below)
+    const bool lazy_labels = p->variant == FSLIC_VARIANT_SLIC && !generic && p->preemptive == 0 && !fusebin;
     launch_rgb_to_lab(f, n, p->convert_to_lab, e->tables, !lazy_labels, s.st, s.gen_step,
                       s.at(s.zero_block, i0), s.zero_bytes, f.cl_n, 2 * (size_t)K, s.h_cl + (size_t)i0 * 4 * K, 4 * (size_t)K);      // (+ the staged centres -> cl_yx)
     if (timed) HIPCHK(hipEventRecord(s.ev[1], s.st));
@@ -392,7 +395,6 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // drops from 51.8 to 45.3 GP/s: the finaliser is a chain of dependent memory round trips at the end of every block and
     // vector work a 1600-thread cluster pass does once.  So: fused where a launch does not fill the chip (latency-bound: the
     // reference's own one-frame-per-call pattern), separate where it does.  FSLIC_FUSEBIN=0 / 2: never / always.
-    const bool fusebin = cluster_pass_fused(f, *p, n, s.W, s.H, generic, separate_cluster_pass);
     int full_obuf = -1;
     for (int it = 0; fusebin && it < p->max_iter; it++) {
         const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
@@ -444,9 +446,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     else if (generic) launch_assign_generic(f, n, 0, 1, full_buf, 0, false, s.st);
     else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf);      // (full_buf: the bins of all clusters; max_iter & 1 unless preemptive)
     if (timed) HIPCHK(hipEventRecord(s.ev[3], s.st));
-    // enforce_connectivity, src/context.cpp:14-20
-    const int thres = (int)round((double)(S * S) * (double)p->min_size_factor);
-    const CcaDev c = cca_view(s, i0, s.f.labels, fb, K, thres);
+    const CcaDev c = cca_view(s, i0, s.f.labels, fb, K, min_size_threshold(s));
     // cluster state, overflow flag and connectivity status back to the host: the last kernel of the connectivity pass
     // writes them into the slot's pinned blocks (three 2-D copy commands per group before: blit kernels with their own
     // barriers).  The status words are final once the select kernel has run, the cluster state since the loop ended.
@@ -656,7 +656,7 @@ int group_finish(fslic_engine* e, Slot& s) {
         elapsed(ms, s.ev_it[2 * it], s.ev_it[2 * it + 1]);
         s.assign_loop_ms += ms;
     }
-    const int thres = (int)round((double)(s.S * s.S) * (double)s.p.min_size_factor);
+    const int thres = min_size_threshold(s);
     const double t_ev = now_us();
     int n_host_topk = 0;
     for (int i = 0; i < n; i++) {

@@ -175,6 +175,11 @@ struct PassGeom {
     int BH;                // visited rows per assign block
     int use_slots;         // 1: the block kernel wrote FrameDev::cpart; 0: everything is in FrameDev::sums
 };
+// Visited rows of a pass over rows == rem (mod stride) of H: PassGeom::Hv (<= 0: the pass visits nothing and launches nothing).
+inline int visited_rows(int H, int rem, int stride) { return (H - rem + stride - 1) / stride; }
+// Eight-row assign blocks (kTileW columns x kWavesPerBlock wavefronts x 8 rows) of a launch over Hv visited rows of nframes frames: the
+// size every rows-per-wavefront and fusing threshold is compared against, whatever block height the launch then takes.
+inline int assign_blocks8(int W, int Hv, int nframes) { return nframes * ((W + kTileW - 1) / kTileW) * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8)); }
 
 struct CcaDev {
     size_t frame_bytes;
@@ -271,6 +276,10 @@ void launch_bin_clusters(const FrameDev& f, int nframes, int mode, int buf, int 
 // kernels back to back in every iteration.  Mode 1 with PassGeom{} (everything is in FrameDev::sums).
 void launch_bin_clusters_lsc(const FrameDev& f, const LscDev& l, int nframes, int buf, int sbuf, hipStream_t st);
 
+// Whether the block-level packed kernel (assign.hip: k_assign_blk2 and its fused forms k_assign_bin / k_assign_pre) takes a pass of this
+// geometry: a packed table exists, the stride has an instantiation, and the plane fits the kernel's 31-bit byte offsets.  Otherwise
+// launch_assign uses the 32-bit kernel, launch_assign_pre returns false and the cluster pass cannot ride on the assign blocks.
+bool blk_kernel_applies(const FrameDev& f, int stride);
 // One assign pass over rows == rem (mod stride); fuse_update also accumulates the centroid sums
 // of src/context.cpp:301-354 for the same rows.  Returns the geometry the following cluster pass needs.
 // obuf: which of the three spill lists the pass reads (buf for the two-buffer rotation of the separate cluster pass).
@@ -278,8 +287,7 @@ PassGeom launch_assign(const FrameDev& f, int nframes, int rem, int stride, int 
 // The same with the cluster pass fused in (src/context.cpp:356-373 + the binning of src/context.cpp:214-221): the LAST assign block
 // that delivers partial sums of a cluster finalises it (integer means, re-binning for the next pass) -- no k_bin_clusters<1> launch
 // between two passes.  Pass `it` reads bins [it & 1] / spill list [it % 3], appends to [(it+1) & 1] / [(it+1) % 3].  Only for
-// geometries assign_fuses_cluster_pass() accepts; positions live in FrameDev::cl_yx (updated in place).
-bool assign_fuses_cluster_pass(const FrameDev& f, int stride);
+// geometries blk_kernel_applies() accepts; positions live in FrameDev::cl_yx (updated in place).
 void launch_assign_fused_bin(const FrameDev& f, int nframes, int rem, int stride, int it, hipStream_t st);
 // rec_dist != nullptr (debug_mode, one frame, fuse_update): the recording kernel, which also writes every visited pixel's
 // minimum distance (uint16, 0xFFFF where no window reaches it) into that plane -- the reference's min_dists

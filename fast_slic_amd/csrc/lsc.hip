@@ -772,12 +772,12 @@ __global__ __launch_bounds__(256) void k_lsc_pre_update(FrameDev f, LscDev l) {
 }
 void launch_lsc_pre_sums(const FrameDev& f_, int nframes, int rem, int stride, int sbuf, hipStream_t st) {
     const FrameDev f = rotated(f_, 0, sbuf);
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     if (Hv <= 0) return;
     launch(k_lsc_pre_sums, dim3((unsigned)(((size_t)Hv * f.W + 255) / 256), nframes), dim3(256), 0, st, f, rem, stride, Hv);
 }
 void launch_lsc_pre_feats(const FrameDev& f, const LscDev& l, int nframes, int rem, int stride, hipStream_t st) {
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     // a pass without visited rows (H <= rem) still recomputes the centroids of the updatable clusters: 0 / 0 = NaN, as
     // ContextLSC::after_update leaves them (src/lsc.cpp:256-269)
     if (Hv > 0) launch(k_lsc_pre_feats, dim3((unsigned)(((size_t)Hv * f.W + 255) / 256), nframes), dim3(256), 0, st, f, l, rem, stride, Hv);
@@ -795,7 +795,7 @@ void launch_lsc_prepare(const FrameDev& f, const LscDev& l, int nframes, hipStre
 void launch_lsc_assign(const FrameDev& f_, const LscDev& l, int nframes, int rem, int stride, int buf, int sbuf, bool stale_sums, hipStream_t st,
                        float* rec_dist) {
     const FrameDev f = rotated(f_, buf, sbuf);
-    const int Hv = (f.H - rem + stride - 1) / stride;
+    const int Hv = visited_rows(f.H, rem, stride);
     if (Hv <= 0) return;
     const dim3 grid((f.W + 63) / 64, (Hv + kLscBH - 1) / kLscBH, nframes);
     if (rec_dist) {
