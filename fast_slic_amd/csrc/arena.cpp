@@ -12,27 +12,10 @@ void free_slot(Slot& s) {
     // the slot's host thread has been stopped by the caller (stop_slot_thread)
     for (auto& g : s.graphs) { if (g.exec) hipGraphExecDestroy(g.exec); if (g.graph) hipGraphDestroy(g.graph); }
     s.graphs.clear();
-    if (s.arena) hipFree(s.arena);
-    if (s.lsc_arena) hipFree(s.lsc_arena);
-    if (s.d_rec) hipFree(s.d_rec);
-    if (s.h_lsc_lut) hipHostFree(s.h_lsc_lut);
-    if (s.h_patchf) hipHostFree(s.h_patchf);
-    if (s.h_clf) hipHostFree(s.h_clf);
-    if (s.h_upd) hipHostFree(s.h_upd);
-    if (s.d_ptrs) hipFree(s.d_ptrs);
-    if (s.d_gen) hipFree(s.d_gen);
-    if (s.h_ptrs) hipHostFree(s.h_ptrs);
-    if (s.h_cl) hipHostFree(s.h_cl);
-    if (s.h_misc) hipHostFree(s.h_misc);
-    if (s.h_lut) hipHostFree(s.h_lut);
-    if (s.h_tab) hipHostFree(s.h_tab);
-    if (s.h_patch) hipHostFree(s.h_patch);
-    if (s.h_cand_leader) hipHostFree(s.h_cand_leader);
-    if (s.h_cand_area) hipHostFree(s.h_cand_area);
     for (auto& e : s.ev) if (e) hipEventDestroy(e);
     for (auto& e : s.ev_it) if (e) hipEventDestroy(e);
     if (s.st) hipStreamDestroy(s.st);
-    s = Slot();
+    s = Slot();                      // the buffers go with the old value
 }
 
 // (Re)allocate the slot's buffers for groups of up to G frames of H x W with K clusters and carve the arena.
@@ -44,27 +27,11 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     const size_t P = (size_t)(2 * S + 1);
     if (G < s.cap_frames && s.keyH == H && s.keyW == W && s.keyK == K) G = s.cap_frames;
 
-    if (s.h_cl_words < (size_t)G * 4 * K) {
-        if (s.h_cl) hipHostFree(s.h_cl);
-        s.h_cl = nullptr; s.h_cl_words = 0;
-        HIPCHK(hipHostMalloc((void**)&s.h_cl, sizeof(uint32_t) * 4 * (size_t)K * G));
-        s.h_cl_words = (size_t)G * 4 * K;
-    }
-    if (!s.h_misc) HIPCHK(hipHostMalloc((void**)&s.h_misc, 64 * kMaxGroup));
-    if (!s.h_lut) HIPCHK(hipHostMalloc((void**)&s.h_lut, kLutMaxWords * 4));
-    if (!s.h_tab) HIPCHK(hipHostMalloc((void**)&s.h_tab, 3 * kTabMaxBytes));
-    if (s.h_patchf_cap < P * P) {
-        if (s.h_patchf) hipHostFree(s.h_patchf);
-        s.h_patchf = nullptr; s.h_patchf_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&s.h_patchf, sizeof(float) * P * P));
-        s.h_patchf_cap = P * P;
-    }
-    if (s.h_patch_cap < P * P) {
-        if (s.h_patch) hipHostFree(s.h_patch);
-        s.h_patch = nullptr; s.h_patch_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&s.h_patch, sizeof(uint16_t) * P * P));
-        s.h_patch_cap = P * P;
-    }
+    int rc;
+    if ((rc = s.h_cl.reserve((size_t)G * 4 * K)) || (rc = s.h_misc.reserve((size_t)kStatusWords * kMaxGroup)) ||
+        (rc = s.h_lut.reserve(kLutMaxWords)) || (rc = s.h_tab.reserve(3 * kTabMaxBytes / sizeof(uint16_t))) ||
+        (rc = s.h_patchf.reserve(P * P)) || (rc = s.h_patch.reserve(P * P)))
+        return rc;
 
     // ---- carve: shared tables, then one frame's sub-arena ----
     size_t off = 0;
@@ -91,7 +58,7 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     const size_t o_zero = off;
     const size_t o_sums = take((size_t)K * 6 * 4), o_sums1 = take((size_t)K * 6 * 4);
     const size_t o_cc0 = take(ncell * 4), o_cc1 = take(ncell * 4);
-    const size_t o_misc = take(256);                                 // ovf_cnt[0..1], err, ovf_cnt[2], cca counters
+    const size_t o_misc = take(256);                                 // the status words (kernels.h, StatusWord)
     const size_t o_arrive = take((size_t)K * 4);                     // fused cluster pass: arrival counters
     const size_t zero_bytes = off - o_zero;
     const size_t o_ci0 = take(ncell * kCellCap * sizeof(ClusterRec)), o_ci1 = take(ncell * kCellCap * sizeof(ClusterRec));
@@ -107,11 +74,7 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     const size_t frame_bytes = off;
     const size_t total = shared_bytes + frame_bytes * (size_t)G;
 
-    if (s.arena_cap < total) {
-        if (s.arena) { hipFree(s.arena); s.arena = nullptr; s.arena_cap = 0; }
-        HIPCHK(hipMalloc((void**)&s.arena, total));
-        s.arena_cap = total;
-    }
+    if ((rc = s.arena.reserve(total))) return rc;
     s.cap_frames = G;
     s.frame_bytes = frame_bytes;
     char* b = s.arena + shared_bytes;          // frame 0
@@ -136,7 +99,7 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     f.cell_cnt[0] = (uint32_t*)(b + o_cc0); f.cell_cnt[1] = (uint32_t*)(b + o_cc1);
     uint32_t* misc = (uint32_t*)(b + o_misc);
     s.d_misc = misc;
-    f.ovf_cnt[0] = misc + 0; f.ovf_cnt[1] = misc + 1; f.err_flag = misc + 2; f.ovf_cnt[2] = misc + 3;
+    f.ovf_cnt[0] = misc + kStSpill0; f.ovf_cnt[1] = misc + kStSpill1; f.err_flag = misc + kStFlags; f.ovf_cnt[2] = misc + kStSpill2;
     f.cl_arrive = (uint32_t*)(b + o_arrive);
     f.cell_items[0] = (ClusterRec*)(b + o_ci0); f.cell_items[1] = (ClusterRec*)(b + o_ci1);
     f.ovf_items[0] = (ClusterRec*)(b + o_ov0); f.ovf_items[1] = (ClusterRec*)(b + o_ov1); f.ovf_items[2] = (ClusterRec*)(b + o_ov2);
@@ -153,9 +116,8 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     c.tiles_x = (W + kCcaTile - 1) / kCcaTile;
     c.lid = (uint16_t*)(b + o_lid); c.nrec = (uint4*)(b + o_nrec); c.narea = (uint32_t*)(b + o_narea);
     c.nfinal = (uint16_t*)(b + o_nfinal); c.vedge = (uint32_t*)(b + o_vedge); c.roots = (uint32_t*)(b + o_roots);
-    c.counters = misc + 4;
+    c.counters = misc + kStCca;
     c.cand_leader = (int32_t*)(b + o_candl); c.cand_area = (uint32_t*)(b + o_canda);
-    s.cand_capacity = ntiles * TT;
 #if defined(FSLIC_LAB) && FSLIC_LAB == 4
     f.lab_stamps = c.cand_area;
 #endif
@@ -199,17 +161,8 @@ int prepare_lsc(Slot& s, int H, int W, int K, int S, int G, float compactness) {
         const size_t zero_bytes = off - o_hist;
         const size_t o_means = take(64), o_cfeat = take((size_t)K * kLscCfPitch * 4);
         const size_t frame_bytes = off, total = shared_bytes + frame_bytes * (size_t)G;
-        if (s.lsc_cap < total) {
-            if (s.lsc_arena) { hipFree(s.lsc_arena); s.lsc_arena = nullptr; s.lsc_cap = 0; }
-            HIPCHK(hipMalloc((void**)&s.lsc_arena, total));
-            s.lsc_cap = total;
-        }
-        if (s.h_lsc_lut_cap < lut_floats) {
-            if (s.h_lsc_lut) hipHostFree(s.h_lsc_lut);
-            s.h_lsc_lut = nullptr; s.h_lsc_lut_cap = 0;
-            HIPCHK(hipHostMalloc((void**)&s.h_lsc_lut, lut_floats * 4));
-            s.h_lsc_lut_cap = lut_floats;
-        }
+        int rc;
+        if ((rc = s.lsc_arena.reserve(total)) || (rc = s.h_lsc_lut.reserve(lut_floats))) return rc;
         char* b = s.lsc_arena + shared_bytes;
         LscDev& l = s.l;
         l.frame_bytes = frame_bytes;
@@ -262,16 +215,6 @@ int prepare_lsc(Slot& s, int H, int W, int K, int S, int G, float compactness) {
         s.l.blk_shift_f = 20 - bits_f; s.l.blk_shift_w = 12 - bits_w;
         s.lsc_S = S; s.lsc_compactness = compactness;
     }
-    return FSLIC_OK;
-}
-
-int ensure_cand_capacity(Slot& s, size_t M) {
-    if (s.h_cand_cap >= M) return FSLIC_OK;
-    if (s.h_cand_leader) { hipHostFree(s.h_cand_leader); hipHostFree(s.h_cand_area); s.h_cand_leader = nullptr; s.h_cand_area = nullptr; }
-    const size_t cap = std::max<size_t>(M, 16384);
-    HIPCHK(hipHostMalloc((void**)&s.h_cand_leader, sizeof(int32_t) * cap));
-    HIPCHK(hipHostMalloc((void**)&s.h_cand_area, sizeof(uint32_t) * cap));
-    s.h_cand_cap = cap;
     return FSLIC_OK;
 }
 

@@ -730,7 +730,7 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
         const int c0 = (int)rfl(wc.x), c1 = (int)rfl(wc.y), c2 = (int)rfl(wc.z), c3 = (int)rfl(wc.w);
         bn = c0 + c1 + c2 + c3;
         if (bn > 64) {                        // more live candidates than idx bits: the host redoes the frame generically
-            if (tid == 0) atomicOr(f.err_flag, 1u);
+            if (tid == 0) atomicOr(f.err_flag, kFlagListOverflow);
             // The plane is reset lazily (FrameDev::fv_mod): rows this launch is the first to look at hold whatever the arena's previous
             // geometry left there.  The frame is redone, but a later pass of THIS run whose list fits again would take that for the
             // pixels' old labels (sums of a cluster number beyond K), and the connectivity pass runs before the host sees the flag.
@@ -1190,7 +1190,7 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
                         global_accumulate(f.sums[0], old, (uint32_t)(yw_lo + r * STRIDE), xo, pix[r]);
                         // the owner of that label may lie outside this block's candidates: nothing orders these atomics before its
                         // finaliser.  Rare (no window covers the pixel); the host redoes the frame with the separate cluster pass.
-                        if (FBIN) atomicOr(f.err_flag, 2u);
+                        if (FBIN) atomicOr(f.err_flag, kFlagStalePixel);
                     }
                 }
             }

@@ -44,12 +44,10 @@ int fslic_hip_create(int device, int n_slots, fslic_engine** out) {
             if (hipEventCreate(&ev) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipEventCreate failed"); }
         for (auto& ev : s.ev_it)
             if (hipEventCreate(&ev) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipEventCreate failed"); }
-        if (hipMalloc((void**)&s.d_ptrs, sizeof(void*) * 2 * kMaxGroup) != hipSuccess ||
-            hipHostMalloc((void**)&s.h_ptrs, sizeof(void*) * 2 * kMaxGroup) != hipSuccess ||
-            hipMalloc((void**)&s.d_gen, 256) != hipSuccess || hipMemset(s.d_gen, 0, 256) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "pointer table allocation failed"); }
+        if (s.d_ptrs.reserve(2 * kMaxGroup) || s.h_ptrs.reserve(2 * kMaxGroup) ||
+            s.d_gen.reserve(64) || hipMemset(s.d_gen, 0, 256) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "pointer table allocation failed"); }
     }
-    if (hipMalloc((void**)&e->d_gamma, sizeof ht.gamma) != hipSuccess ||
-        hipMalloc((void**)&e->d_labtbl, sizeof ht.lab) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipMalloc(tables) failed"); }
+    if (e->d_gamma.reserve(sizeof ht.gamma / sizeof ht.gamma[0]) || e->d_labtbl.reserve(sizeof ht.lab / sizeof ht.lab[0])) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipMalloc(tables) failed"); }
     if (hipMemcpy(e->d_gamma, ht.gamma, sizeof ht.gamma, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(e->d_labtbl, ht.lab, sizeof ht.lab, hipMemcpyHostToDevice) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "table upload failed"); }
     e->tables.gamma = e->d_gamma;
@@ -67,9 +65,26 @@ void fslic_hip_destroy(fslic_engine* e) {
         if (s.st) hipStreamSynchronize(s.st);
         free_slot(s);
     }
-    if (e->d_gamma) hipFree(e->d_gamma);
-    if (e->d_labtbl) hipFree(e->d_labtbl);
-    delete e;
+    delete e;                        // (the tables and whatever a slot still holds: released here, the device being current)
+}
+
+// The synchronous forms' common body: one frame on the slot the caller has leased, run to completion, and the calling thread's reports.
+// (After a failure, also a late one, nothing touches the frame buffers any more: the caller's, or the stage buffers of a slot about to be
+// released.)
+static int iterate_on(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K,
+                      const uint8_t* d_rgb, fslic_cluster* clusters, uint16_t* d_labels) {
+    GroupJob job;
+    int rc = fill_job(job, p, H, W, K, 1, &d_rgb, &clusters, &d_labels);
+    if (rc) return rc;
+    s.launch_timing = e->launch_timing;
+    rc = run_group(e, s, job, p->debug_mode != 0);
+    if (rc) return rc;
+    std::string report;
+    rc = make_recorder_report(s, report);
+    if (rc) { drain_failed(s); return rc; }
+    set_thread_timing_report(make_timing_report(s));
+    set_thread_recorder_report(std::move(report));
+    return FSLIC_OK;
 }
 
 int fslic_hip_iterate_device(fslic_engine* e, int slot, const fslic_params* p, int H, int W, int K,
@@ -78,24 +93,8 @@ int fslic_hip_iterate_device(fslic_engine* e, int slot, const fslic_params* p, i
     if (slot < 0 || slot >= (int)e->slots.size()) return fail(FSLIC_E_INVALID, "slot out of range");
     HIPCHK(hipSetDevice(e->device));
     SlotLease lease(e);
-    int rc = lease.take(slot);
-    if (rc) return rc;
-    Slot& s = e->slots[slot];
-    s.launch_timing = e->launch_timing;
-    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_labels, p && p->debug_mode != 0);
-    if (rc == FSLIC_OK) rc = group_finish(e, s);
-    std::string report;
-    if (rc == FSLIC_OK) rc = make_recorder_report(s, report);
-    if (rc != FSLIC_OK) {            // a failure after a partial enqueue: nothing may still touch the caller's buffers on return
-        const std::string msg = last_error();
-        (void)hipStreamSynchronize(s.st);
-        (void)hipGetLastError();
-        set_last_error(msg);
-        return rc;
-    }
-    set_thread_timing_report(make_timing_report(s));
-    set_thread_recorder_report(std::move(report));
-    return rc;
+    const int rc = lease.take(slot);
+    return rc ? rc : iterate_on(e, e->slots[slot], p, H, W, K, d_rgb, clusters, d_labels);
 }
 
 // Host frame in, host label map out, on whichever slot is free: concurrent calls from different threads (different
@@ -115,8 +114,6 @@ int fslic_hip_iterate(fslic_engine* e, const fslic_params* p, int H, int W, int 
     const size_t N = (size_t)H * W;
     rc = ensure_prepared(e, s, H, W, K, S, 1);
     if (rc) return rc;
-    const uint8_t* d_rgb = s.d_rgb_stage;
-    uint16_t* d_out = s.d_out_stage;
     // Pageable hipMemcpyAsync in and out on the slot's stream (the runtime's own staging).  Measured against it and not kept
     // (profiles/r03_e2e_probe.txt, 1280x720 K=1600, one caller thread: 432 us per call like this): pinned staging read and written
     // in place by the LAB / relabel kernels (490 us: kernels working over PCIe take 84 us longer than on HBM) and pinned staging
@@ -124,27 +121,14 @@ int fslic_hip_iterate(fslic_engine* e, const fslic_params* p, int H, int W, int 
     const double t0 = knobs().host_timing ? now_us() : 0.0;
     HIPCHK(hipMemcpyAsync(s.d_rgb_stage, rgb, N * 3, hipMemcpyHostToDevice, s.st));
     const double t1 = knobs().host_timing ? now_us() : 0.0;
-    s.launch_timing = e->launch_timing;
-    rc = group_begin(e, s, p, H, W, K, 1, &d_rgb, &clusters, &d_out, p->debug_mode != 0);
-    const double t2 = knobs().host_timing ? now_us() : 0.0;
-    if (rc == FSLIC_OK) rc = group_finish(e, s);
-    std::string report;
-    if (rc == FSLIC_OK) rc = make_recorder_report(s, report);
-    if (rc != FSLIC_OK) {            // a failure after a partial enqueue: nothing may still run on the slot's stage buffers when the slot is released
-        const std::string msg = last_error();
-        (void)hipStreamSynchronize(s.st);
-        (void)hipGetLastError();
-        set_last_error(msg);
-        return rc;
-    }
-    const double t3 = knobs().host_timing ? now_us() : 0.0;
+    rc = iterate_on(e, s, p, H, W, K, s.d_rgb_stage, clusters, s.d_out_stage);
+    if (rc) return rc;
+    const double t2 = s.t_begun_us, t3 = knobs().host_timing ? now_us() : 0.0;
     HIPCHK(hipMemcpyAsync(labels, s.d_out_stage, N * 2, hipMemcpyDeviceToHost, s.st));
     HIPCHK(hipStreamSynchronize(s.st));
     if (knobs().host_timing)
         fprintf(stderr, "[fslic host] iterate: frame in %.1f us, group begin %.1f, group finish (wait + write-back) %.1f, labels out %.1f (device %.1f us)\n",
                 t1 - t0, t2 - t1, t3 - t2, now_us() - t3, s.total_ms * 1e3);
-    set_thread_timing_report(make_timing_report(s));
-    set_thread_recorder_report(std::move(report));
     return FSLIC_OK;
 }
 
@@ -170,15 +154,18 @@ int fslic_hip_iterate_batch(fslic_engine* e, const fslic_params* p, int H, int W
     int S = 0;
     int rc = validate(p, H, W, K, S);
     if (rc) return rc;
-    for (int i = 0; i < n_frames; i++)
-        if (!rgb[i] || !clusters[i] || !labels[i]) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    rc = acquire_all_slots(e);
-    if (rc) return rc;
     // Frames are cut into groups of up to group_size; every launch of a group covers all of its frames (frame =
     // last grid dimension).  Groups rotate over the slots (one stream each), so the host-side tail of one group
     // (cluster write-back) overlaps the kernels of the next.
     int G = std::min(std::max(e->group_size, 1), (int)kMaxGroup);
     if (n_frames < G * ns) G = std::max(1, (n_frames + ns - 1) / ns);       // spread a small batch over the slots
+    std::vector<GroupJob> jobs((size_t)(n_frames + G - 1) / G);             // checked before anything starts
+    for (size_t g = 0; g < jobs.size(); g++) {
+        const int first = (int)g * G;
+        if ((rc = fill_job(jobs[g], p, H, W, K, std::min(G, n_frames - first), rgb + first, clusters + first, labels + first)) || (rc = check_job(jobs[g], S))) return rc;
+    }
+    rc = acquire_all_slots(e);
+    if (rc) return rc;
     struct Pending { int slot, first, n; };
     std::vector<Pending> inflight;
     auto finish_one = [&](const Pending& pd) -> int {
@@ -195,11 +182,8 @@ int fslic_hip_iterate_batch(fslic_engine* e, const fslic_params* p, int H, int W
     // On an error nothing may still be running against the caller's buffers when control returns: every group in
     // flight is waited for first (their results are dropped), then the first error is reported.
     auto bail = [&](int code) -> int {
-        const std::string msg = last_error();
-        for (const Pending& pd : inflight) (void)hipStreamSynchronize(e->slots[pd.slot].st);
-        (void)hipGetLastError();
+        for (const Pending& pd : inflight) drain_failed(e->slots[pd.slot]);
         release_all_slots(e);
-        set_last_error(msg);
         return code;
     };
     int next_slot = 0;
@@ -217,23 +201,20 @@ int fslic_hip_iterate_batch(fslic_engine* e, const fslic_params* p, int H, int W
                 break;
             }
         Slot& s = e->slots[si];
-        const uint8_t* d_rgb[kMaxGroup];
-        uint16_t* d_out[kMaxGroup];
-        if (!device_ptrs) {
+        GroupJob& job = jobs[(size_t)(first / G)];
+        if (!device_ptrs) {      // the job's frame buffers become the slot's stage buffers
             rc = ensure_prepared(e, s, H, W, K, S, n);
             if (rc) return bail(rc);
             for (int i = 0; i < n; i++) {
                 if (hipMemcpyAsync(s.at(s.d_rgb_stage, i), rgb[first + i], N * 3, hipMemcpyHostToDevice, s.st) != hipSuccess)
                     return bail(fail(FSLIC_E_HIP, "frame upload failed"));
-                d_rgb[i] = s.at(s.d_rgb_stage, i);
-                d_out[i] = s.at(s.d_out_stage, i);
+                job.d_rgb[i] = s.at(s.d_rgb_stage, i);
+                job.d_out[i] = s.at(s.d_out_stage, i);
             }
-        } else {
-            for (int i = 0; i < n; i++) { d_rgb[i] = rgb[first + i]; d_out[i] = labels[first + i]; }
         }
         s.launch_timing = e->launch_timing;
         inflight.push_back({si, first, n});                  // from here on the slot's stream may hold work of this group
-        rc = group_begin(e, s, p, H, W, K, n, d_rgb, clusters + first, d_out);
+        rc = group_begin(e, s, job);
         if (rc) return bail(rc);
     }
     while (!inflight.empty()) {
@@ -652,10 +633,10 @@ int fslic_hip_crf_expf_host(const float* in, float* out, size_t n, int use_libm)
 int fslic_hip_crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n) { return crf_expf_device(e, in, out, n); }
 
 #ifdef FSLIC_LAB
-// lab build only: the 16 status words of frame `frame` of the last group on `slot` as the export left them in pinned memory
+// lab build only: the status words of frame `frame` of the last group on `slot` as the export left them in pinned memory
 int fslic_hip_debug_status_words(fslic_engine* e, int slot, int frame, uint32_t* out16) {
     if (!e || slot < 0 || slot >= (int)e->slots.size() || frame < 0 || frame >= (int)kMaxGroup || !out16) return FSLIC_E_INVALID;
-    std::memcpy(out16, e->slots[slot].h_misc + 16 * (size_t)frame, 64);
+    std::memcpy(out16, status(e->slots[slot], frame), sizeof(uint32_t) * kStatusWords);
     return FSLIC_OK;
 }
 // lab build only: the last `nwords` words of frame `frame`'s candidate-leader array (where lab build 2 leaves the tile

@@ -621,7 +621,7 @@ __global__ __launch_bounds__(256) void k_cca_compress(CcaDev c, int nframes) {
 //                       redoes the step with std::partial_sort itself.
 // Kept leaders are ranked (raster buckets, LDS) and nfinal[node of the leader] = rank, i.e. labels 0,1,2.. in raster order
 // of each component's first pixel (src/cca.cpp:229-237).
-// status word (counters[3]): 0 = done here; 1 = area tie at the cut: the candidates have been written to
+// status word (kStSelect, counters[3]): 0 = done here; 1 = area tie at the cut: the candidates have been written to
 // dense_leader / dense_area SORTED BY LEADER (counters[1] = M), which is the order the reference feeds to
 // std::partial_sort, and the host only has to run that one call; 2 = too many candidates for this block, the
 // host gathers and sorts them itself.
@@ -1018,7 +1018,7 @@ __global__ __launch_bounds__(1024) void k_cca_select(CcaDev c, int cap) {
     if (tid < 8) s_v[tid] = 0;
     if (tid == 0) c.counters[2] = M;
     if (M > (uint32_t)cap) {
-        if (tid == 0) c.counters[3] = 2u;
+        if (tid == 0) c.counters[kStSelect - kStCca] = kSelectHost;
         return;
     }
     // (leader, node) -> area of that node: two dependent global loads per candidate (three until k_cca_compress wrote the node beside the
@@ -1076,11 +1076,11 @@ __global__ __launch_bounds__(1024) void k_cca_select(CcaDev c, int cap) {
             // libstdc++'s heap mechanics, so its __heap_select is replayed here, operation by operation, on the candidates
             // in ascending-leader order (the order the reference feeds it).  See tie_heap_select below.
             if (M > (uint32_t)kSelSortCap) {
-                if (tid == 0) c.counters[3] = 2u;
+                if (tid == 0) c.counters[kStSelect - kStCca] = kSelectHost;
                 return;
             }
             tie_heap_select(c, M, (uint32_t)K, astar, s_area, s_lead, s_key, s_bcnt, s_bstart, s_bfill, s_w);
-            if (tid == 0) c.counters[3] = 0u;
+            if (tid == 0) c.counters[kStSelect - kStCca] = kSelectDone;
             return;
         }
     }
@@ -1128,7 +1128,7 @@ __global__ __launch_bounds__(1024) void k_cca_select(CcaDev c, int cap) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) if (kept[u]) c.nfinal[nd[u]] = (uint16_t)r[u];
     }
-    if (tid == 0) c.counters[3] = 0u;
+    if (tid == 0) c.counters[kStSelect - kStCca] = kSelectDone;
 }
 
 // Grid of a pass over the nodes: one node per thread for up to N / 48 nodes (a structured frame has fewer once the closed small
@@ -1262,7 +1262,7 @@ __global__ __launch_bounds__(256) void k_cca_relabel(CcaDev c, ExportDev ex, int
         const int K = ex.K;
         for (int i = ((int)blockIdx.x - relabel_blocks) * blockDim.x + threadIdx.x; i < 4 * K; i += ((int)gridDim.x - relabel_blocks) * blockDim.x)
             out[i] = i < K ? yx[i] : rest[i - K];              // [0,K) positions, [K,4K) colour, member count, moved flag
-        if ((int)blockIdx.x == relabel_blocks && threadIdx.x < 16) ex.h_misc[16 * (size_t)z + threadIdx.x] = misc[threadIdx.x];
+        if ((int)blockIdx.x == relabel_blocks && threadIdx.x < kStatusWords) ex.h_misc[kStatusWords * (size_t)z + threadIdx.x] = misc[threadIdx.x];
         return;
     }
     c.select(z);

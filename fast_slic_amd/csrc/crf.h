@@ -154,16 +154,16 @@ struct fslic_crf {                          // SimpleCRF (src/simple-crf.hpp:70-
     fslic_engine* eng = nullptr;
     int capT = 0;                           // frames the buffers are sized for
     size_t cap_edges = 0;
-    float* d_q[2] = {nullptr, nullptr};     // [capT][C][K] each, d_q[cur] holds the current q
+    fslic::Device<float> d_q[2];                // [capT][C][K] each, d_q[cur] holds the current q
     int cur = 0;
-    float* d_unary = nullptr;
-    float* d_compat = nullptr;
-    float* d_scratch = nullptr;             // messages when they do not fit in LDS (crf_messages_in_lds)
-    fslic_cluster* d_cl = nullptr;
-    uint32_t* d_rowptr = nullptr;           // [capT * K + 1]
-    uint32_t* d_idx = nullptr;              // [cap_edges]
-    float2* d_edge = nullptr;               // per edge (energy, factor)
-    float4* d_temporal = nullptr;           // per node (energy, factor) towards t-1 and t+1
+    fslic::Device<float> d_unary;
+    fslic::Device<float> d_compat;
+    fslic::Device<float> d_scratch;             // messages when they do not fit in LDS (crf_messages_in_lds)
+    fslic::Device<fslic_cluster> d_cl;
+    fslic::Device<uint32_t> d_rowptr;           // [capT * K + 1]
+    fslic::Device<uint32_t> d_idx;              // [cap_edges]
+    fslic::Device<float2> d_edge;               // per edge (energy, factor)
+    fslic::Device<float4> d_temporal;           // per node (energy, factor) towards t-1 and t+1
     bool graph_uploaded = false;
 };
 

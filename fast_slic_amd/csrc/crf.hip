@@ -128,21 +128,10 @@ void launch_crf_expf(const float* in, float* out, size_t n, hipStream_t st) {
 }
 
 // ---- host side of inference() ------------------------------------------------------------------------------------------------------
-namespace {
-template <class T> int crf_alloc(T*& p, size_t count) {
-    HIPCHK(hipMalloc((void**)&p, std::max<size_t>(count * sizeof(T), 16)));
-    return FSLIC_OK;
-}
-template <class T> void crf_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-}  // namespace
-
 void crf_release_device(fslic_crf* crf) {
     if (crf->eng) (void)hipSetDevice(crf->eng->device);
-    crf_free(crf->d_q[0]); crf_free(crf->d_q[1]); crf_free(crf->d_unary); crf_free(crf->d_compat); crf_free(crf->d_scratch);
-    crf_free(crf->d_cl); crf_free(crf->d_rowptr); crf_free(crf->d_idx); crf_free(crf->d_edge); crf_free(crf->d_temporal);
+    crf->d_q[0].release(); crf->d_q[1].release(); crf->d_unary.release(); crf->d_compat.release(); crf->d_scratch.release();
+    crf->d_cl.release(); crf->d_rowptr.release(); crf->d_idx.release(); crf->d_edge.release(); crf->d_temporal.release();
     crf->capT = 0;
     crf->cap_edges = 0;
     crf->cur = 0;
@@ -194,16 +183,16 @@ static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, siz
     }
     // 2. buffers
     if (realloc) {
-        crf_free(crf->d_q[0]); crf_free(crf->d_q[1]); crf_free(crf->d_unary); crf_free(crf->d_scratch); crf_free(crf->d_cl);
-        crf_free(crf->d_rowptr); crf_free(crf->d_temporal);
+        crf->d_q[0].release(); crf->d_q[1].release(); crf->d_unary.release(); crf->d_scratch.release(); crf->d_cl.release();
+        crf->d_rowptr.release(); crf->d_temporal.release();
         const size_t n = (size_t)T * K;
         int rc;
-        if ((rc = crf_alloc(crf->d_q[0], (size_t)T * CK)) || (rc = crf_alloc(crf->d_q[1], (size_t)T * CK)) ||
-            (rc = crf_alloc(crf->d_unary, (size_t)T * CK)) || (rc = crf_alloc(crf->d_cl, n)) || (rc = crf_alloc(crf->d_rowptr, n + 1)) ||
-            (rc = crf_alloc(crf->d_temporal, n)))
+        if ((rc = crf->d_q[0].reserve((size_t)T * CK)) || (rc = crf->d_q[1].reserve((size_t)T * CK)) ||
+            (rc = crf->d_unary.reserve((size_t)T * CK)) || (rc = crf->d_cl.reserve(n)) || (rc = crf->d_rowptr.reserve(n + 1)) ||
+            (rc = crf->d_temporal.reserve(n)))
             return rc;
-        if (!crf_messages_in_lds((int)C) && (rc = crf_alloc(crf->d_scratch, (size_t)T * CK))) return rc;
-        if (!crf->d_compat && (rc = crf_alloc(crf->d_compat, C))) return rc;
+        if (!crf_messages_in_lds((int)C) && (rc = crf->d_scratch.reserve((size_t)T * CK))) return rc;
+        if (!crf->d_compat && (rc = crf->d_compat.reserve(C))) return rc;
         crf->capT = T;
         crf->cur = 0;
     }
@@ -226,9 +215,9 @@ static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, siz
                 std::copy(l.begin(), l.end(), idx.begin() + rowptr[(size_t)w * K + i]);
             }
         if (total > crf->cap_edges || !crf->d_idx) {
-            crf_free(crf->d_idx); crf_free(crf->d_edge);
+            crf->d_idx.release(); crf->d_edge.release();
             int rc;
-            if ((rc = crf_alloc(crf->d_idx, total)) || (rc = crf_alloc(crf->d_edge, total))) return rc;
+            if ((rc = crf->d_idx.reserve(total)) || (rc = crf->d_edge.reserve(total))) return rc;
             crf->cap_edges = total;
         }
         HIPCHK(hipMemcpyAsync(crf->d_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice, st));
@@ -308,8 +297,8 @@ int crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n) {
     int rc = lease.take();
     if (rc) return rc;
     hipStream_t st = e->slots[lease.slot].st;
-    float* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, 2 * n * sizeof(float)));
+    Device<float> d;
+    if ((rc = d.reserve(2 * n))) return rc;
     hipError_t he = hipMemcpyAsync(d, in, n * sizeof(float), hipMemcpyHostToDevice, st);
     if (he == hipSuccess) {
         launch_crf_expf(d, d + n, n, st);
@@ -317,7 +306,6 @@ int crf_expf_device(fslic_engine* e, const float* in, float* out, size_t n) {
     }
     if (he == hipSuccess) he = hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, st);
     const hipError_t hs = hipStreamSynchronize(st);
-    (void)hipFree(d);
     if (he != hipSuccess || hs != hipSuccess) return fail(FSLIC_E_HIP, std::string("crf_expf on the device: ") + hipGetErrorString(he != hipSuccess ? he : hs));
     return FSLIC_OK;
 }

@@ -16,6 +16,7 @@
 #include "launch.h"
 #include "../../include/fslic_hip.h"
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -44,6 +45,54 @@ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v
 inline float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 double now_us();
+
+// ---- buffers that own themselves: pinned host (Pinned<T>) or device (Device<T>) memory that grows on demand, is released with its
+// owner and reads as the T* it holds.  Move-only. ----
+template <class T, bool kDevice>
+class Buffer {
+    T* p_ = nullptr;
+    size_t cap_ = 0;                 // elements
+public:
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    Buffer& operator=(Buffer&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+    ~Buffer() { release(); }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    void release() {
+        if (p_) (void)(kDevice ? hipFree(p_) : hipHostFree(p_));
+        p_ = nullptr; cap_ = 0;
+    }
+    // room for `count` elements (never shrinks; the content is NOT kept when it grows; at least 16 bytes, so that a held buffer is never NULL)
+    int reserve(size_t count) {
+        if (p_ && cap_ >= count) return FSLIC_OK;
+        release();
+        const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+        const hipError_t err = kDevice ? hipMalloc((void**)&p_, bytes) : hipHostMalloc((void**)&p_, bytes);
+        if (err != hipSuccess) {
+            p_ = nullptr;
+            return fail(FSLIC_E_HIP, std::string(kDevice ? "hipMalloc(" : "hipHostMalloc(") + std::to_string(bytes) + " bytes): " + hipGetErrorString(err));
+        }
+        cap_ = count;
+        return FSLIC_OK;
+    }
+};
+template <class T> using Pinned = Buffer<T, false>;
+template <class T> using Device = Buffer<T, true>;
+
+// One group request as the C entry points receive it: up to kMaxGroup frames of one geometry under one parameter set.
+struct GroupJob {
+    fslic_params p{};
+    int H = 0, W = 0, K = 0, n = 0;
+    const uint8_t* d_rgb[kMaxGroup] = {};
+    fslic_cluster* clusters[kMaxGroup] = {};
+    uint16_t* d_out[kMaxGroup] = {};
+    // the frames of `j` behind this job's (the caller has made sure that they fit and ask for the same work)
+    void append(const GroupJob& j) {
+        for (int i = 0; i < j.n; i++) { d_rgb[n + i] = j.d_rgb[i]; clusters[n + i] = j.clusters[i]; d_out[n + i] = j.d_out[i]; }
+        n += j.n;
+    }
+};
 
 // Environment switches, read ONCE when the library is loaded (never on a call path).
 //   FSLIC_GROUP        frames per launch group of fslic_hip_iterate_batch (default 8, at most 16)
@@ -82,8 +131,7 @@ struct Slot {
     float assign_loop_ms = 0;        // sum of the fused assign launches' durations of the last group
     double assign_loop_px = 0;       // pixels those launches visited (all frames of the group)
     // device: one arena = [shared spatial tables][frame 0][frame 1]...; f / c hold frame 0's pointers
-    char* arena = nullptr;
-    size_t arena_cap = 0;
+    Device<char> arena;
     int cap_frames = 0;              // frames the arena is carved for
     size_t frame_bytes = 0;
     FrameDev f{};
@@ -93,37 +141,33 @@ struct Slot {
     size_t zero_bytes = 0;
     char* stamp_block = nullptr;     // the bin slots' generation stamps (cleared when carved and when the stamps wrap)
     size_t stamp_bytes = 0;
-    uint32_t* d_misc = nullptr;      // 64 B: ovf_cnt[0..1], err flags (bit 0: candidate-list overflow, bit 1: stale pixel under the fused cluster pass), ovf_cnt[2], cca counters[4]
+    uint32_t* d_misc = nullptr;      // frame 0's status words (kernels.h, StatusWord)
     uint32_t* d_yx_alt[2] = {nullptr, nullptr};   // the cluster pass's alternating position buffers (frame 0)
     uint8_t* d_rgb_stage = nullptr;
     uint16_t* d_out_stage = nullptr;
     int32_t* d_keep_leader = nullptr;
     uint16_t* d_keep_label = nullptr;
     // per-frame caller pointers of the current group: [0, kMaxGroup) inputs, [kMaxGroup, 2*kMaxGroup) outputs
-    void** d_ptrs = nullptr;         // device copy (allocated with the slot)
-    void** h_ptrs = nullptr;         // pinned staging
+    Device<void*> d_ptrs;            // device copy (allocated with the slot)
+    Pinned<void*> h_ptrs;            // pinned staging
     // shared tables
     uint16_t* d_patch = nullptr;
     uint32_t* d_lut = nullptr;
-    uint32_t* h_lut = nullptr;
+    Pinned<uint32_t> h_lut;
     uint16_t* d_tab = nullptr;
-    uint16_t* h_tab = nullptr;
+    Pinned<uint16_t> h_tab;
     // pinned host (device-accessible: the first cluster pass reads the centres from it, the export kernel writes the
     // results into it -- no copy commands in a group's launch sequence)
-    uint32_t* h_cl = nullptr;        // per frame 4K words: in [0,K) yx; out (yx, lab, n, moved)
-    size_t h_cl_words = 0;
-    uint32_t* h_misc = nullptr;      // per frame 16 words (copy of d_misc)
-    uint16_t* h_patch = nullptr;
-    size_t h_patch_cap = 0;
-    int32_t* h_cand_leader = nullptr;
-    uint32_t* h_cand_area = nullptr;
-    size_t h_cand_cap = 0;
-    uint32_t* d_gen = nullptr;       // device word: base of the bin generation stamps (FrameDev::gen_base)
+    Pinned<uint32_t> h_cl;           // per frame 4K words: in [0,K) yx; out (yx, lab, n, moved)
+    Pinned<uint32_t> h_misc;         // per frame its status words as the export left them: status(s, frame)
+    Pinned<uint16_t> h_patch;
+    Pinned<int32_t> h_cand_leader;   // the host top-K step's candidates (cca_finish_group)
+    Pinned<uint32_t> h_cand_area;
+    Device<uint32_t> d_gen;          // device word: base of the bin generation stamps (FrameDev::gen_base)
     uint64_t gen_host = 0;           // host mirror of *d_gen
     uint32_t gen_span_prev = 0;      // stamps the previous group used above its base (max_iter + 3): what the next group's first kernel adds to *d_gen
     uint32_t gen_step = 0;           // ... for the group being enqueued
     int keyH = 0, keyW = 0, keyK = 0;
-    size_t cand_capacity = 0;        // entries of the per-frame candidate arrays (>= N)
     // Recorded launch sequences (hipGraph, launch.h), one per distinct (geometry, options, group size, arena carving): a group
     // start is ~45 stream operations at ~3 us of host time each when enqueued one by one, ~8 us as one graph launch
     // (scripts/microbench/graph_launch.hip).  A key is recorded the second time it is seen.
@@ -137,6 +181,7 @@ struct Slot {
     std::vector<GraphEntry> graphs;
     int last_launch_mode = 0;        // 0 direct, 1 recorded this call, 2 replayed
     bool launch_timing = false;      // the engine's flag as it stood when this slot's current group was submitted
+    double t_begun_us = 0;           // FSLIC_HOST_TIMING: when group_begin returned
     // the slot's own host thread waits for a group by sleeping and polling instead of spinning (group.cpp, nap_wait)
     bool nap_wait = false;           // set for groups served by the slot thread
     double recent_wait_us[4] = {1e30, 1e30, 1e30, 1e30};   // its last four waits (1e30: none yet)
@@ -147,9 +192,7 @@ struct Slot {
     int nframes = 0;
     bool generic = false;
     fslic_params p{};
-    fslic_cluster* clusters[kMaxGroup] = {};
-    const uint8_t* d_rgb[kMaxGroup] = {};
-    uint16_t* d_out[kMaxGroup] = {};
+    fslic_cluster* clusters[kMaxGroup] = {};      // the group's Cluster[K] blocks (its frame buffers live in the device pointer table)
     float total_ms = 0, fa_ms = 0, lab_ms = 0, loop_ms = 0, cca_ms = 0;
     int last_path = 0;
     int n_host_topk = 0;             // frames of the last group whose top-K step ran on the host
@@ -165,11 +208,7 @@ struct Slot {
     struct Async {
         std::thread worker;
         bool has_job = false, done = false, quit = false;      // guarded by fslic_engine::mu
-        fslic_params p{};
-        int H = 0, W = 0, K = 0, n = 0;
-        const uint8_t* d_rgb[kMaxGroup] = {};
-        fslic_cluster* clusters[kMaxGroup] = {};
-        uint16_t* d_out[kMaxGroup] = {};
+        GroupJob job;
         int rc = 0;
         std::string err;
         bool from_queue = false;      // the job was taken from the engine's submit queue (the thread collects it itself)
@@ -177,25 +216,21 @@ struct Slot {
     };
     std::unique_ptr<Async> async;
     uint32_t* d_pre = nullptr;       // frame 0's preemptive state: is_updatable[K], is_active[K], cells, flags
-    uint32_t* h_upd = nullptr;       // pinned: is_updatable counters back from the device, per frame K words
-    size_t h_upd_words = 0;
+    Pinned<uint32_t> h_upd;          // is_updatable counters back from the device, per frame K words
     float* d_clf = nullptr;          // frame 0's float centroids ('noq')
-    float* h_clf = nullptr;          // pinned, per frame K * 8 floats: upload (y, x) / download (y, x, r, g, b)
-    size_t h_clf_floats = 0;
+    Pinned<float> h_clf;             // per frame K * 8 floats: upload (y, x) / download (y, x, r, g, b)
     // float-distance variants: f32 spatial patch (shared region of the arena) and its pinned staging
     float* d_patchf = nullptr;
-    float* h_patchf = nullptr;
-    size_t h_patchf_cap = 0;
+    Pinned<float> h_patchf;
     int pf_S = 0, pf_shift = -1, pf_variant = -1;
     float pf_compactness = -1.0f;
     bool pf_manhattan = true;
     // LSC variant: own arena = [shared tables][frame 0][frame 1]...; l holds frame 0's pointers
-    char* lsc_arena = nullptr;
-    size_t lsc_cap = 0, lsc_frame_bytes = 0, lsc_zero_bytes = 0;
+    Device<char> lsc_arena;
+    size_t lsc_frame_bytes = 0, lsc_zero_bytes = 0;
     char* lsc_zero = nullptr;
     LscDev l{};
-    float* h_lsc_lut = nullptr;      // pinned staging of the tables: [4][256] colour, [2][W], [2][H]
-    size_t h_lsc_lut_cap = 0;
+    Pinned<float> h_lsc_lut;         // staging of the tables: [4][256] colour, [2][W], [2][H]
     int lsc_H = 0, lsc_W = 0, lsc_K = 0, lsc_G = 0, lsc_S = 0;
     float lsc_compactness = -1.0f;
     // cached spatial configuration (configure_spatial)
@@ -204,12 +239,23 @@ struct Slot {
     float sp_compactness = 0.0f;
     // debug_mode (group.cpp, "the recording path"): the snapshot ring of the current call (RecLayout), grown on demand and kept
     bool recording = false;          // the current group is a recording one-frame call
-    char* d_rec = nullptr;
-    size_t d_rec_cap = 0;
+    Device<char> d_rec;
     std::vector<fslic_cluster> rec_clusters;   // the caller's Cluster block as it came in (snapshot -1, the unmoved positions)
 
     template <class T> T* at(T* p, int frame) const { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + (size_t)frame * frame_bytes); }
 };
+
+// the status words of frame `frame` of the slot's last group (host copy)
+inline uint32_t* status(const Slot& s, int frame) { return s.h_misc + (size_t)kStatusWords * frame; }
+
+// Where the reference leaves a cluster after an update (src/context.cpp:368-380): one that has moved (an update with members) at its
+// integer centre `yx` (y << 16 | x) or, for 'noq', at its float centroid (y, x; NULL otherwise); one that has not at the caller's
+// position `in`, clamped by assign()'s safeguard (src/context.cpp:208-211).
+inline void cluster_position(bool moved, uint32_t yx, const float* centroid, const fslic_cluster& in, int H, int W, float& y, float& x) {
+    if (moved && centroid) { y = centroid[0]; x = centroid[1]; }
+    else if (moved) { y = (float)(yx >> 16); x = (float)(yx & 0xFFFFu); }
+    else { x = clampf(in.x, 0.0f, (float)(W - 1)); y = clampf(in.y, 0.0f, (float)(H - 1)); }
+}
 
 }  // namespace fslic
 
@@ -218,8 +264,7 @@ struct fslic_engine {
     int group_size = 8;              // frames per launch group of iterate_batch (FSLIC_GROUP)
     bool launch_timing = false;      // bracket every subsampled assign launch with HIP events (fslic_hip_set_launch_timing)
     std::vector<fslic::Slot> slots;
-    uint16_t* d_gamma = nullptr;
-    uint16_t* d_labtbl = nullptr;
+    fslic::Device<uint16_t> d_gamma, d_labtbl;
     fslic::LabTables tables{};
     // slot ownership and the completion of asynchronous groups
     std::mutex mu;
@@ -234,14 +279,7 @@ struct fslic_engine {
     // Submissions wait here for a slot thread (guarded by mu).  With batching on (fslic_hip_pipeline_batching), a thread
     // that finds several compatible submissions waiting serves them as ONE group: fewer, fuller launches when the
     // caller submits faster than the device finishes.
-    struct PipeJob {
-        fslic_params p{};
-        int H = 0, W = 0, K = 0, n = 0;
-        const uint8_t* d_rgb[fslic::kMaxGroup] = {};
-        fslic_cluster* clusters[fslic::kMaxGroup] = {};
-        uint16_t* d_out[fslic::kMaxGroup] = {};
-    };
-    std::deque<PipeJob> pipe_q;
+    std::deque<fslic::GroupJob> pipe_q;
     int pipe_inflight = 0;           // groups taken from the queue and not yet collected
     int pipe_batch_frames = 0;       // 0: one submission per group; otherwise the most frames a group may gather
     bool pipe_gathering = false;     // a slot thread is waiting briefly for a companion of the submission it took
@@ -266,18 +304,25 @@ void free_slot(Slot& s);
 int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G);
 int ensure_prepared(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G);
 int prepare_lsc(Slot& s, int H, int W, int K, int S, int G, float compactness);
-int ensure_cand_capacity(Slot& s, size_t M);
 
 // ---- group.cpp ----
 int validate(const fslic_params* p, int H, int W, int K, int& S);
+// An entry point's arguments as a job (what cannot be copied -- a missing array or parameter block -- is refused here), and what every
+// group is checked for: its size, validate(), no frame pointer NULL.  Both run on the caller's thread.
+int fill_job(GroupJob& j, const fslic_params* p, int H, int W, int K, int n,
+             const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out);
+int check_job(const GroupJob& j, int& S);
 int upload_ptrs(Slot& s, int n, const uint8_t* const* d_rgb, uint16_t* const* d_out);
 CcaDev cca_view(const Slot& s, int i0, const uint16_t* d_in0, size_t in_stride, int K, int min_threshold);
 void cca_enqueue(Slot& s, const CcaDev& c, int i0, int n, const ExportDev* ex = nullptr);
 int cca_finish_group(Slot& s, int first, int n, const uint16_t* d_in0, size_t in_stride, int K, int thres);
 // record: the recording path of debug_mode (one frame; only fslic_hip_iterate / fslic_hip_iterate_device ask for it)
-int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K, int n,
-                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out, bool record = false);
+int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record = false);
 int group_finish(fslic_engine* e, Slot& s);
+// After a failure on the slot's stream: waits until nothing touches the caller's buffers any more; the error message survives.
+void drain_failed(Slot& s);
+// One group from start to completion: group_begin, group_finish, and drain_failed if either fails.
+int run_group(fslic_engine* e, Slot& s, const GroupJob& job, bool record = false);
 std::string make_timing_report(const Slot& s);
 void set_thread_timing_report(const std::string& json);
 const std::string& thread_timing_report();

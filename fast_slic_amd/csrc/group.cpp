@@ -39,6 +39,24 @@ int validate(const fslic_params* p, int H, int W, int K, int& S) {
     return FSLIC_OK;
 }
 
+int fill_job(GroupJob& j, const fslic_params* p, int H, int W, int K, int n,
+             const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out) {
+    if (n < 1 || n > (int)kMaxGroup || !d_rgb || !clusters || !d_out) return fail(FSLIC_E_INVALID, "bad group arguments");
+    if (!p) return fail(FSLIC_E_INVALID, "params is NULL");
+    j.p = *p; j.H = H; j.W = W; j.K = K; j.n = n;
+    for (int i = 0; i < n; i++) { j.d_rgb[i] = d_rgb[i]; j.clusters[i] = clusters[i]; j.d_out[i] = d_out[i]; }
+    return FSLIC_OK;
+}
+
+int check_job(const GroupJob& j, int& S) {
+    if (j.n < 1 || j.n > (int)kMaxGroup) return fail(FSLIC_E_INVALID, "bad group arguments");
+    const int rc = validate(&j.p, j.H, j.W, j.K, S);
+    if (rc) return rc;
+    for (int i = 0; i < j.n; i++)
+        if (!j.clusters[i] || !j.d_rgb[i] || !j.d_out[i]) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    return FSLIC_OK;
+}
+
 // ---- the top-K / ranking step of ConnectivityEnforcer::execute (src/cca.cpp:205-237) on the host ----
 // Input: candidates (components with area >= threshold) in ASCENDING LEADER order, which is ascending component
 // number, the order the reference hands to std::partial_sort.  libstdc++'s std::partial_sort decides ties at
@@ -108,17 +126,18 @@ void cca_enqueue(Slot& s, const CcaDev& c, int i0, int n, const ExportDev* ex) {
 // device sorts): gather + sort on the host, frame by frame, then chain + relabel again for that frame.
 int cca_finish_group(Slot& s, int first, int n, const uint16_t* d_in0, size_t in_stride, int K, int thres) {
     int n_slow = 0;
-    for (int i = first; i < first + n; i++) n_slow += s.h_misc[16 * (size_t)i + 4 + 3] == 2;
+    for (int i = first; i < first + n; i++) n_slow += status(s, i)[kStSelect] == kSelectHost;
     if (n_slow == 0) return FSLIC_OK;
     for (int i = first; i < first + n && n_slow; i++) {
-        uint32_t* hm = s.h_misc + 16 * (size_t)i;
-        if (hm[4 + 3] != 2) continue;
+        const uint32_t* hm = status(s, i);
+        if (hm[kStSelect] != kSelectHost) continue;
         const CcaDev c1 = cca_view(s, i, d_in0, in_stride, K, thres);
         int32_t* d_dl = s.at(s.c.cand_leader, i);      // dense (appended by k_cca_compress), unordered
         uint32_t* d_da = s.at(s.c.cand_area, i);
-        const uint32_t M = hm[4 + 1];
-        int rc = ensure_cand_capacity(s, std::max<size_t>(M, 1) * 2);
-        if (rc) return rc;
+        const uint32_t M = hm[kStCands];
+        const size_t cap = std::max<size_t>((size_t)M * 2, 16384);      // (two halves: the gathered list, then the same in leader order)
+        int rc;
+        if ((rc = s.h_cand_leader.reserve(cap)) || (rc = s.h_cand_area.reserve(cap))) return rc;
         launch_cca_gather_area(c1, s.st);
         HIPCHK(hipMemcpyAsync(s.h_cand_leader, d_dl, sizeof(int32_t) * M, hipMemcpyDeviceToHost, s.st));
         HIPCHK(hipMemcpyAsync(s.h_cand_area, d_da, sizeof(uint32_t) * M, hipMemcpyDeviceToHost, s.st));
@@ -134,7 +153,7 @@ int cca_finish_group(Slot& s, int first, int n, const uint16_t* d_in0, size_t in
         // and from there to the device on the slot's OWN stream: a copy on the default stream fails while another slot
         // of the engine was capturing its graph (stream capture is gone since: launch.h)
         int32_t* kl = s.h_cand_leader;
-        uint16_t* kb = reinterpret_cast<uint16_t*>(s.h_cand_area);
+        uint16_t* kb = reinterpret_cast<uint16_t*>(s.h_cand_area.get());
         uint32_t n_keep = 0;
         select_kept_sorted(sl, sa, M, K, kl, kb, n_keep);
         int32_t* d_kl = s.at(s.d_keep_leader, i);
@@ -452,7 +471,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // barriers).  The status words are final once the select kernel has run, the cluster state since the loop ended.
     ExportDev ex{};
     ex.frame_bytes = fb; ex.K = K; ex.yx_cur = yx_cur; ex.lab_n_moved = yx_up + K; ex.misc0 = s.at(s.d_misc, i0);
-    ex.h_cl = s.h_cl + (size_t)i0 * 4 * K; ex.h_stride = 4 * (size_t)K; ex.h_misc = s.h_misc + 16 * (size_t)i0;
+    ex.h_cl = s.h_cl + (size_t)i0 * 4 * K; ex.h_stride = 4 * (size_t)K; ex.h_misc = status(s, i0);
     cca_enqueue(s, c, i0, n, &ex);
     if (timed) HIPCHK(hipEventRecord(s.ev[4], s.st));
     if (pre) HIPCHK(hipMemcpy2DAsync(s.h_upd + (size_t)i0 * K, sizeof(uint32_t) * (size_t)K, f.cl_upd, fb,
@@ -535,22 +554,20 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
     return FSLIC_OK;
 }
 
-int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K, int n,
-                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out, bool record) {
+int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     const double t_begin = now_us();
+    const fslic_params* p = &job.p;
+    const int H = job.H, W = job.W, K = job.K, n = job.n;
     int S = 0;
     s.recording = false;
-    int rc = validate(p, H, W, K, S);
+    int rc = check_job(job, S);
     if (rc) return rc;
-    if (n < 1 || n > kMaxGroup) return fail(FSLIC_E_INTERNAL, "bad group size");
     if (record && n != 1) return fail(FSLIC_E_INTERNAL, "a recording group holds one frame");
-    for (int i = 0; i < n; i++)
-        if (!clusters[i] || !d_rgb[i] || !d_out[i]) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     rc = ensure_prepared(e, s, H, W, K, S, n);           // (carves for at least the engine's batching reserve)
     if (rc) return rc;
     const int cap_frames = s.cap_frames;
     s.H = H; s.W = W; s.K = K; s.S = S; s.p = *p; s.nframes = n;
-    for (int i = 0; i < n; i++) { s.clusters[i] = clusters[i]; s.d_rgb[i] = d_rgb[i]; s.d_out[i] = d_out[i]; }
+    std::copy(job.clusters, job.clusters + n, s.clusters);
     rc = configure_spatial(s, S, p);
     if (rc) return rc;
     if (p->variant == FSLIC_VARIANT_LSC) {
@@ -561,42 +578,30 @@ int group_begin(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, i
         rc = configure_patchf(s, S, p);
         if (rc) return rc;
     }
-    if (p->variant == FSLIC_VARIANT_REALDIST_NOQ && s.h_clf_floats < (size_t)s.cap_frames * K * 8) {
-        if (s.h_clf) hipHostFree(s.h_clf);
-        s.h_clf = nullptr; s.h_clf_floats = 0;
-        HIPCHK(hipHostMalloc((void**)&s.h_clf, sizeof(float) * 8 * (size_t)K * s.cap_frames));
-        s.h_clf_floats = (size_t)s.cap_frames * K * 8;
-    }
-    rc = upload_ptrs(s, n, d_rgb, d_out);
+    if (p->variant == FSLIC_VARIANT_REALDIST_NOQ && (rc = s.h_clf.reserve((size_t)s.cap_frames * K * 8))) return rc;
+    rc = upload_ptrs(s, n, job.d_rgb, job.d_out);
     if (rc) return rc;
     if (record) {
-        s.rec_clusters.assign(clusters[0], clusters[0] + K);
+        s.rec_clusters.assign(job.clusters[0], job.clusters[0] + K);
         s.recording = true;       // (before rec_layout: it reads s.H, s.W, s.K, s.p)
         const size_t need = rec_layout(s).bytes;
-        if (s.d_rec_cap < need) {
-            if (s.d_rec) HIPCHK(hipFree(s.d_rec));
-            s.d_rec = nullptr; s.d_rec_cap = 0;
-            if (hipMalloc((void**)&s.d_rec, need) != hipSuccess) {
-                (void)hipGetLastError();
-                s.recording = false;
-                return fail(FSLIC_E_HIP, "debug_mode: hipMalloc of the snapshot ring (" + std::to_string(need) + " bytes) failed");
-            }
-            s.d_rec_cap = need;
+        if (s.d_rec.reserve(need)) {
+            (void)hipGetLastError();
+            s.recording = false;
+            return fail(FSLIC_E_HIP, "debug_mode: hipMalloc of the snapshot ring (" + std::to_string(need) + " bytes) failed");
         }
     }
     s.generic = p->variant == FSLIC_VARIANT_SLIC && (e->lab_force_generic.load() != 0 || !s.sp_tiled_ok || record);
-    if (p->preemptive && s.h_upd_words < (size_t)s.cap_frames * K) {
-        if (s.h_upd) hipHostFree(s.h_upd);
-        s.h_upd = nullptr; s.h_upd_words = 0;
-        HIPCHK(hipHostMalloc((void**)&s.h_upd, sizeof(uint32_t) * (size_t)K * s.cap_frames));
-        s.h_upd_words = (size_t)s.cap_frames * K;
-    }
+    if (p->preemptive && (rc = s.h_upd.reserve((size_t)s.cap_frames * K))) return rc;
     stage_group(e, s, 0, n, true);
     rc = launch_group(e, s, n);
     if (rc) return rc;
     s.have_pre = true;
     s.last_path = s.generic ? 1 : 0;
-    if (knobs().host_timing) fprintf(stderr, "[fslic host] group_begin n=%d: %.1f us | slot %d begin %.1f .. %.1f\n", n, now_us() - t_begin, (int)(&s - e->slots.data()), t_begin, now_us());
+    if (knobs().host_timing) {
+        fprintf(stderr, "[fslic host] group_begin n=%d: %.1f us | slot %d begin %.1f .. %.1f\n", n, now_us() - t_begin, (int)(&s - e->slots.data()), t_begin, now_us());
+        s.t_begun_us = now_us();
+    }
     return FSLIC_OK;
 }
 
@@ -660,13 +665,14 @@ int group_finish(fslic_engine* e, Slot& s) {
     const double t_ev = now_us();
     int n_host_topk = 0;
     for (int i = 0; i < n; i++) {
-        n_host_topk += s.h_misc[16 * (size_t)i + 4 + 3] == 2;
-        // Flags of the tiled kernels.  Bit 1: a visited pixel that no window covered kept its label while the cluster pass was
+        const uint32_t* hm = status(s, i);
+        n_host_topk += hm[kStSelect] == kSelectHost;
+        // Flags of the tiled kernels.  kFlagStalePixel: a visited pixel that no window covered kept its label while the cluster pass was
         // fused into the assign kernel (its sums reached the owner through global atomics that nothing orders before the owner's
-        // finaliser): that frame alone is redone with the separate cluster pass.  Bit 0: a block's candidate list overflowed: that
+        // finaliser): that frame alone is redone with the separate cluster pass.  kFlagListOverflow: a block's candidate list overflowed: that
         // frame alone is redone with the generic kernel.
-        for (int attempt = 0; attempt < 2 && !s.generic && s.h_misc[16 * (size_t)i + 2] != 0; attempt++) {
-            const bool overflow = (s.h_misc[16 * (size_t)i + 2] & 1u) != 0;
+        for (int attempt = 0; attempt < 2 && !s.generic && hm[kStFlags] != 0; attempt++) {
+            const bool overflow = (hm[kStFlags] & kFlagListOverflow) != 0;
             if (knobs().host_timing) fprintf(stderr, "[fslic host] frame %d redone with %s\n", i, overflow ? "the generic kernel (candidate-list overflow)" : "the separate cluster pass (stale pixel)");
             stage_group(e, s, i, 1, false);
             s.gen_step = s.gen_span_prev;                 // past the stamps of the pass just made (same span)
@@ -675,13 +681,13 @@ int group_finish(fslic_engine* e, Slot& s) {
             if (rc) return rc;
             HIPCHK(hipStreamSynchronize(s.st));
             if (overflow) {
-                if (s.h_misc[16 * (size_t)i + 2] != 0) return fail(FSLIC_E_INTERNAL, "generic path reported a candidate overflow");
+                if (hm[kStFlags] != 0) return fail(FSLIC_E_INTERNAL, "generic path reported a candidate overflow");
                 s.last_path = 1;
             } else {
                 __atomic_fetch_add(&s.n_separate_redo, 1, __ATOMIC_RELAXED);      // (read by fslic_hip_separate_pass_redos without the engine lock)
             }
         }
-        if (!s.generic && s.h_misc[16 * (size_t)i + 2] != 0) return fail(FSLIC_E_INTERNAL, "a redone frame still carries a kernel flag");
+        if (!s.generic && hm[kStFlags] != 0) return fail(FSLIC_E_INTERNAL, "a redone frame still carries a kernel flag");
     }
     {
         int rc = cca_finish_group(s, 0, n, s.f.labels, s.frame_bytes, K, thres);
@@ -690,6 +696,7 @@ int group_finish(fslic_engine* e, Slot& s) {
     s.n_host_topk = n_host_topk;
     const double t_cca = now_us();
     // write the cluster state back the way the reference leaves it
+    const bool noq = s.p.variant == FSLIC_VARIANT_REALDIST_NOQ;
     for (int i = 0; i < n; i++) {
         const uint32_t* yx = s.h_cl + (size_t)i * 4 * K;
         const uint32_t* lab = yx + K;
@@ -700,16 +707,9 @@ int group_finish(fslic_engine* e, Slot& s) {
             cl[k].r = (float)(lab[k] & 255u);                 // src/context.cpp:132-134 / :370-372
             cl[k].g = (float)((lab[k] >> 8) & 255u);
             cl[k].b = (float)((lab[k] >> 16) & 255u);
-            if (moved[k] && s.p.variant == FSLIC_VARIANT_REALDIST_NOQ) {      // src/context.cpp:374-380
-                const float* c = s.h_clf + ((size_t)i * K + k) * 8;
-                cl[k].y = c[0]; cl[k].x = c[1]; cl[k].r = c[2]; cl[k].g = c[3]; cl[k].b = c[4];
-            } else if (moved[k]) {                             // src/context.cpp:368-369
-                cl[k].y = (float)(yx[k] >> 16);
-                cl[k].x = (float)(yx[k] & 0xFFFFu);
-            } else {                                           // assign() safeguard, src/context.cpp:208-211
-                cl[k].x = clampf(cl[k].x, 0.0f, (float)(W - 1));
-                cl[k].y = clampf(cl[k].y, 0.0f, (float)(H - 1));
-            }
+            const float* c = noq ? s.h_clf + ((size_t)i * K + k) * 8 : nullptr;
+            if (moved[k] && c) { cl[k].r = c[2]; cl[k].g = c[3]; cl[k].b = c[4]; }      // src/context.cpp:374-380
+            cluster_position(moved[k] != 0, yx[k], c, cl[k], H, W, cl[k].y, cl[k].x);
             if (s.p.max_iter > 0) cl[k].num_members = nm[k];  // src/context.cpp:362
             cl[k].is_updatable = s.p.preemptive ? (uint8_t)s.h_upd[(size_t)i * K + k] : 2;   // src/preemptive.h:59-67, :131-139
             cl[k].is_active = 1;                               // src/preemptive.h:69-74
@@ -719,6 +719,20 @@ int group_finish(fslic_engine* e, Slot& s) {
         fprintf(stderr, "[fslic host] group_finish n=%d slot %d at %.1f .. %.1f: sync wait %.1f us, events %.1f us, host top-K (%d frames) %.1f us, write-back %.1f us (device %.1f us)\n",
                 n, (int)(&s - e->slots.data()), t_begin, now_us(), t_sync - t_begin, t_ev - t_sync, n_host_topk, t_cca - t_ev, now_us() - t_cca, s.total_ms * 1e3);
     return FSLIC_OK;
+}
+
+void drain_failed(Slot& s) {
+    const std::string msg = last_error();
+    (void)hipStreamSynchronize(s.st);
+    (void)hipGetLastError();
+    set_last_error(msg);
+}
+
+int run_group(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
+    int rc = group_begin(e, s, job, record);
+    if (rc == FSLIC_OK) rc = group_finish(e, s);
+    if (rc != FSLIC_OK) drain_failed(s);
+    return rc;
 }
 
 // BaseContext::get_timing_report (src/context.h:74) in the fstimer schema (src/timer.cpp:4-18), durations from the
@@ -761,8 +775,8 @@ const std::string& thread_recorder_report() { return t_recorder; }
 
 // RecorderSnapshot::gen / Recorder::gen (src/recorder.h) over the ring of the slot's last call, after group_finish.  The Cluster view of
 // a snapshot is the reference's Cluster[K] at that moment: snapshot -1 holds the caller's block with the fetched colours and
-// is_updatable = cooldown (PreemptiveGrid::initialize, src/preemptive.h:59-66); after an update a cluster that has moved (an update
-// with members) sits at its centroid, one that has not at the caller's position clamped by assign()'s safeguard (src/context.cpp:208-211).
+// is_updatable = cooldown (PreemptiveGrid::initialize, src/preemptive.h:59-66); after an update a cluster sits where cluster_position()
+// says, as in the write-back of group_finish.
 int make_recorder_report(Slot& s, std::string& out) {
     const int H = s.H, W = s.W, K = s.K;
     if (!s.recording) {
@@ -793,14 +807,10 @@ int make_recorder_report(Slot& s, std::string& out) {
             float y = a.y, x = a.x, r = (float)(lab & 255u), g = (float)((lab >> 8) & 255u), b = (float)((lab >> 16) & 255u);
             uint32_t upd = 2, act = a.is_active, nm = a.num_members;
             if (i > 0) {
-                if (c[3 * (size_t)K + k] && noq) {
-                    const float* cf = reinterpret_cast<const float*>(c + 6 * (size_t)K) + 8 * (size_t)k;
-                    y = cf[0]; x = cf[1]; r = cf[2]; g = cf[3]; b = cf[4];
-                } else if (c[3 * (size_t)K + k]) {
-                    y = (float)(c[k] >> 16); x = (float)(c[k] & 0xFFFFu);
-                } else {
-                    x = clampf(a.x, 0.0f, (float)(W - 1)); y = clampf(a.y, 0.0f, (float)(H - 1));
-                }
+                const bool moved = c[3 * (size_t)K + k] != 0;
+                const float* cf = noq ? reinterpret_cast<const float*>(c + 6 * (size_t)K) + 8 * (size_t)k : nullptr;
+                if (moved && cf) { r = cf[2]; g = cf[3]; b = cf[4]; }
+                cluster_position(moved, c[k], cf, a, H, W, y, x);
                 nm = c[2 * (size_t)K + k];
                 if (pre) { upd = c[4 * (size_t)K + k]; act = c[5 * (size_t)K + k]; }
             }

@@ -58,12 +58,13 @@ int fslic_hip_rgb_to_lab(fslic_engine* e, int H, int W, const uint8_t* rgb, int 
     if (H <= 0 || W <= 0 || (long long)H * W >= (1ll << 31)) return fail(FSLIC_E_INVALID, "bad image size");
     HIPCHK(hipSetDevice(e->device));
     const size_t N = (size_t)H * W;
-    uint8_t* d_rgb = nullptr;
-    uint32_t* d_lab = nullptr;
-    HIPCHK(hipMalloc((void**)&d_rgb, N * 3));
-    if (hipMalloc((void**)&d_lab, N * 4) != hipSuccess) { hipFree(d_rgb); return fail(FSLIC_E_HIP, "hipMalloc failed"); }
+    Device<uint8_t> d_rgb;
+    Device<uint32_t> d_lab;
+    int rc = d_rgb.reserve(N * 3);
+    if (rc) return rc;
+    if (d_lab.reserve(N)) return fail(FSLIC_E_HIP, "hipMalloc failed");
     SlotLease lease(e);                       // the slot's stream and pointer table for the length of the call
-    if (lease.take() != FSLIC_OK) { hipFree(d_rgb); hipFree(d_lab); return FSLIC_E_INVALID; }
+    if (lease.take() != FSLIC_OK) return FSLIC_E_INVALID;
     Slot& sl = e->slots[lease.slot];
     hipStream_t st = sl.st;
     hipMemcpyAsync(d_rgb, rgb, N * 3, hipMemcpyHostToDevice, st);
@@ -71,13 +72,11 @@ int fslic_hip_rgb_to_lab(fslic_engine* e, int H, int W, const uint8_t* rgb, int 
     f.N = (int)N; f.H = H; f.W = W;
     f.lab = d_lab;
     const uint8_t* in1[1] = {d_rgb};
-    if (upload_ptrs(sl, 1, in1, nullptr) != FSLIC_OK) { hipFree(d_rgb); hipFree(d_lab); return FSLIC_E_HIP; }
-    f.rgbs = reinterpret_cast<const uint8_t* const*>(sl.d_ptrs);
+    if (upload_ptrs(sl, 1, in1, nullptr) != FSLIC_OK) return FSLIC_E_HIP;
+    f.rgbs = reinterpret_cast<const uint8_t* const*>(sl.d_ptrs.get());
     launch_rgb_to_lab(f, 1, convert, e->tables, false, st);
     hipMemcpyAsync(lab4, d_lab, N * 4, hipMemcpyDeviceToHost, st);
-    hipError_t err = hipStreamSynchronize(st);
-    hipFree(d_rgb);
-    hipFree(d_lab);
+    const hipError_t err = hipStreamSynchronize(st);
     if (err != hipSuccess) return fail(FSLIC_E_HIP, hipGetErrorString(err));
     return FSLIC_OK;
 }
@@ -110,9 +109,9 @@ static int enforce_connectivity_impl(fslic_engine* e, uint16_t* labels, int H, i
     if (rc) return rc;
     const CcaDev c = cca_view(s, 0, s.d_out_stage, 0, K, min_threshold);
     cca_enqueue(s, c, 0, 1);
-    HIPCHK(hipMemcpyAsync(s.h_misc, s.d_misc, 64, hipMemcpyDeviceToHost, s.st));
+    HIPCHK(hipMemcpyAsync(status(s, 0), s.d_misc, sizeof(uint32_t) * kStatusWords, hipMemcpyDeviceToHost, s.st));
     HIPCHK(hipStreamSynchronize(s.st));
-    if (n_nodes) *n_nodes = s.h_misc[4];      // CcaDev::counters[0]
+    if (n_nodes) *n_nodes = status(s, 0)[kStNodes];
     rc = cca_finish_group(s, 0, 1, s.d_out_stage, 0, K, min_threshold);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(labels, s.d_out_stage, N * 2, hipMemcpyDeviceToHost, s.st));
@@ -133,24 +132,23 @@ namespace {
 // A caller's plane: used in place when it already lives in device memory, staged through a temporary otherwise.
 struct Staged {
     void* p = nullptr;
-    bool owned = false;
-    ~Staged() { if (owned && p) hipFree(p); }
+    Device<char> own;                // the temporary, where there is one
 };
 bool is_device_pointer(const void* p) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain host memory
     return a.type == hipMemoryTypeDevice;
 }
+int device_scratch(size_t bytes, Staged& out) {
+    const int rc = out.own.reserve(bytes);
+    out.p = out.own;
+    return rc;
+}
 int stage_in(const void* src, size_t bytes, hipStream_t st, Staged& out) {
     if (is_device_pointer(src)) { out.p = const_cast<void*>(src); return FSLIC_OK; }
-    HIPCHK(hipMalloc(&out.p, std::max<size_t>(bytes, 16)));
-    out.owned = true;
+    const int rc = device_scratch(bytes, out);
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out.p, src, bytes, hipMemcpyHostToDevice, st));
-    return FSLIC_OK;
-}
-int device_scratch(size_t bytes, Staged& out) {
-    HIPCHK(hipMalloc(&out.p, std::max<size_t>(bytes, 16)));
-    out.owned = true;
     return FSLIC_OK;
 }
 int check_map(const fslic_engine* e, int H, int W, int K) {
@@ -314,9 +312,8 @@ int fslic_hip_copy_bandwidth(fslic_engine* e, size_t bytes, int reps, double* gb
     if (rc) return rc;
     Slot& s = e->slots[lease.slot];
     HIPCHK(hipSetDevice(e->device));
-    void *a = nullptr, *b = nullptr;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) {
-        if (a) hipFree(a);
+    Device<char> a, b;
+    if (a.reserve(bytes) || b.reserve(bytes)) {
         (void)hipGetLastError();
         return fail(FSLIC_E_HIP, "hipMalloc failed for the copy probe");
     }
@@ -331,7 +328,6 @@ int fslic_hip_copy_bandwidth(fslic_engine* e, size_t bytes, int reps, double* gb
         if (err == hipSuccess) err = hipEventElapsedTime(&ms, s.ev[0], s.ev[1]);
         if (r > 0 && ms > 0.0f) best = std::max(best, 2.0 * (double)bytes / ((double)ms * 1e-3) / 1e9);
     }
-    hipFree(a); hipFree(b);
     if (err != hipSuccess) return fail(FSLIC_E_HIP, std::string("copy probe: ") + hipGetErrorString(err));
     *gb_per_s = best;
     return FSLIC_OK;

@@ -31,6 +31,25 @@ constexpr int kCcaTilePx = kCcaTile * kCcaTileH;
 #endif
 constexpr int kMaxGroup = FSLIC_MAX_GROUP;       // frames of one group share every launch (frame index = a grid dimension)
 
+// The status words of a frame: kStatusWords (16) dwords inside the frame's zeroed region of the arena, which the last kernel of the
+// connectivity pass copies into the engine's pinned block (ExportDev), one such row per frame of the group.
+enum StatusWord {
+    kStSpill0 = 0, kStSpill1 = 1,   // FrameDev::ovf_cnt[0..1]: entries in the spill lists of the two bin parities
+    kStFlags = 2,                   // FrameDev::err_flag: kFlag* bits set by the tiled assign kernels
+    kStSpill2 = 3,                  // FrameDev::ovf_cnt[2] (the fused cluster pass rotates over three lists)
+    kStCca = 4,                     // CcaDev::counters: the next four words
+    kStNodes = kStCca + 0,          //   number of nodes (append cursor of k_cca_local)
+    kStCands = kStCca + 1,          //   M = number of candidates (append cursor of k_cca_compress)
+    kStCandsSeen = kStCca + 2,      //   M again, as k_cca_select read it
+    kStSelect = kStCca + 3          //   kSelect* status of the top-K step
+};                                  // the rest is unused (lab builds keep time stamps there)
+constexpr int kStatusWords = 16;
+constexpr uint32_t kFlagListOverflow = 1u;   // a block's LDS candidate list overflowed: the host redoes the frame with the generic kernel
+constexpr uint32_t kFlagStalePixel = 2u;     // a visited pixel no window covered kept its label under the fused cluster pass: redone with the separate pass
+constexpr uint32_t kSelectDone = 0u;         // the device resolved the top-K step
+constexpr uint32_t kSelectTie = 1u;          // area tie at the cut, candidates left sorted by leader (k_cca_select; resolved on the device since)
+constexpr uint32_t kSelectHost = 2u;         // more candidates than the device sorts: the host gathers and sorts (cca_finish_group)
+
 // One cluster as the kernels see it (16 B, one ds_read_b128 / global_load_dwordx4).
 //   yx  = y << 16 | x          (integer centre, src/context.cpp:262 casts to int16)
 //   lab = L | a << 8 | b << 16 (integer colour, always <= 255 per channel)
@@ -99,7 +118,7 @@ struct FrameDev {
     uint32_t* ovf_cnt[3];      // 1    (the third buffer serves the fused cluster pass only: read / append / clear rotate over three)
     ClusterRec* ovf_items[3];  // K
     uint32_t* cl_arrive;       // K  fused cluster pass: assign blocks that have delivered their partial sums of the cluster in this pass
-    uint32_t* err_flag;        // != 0: a block overflowed its LDS candidate list -> host reruns generic
+    uint32_t* err_flag;        // kFlag* bits (status word kStFlags): != 0 -> the host redoes the frame
     // LDS spatial table of the tiled kernel (lut_words == 0: fixed-point mode, no table)
     const uint32_t* lut;       // lut_words entries: patch value << 16, or kHuge for out-of-window indices
     int lut_words, lut_row, lut_oow;   // index = ux' + uy' * lut_row, ux'/uy' = |d| if <= S else lut_oow
@@ -200,7 +219,7 @@ struct CcaDev {
     uint16_t* nfinal;     // NP: final labels (global roots: select / chain; every node after k_cca_chain)
     uint32_t* vedge;      // tiles * 2 * kCcaTileH: (label | number << 16) of every tile's first and last column, row by row
     uint32_t* roots;      // the frame's nodes, dense: counters[0] of them (capacity NP)
-    uint32_t* counters;   // [0] number of nodes (append cursor of k_cca_local), [1] M = number of candidates (append cursor of k_cca_compress), [2] M again, [3] select status
+    uint32_t* counters;   // the frame's status words from kStCca on
     int32_t* cand_leader; // dense candidate list (components with area >= threshold): their leaders (capacity NP)
     uint32_t* cand_area;  //   same capacity: the host top-K path gathers the candidates' areas into it
     __host__ __device__ __forceinline__ void select(int z) {
@@ -323,17 +342,17 @@ void launch_noq_assign(const FrameDev& f, float coef, bool manhattan, int nframe
 void launch_preempt_update(const FrameDev& f, int nframes, int buf, int sbuf, bool rebin_all, float l1_thres, hipStream_t st);
 // connectivity
 void launch_cca_phase1(const CcaDev& c, int nframes, hipStream_t st);   // local CCL, border merge, compress, collect
-// device top-K + ranking, including the area tie at the cut; counters[3] = status (see k_cca_select)
+// device top-K + ranking, including the area tie at the cut; status word kStSelect (see k_cca_select)
 void launch_cca_select(const CcaDev& c, int nframes, hipStream_t st);
 // End of a group: what the last kernel also writes into the engine's pinned host blocks (device-accessible), so that a
 // group's launch sequence holds no copy command.  Pointers are frame 0's (frame z: + z * frame_bytes); frame z lands at
-// h_cl + z * h_stride words: [0,K) positions, [K,4K) colour / member count / moved flag; h_misc + 16 z: the status words.
+// h_cl + z * h_stride words: [0,K) positions, [K,4K) colour / member count / moved flag; h_misc + kStatusWords * z: the status words.
 struct ExportDev {
     size_t frame_bytes;
     int K;                          // 0: nothing to export
     const uint32_t* yx_cur;         // the current position buffer
     const uint32_t* lab_n_moved;    // FrameDev::cl_lab (cl_n and cl_moved follow it, K words each)
-    const uint32_t* misc0;          // the frame's 16 status words
+    const uint32_t* misc0;          // the frame's status words
     uint32_t* h_cl;
     size_t h_stride;
     uint32_t* h_misc;

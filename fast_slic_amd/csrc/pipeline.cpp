@@ -145,8 +145,8 @@ void pipeline_collect(fslic_engine* e, Slot& s) {
     s.pending = false;
 }
 
-bool same_work(const fslic_engine::PipeJob& j, const Slot::Async& a) {
-    return j.H == a.H && j.W == a.W && j.K == a.K && memcmp(&j.p, &a.p, sizeof(fslic_params)) == 0;
+bool same_work(const GroupJob& a, const GroupJob& b) {
+    return a.H == b.H && a.W == b.W && a.K == b.K && memcmp(&a.p, &b.p, sizeof(fslic_params)) == 0;
 }
 
 void slot_worker(fslic_engine* e, Slot* s) {
@@ -162,16 +162,15 @@ void slot_worker(fslic_engine* e, Slot* s) {
             if (!a.has_job) {
                 // the submit queue's head, plus -- with batching on -- the submissions behind it that ask for the same work,
                 // as long as the group stays within the frame limit
-                const fslic_engine::PipeJob& j0 = e->pipe_q.front();
-                a.p = j0.p; a.H = j0.H; a.W = j0.W; a.K = j0.K; a.n = 0; a.jobs = 0;
+                GroupJob& g = a.job;
+                const int unit = e->pipe_q.front().n;
+                g = e->pipe_q.front(); g.n = 0; a.jobs = 0;      // the head's work; its frames arrive with the first gather
                 const int limit = std::min(e->pipe_batch_frames, (int)kMaxGroup);
-                const int unit = j0.n;
                 auto gather = [&](int max_jobs) {
                     while (!e->pipe_q.empty() && a.jobs < max_jobs) {
-                        const fslic_engine::PipeJob& j = e->pipe_q.front();
-                        if (a.jobs > 0 && (!same_work(j, a) || a.n + j.n > limit)) break;
-                        for (int i = 0; i < j.n; i++) { a.d_rgb[a.n + i] = j.d_rgb[i]; a.clusters[a.n + i] = j.clusters[i]; a.d_out[a.n + i] = j.d_out[i]; }
-                        a.n += j.n; a.jobs++;
+                        const GroupJob& j = e->pipe_q.front();
+                        if (a.jobs > 0 && (!same_work(j, g) || g.n + j.n > limit)) break;
+                        g.append(j); a.jobs++;
                         e->pipe_q.pop_front();
                     }
                 };
@@ -190,7 +189,7 @@ void slot_worker(fslic_engine* e, Slot* s) {
                 // meanwhile), so that the first groups of a burst are as full as the later ones.
                 // (only while the caller IS in the middle of a burst -- its last submission is a few microseconds old: the slot that takes
                 // the last submission of a burst would otherwise wait 100 us for a companion that never comes, 3 % of the driver's region)
-                if (a.n + unit <= limit && e->pipe_q.empty() && !e->pipe_gathering && now_us() - e->pipe_last_submit_us < 50.0) {
+                if (g.n + unit <= limit && e->pipe_q.empty() && !e->pipe_gathering && now_us() - e->pipe_last_submit_us < 50.0) {
                     e->pipe_gathering = true;
                     e->cv_work.wait_for(lk, std::chrono::microseconds(100), [&] { return !e->pipe_q.empty() || a.quit; });
                     e->pipe_gathering = false;
@@ -202,16 +201,9 @@ void slot_worker(fslic_engine* e, Slot* s) {
             }
         }
         if (took) { e->cv.notify_all(); e->cv_work.notify_all(); }      // room in the queue (callers); the gathering wait is over (the other slot threads)
-        int rc = group_begin(e, *s, &a.p, a.H, a.W, a.K, a.n, a.d_rgb, a.clusters, a.d_out);
-        s->nap_wait = true;
-        if (rc == FSLIC_OK) rc = group_finish(e, *s);
+        s->nap_wait = true;          // (read by group_finish alone)
+        const int rc = run_group(e, *s, a.job);      // (on a failure nothing runs against the caller's buffers any more once the group is reported done)
         s->nap_wait = false;
-        if (rc != FSLIC_OK) {        // nothing may still run against the caller's buffers once the group is reported done
-            const std::string msg = last_error();
-            (void)hipStreamSynchronize(s->st);
-            (void)hipGetLastError();
-            set_last_error(msg);
-        }
         {
             std::lock_guard<std::mutex> lk(e->mu);
             a.rc = rc;
@@ -236,28 +228,23 @@ void ensure_worker(fslic_engine* e, Slot& s) {
 }
 
 // caller holds e->mu; the slot is neither busy nor pending
-void hand_over(fslic_engine* e, Slot& s, const fslic_params* p, int H, int W, int K, int n,
-               const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_labels) {
+void hand_over(fslic_engine* e, Slot& s, const GroupJob& job) {
     ensure_worker(e, s);
     Slot::Async& a = *s.async;
-    a.p = *p; a.H = H; a.W = W; a.K = K; a.n = n; a.from_queue = false; a.jobs = 1;
+    a.job = job; a.from_queue = false; a.jobs = 1;
     s.launch_timing = e->launch_timing;      // sampled on the caller's thread: the worker may start later
-    for (int i = 0; i < n; i++) { a.d_rgb[i] = d_rgb[i]; a.clusters[i] = clusters[i]; a.d_out[i] = d_labels[i]; }
     a.done = false;
     a.has_job = true;
     s.pending = true;
 }
 
-int check_group_args(fslic_engine* e, const fslic_params* p, int H, int W, int K, int n_frames,
-                     const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_labels) {
+// the arguments of an asynchronous entry point as a checked job: argument errors surface on the caller's thread
+int checked_job(GroupJob& job, fslic_engine* e, const fslic_params* p, int H, int W, int K, int n_frames,
+                const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_labels) {
     if (!e) return fail(FSLIC_E_INVALID, "engine is NULL");
-    if (n_frames < 1 || n_frames > (int)kMaxGroup || !d_rgb || !clusters || !d_labels) return fail(FSLIC_E_INVALID, "bad group arguments");
     int S = 0;
-    const int rc = validate(p, H, W, K, S);          // argument errors surface on the caller's thread
-    if (rc) return rc;
-    for (int i = 0; i < n_frames; i++)
-        if (!clusters[i] || !d_rgb[i] || !d_labels[i]) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    return FSLIC_OK;
+    const int rc = fill_job(job, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
+    return rc ? rc : check_job(job, S);
 }
 
 }  // namespace
@@ -281,7 +268,8 @@ extern "C" {
 
 int fslic_hip_submit_group(fslic_engine* e, int slot, const fslic_params* p, int H, int W, int K, int n_frames,
                            const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_labels) {
-    int rc = check_group_args(e, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
+    GroupJob job;
+    int rc = checked_job(job, e, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
     if (rc) return rc;
     if (slot < 0 || slot >= (int)e->slots.size()) return fail(FSLIC_E_INVALID, "slot out of range");
     {
@@ -294,7 +282,7 @@ int fslic_hip_submit_group(fslic_engine* e, int slot, const fslic_params* p, int
             if (!s.busy && !s.pending) break;
             e->cv.wait(lk);
         }
-        hand_over(e, s, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
+        hand_over(e, s, job);
     }
     e->cv_work.notify_all();          // the slot's thread
     return FSLIC_OK;
@@ -331,7 +319,8 @@ int fslic_hip_group_done(fslic_engine* e, int slot) {
 // while the queue is full (two submissions per slot).
 int fslic_hip_pipeline_submit(fslic_engine* e, const fslic_params* p, int H, int W, int K, int n_frames,
                               const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_labels) {
-    int rc = check_group_args(e, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
+    GroupJob job;
+    int rc = checked_job(job, e, p, H, W, K, n_frames, d_rgb, clusters, d_labels);
     if (rc) return rc;
     {
         std::unique_lock<std::mutex> lk(e->mu);
@@ -339,11 +328,8 @@ int fslic_hip_pipeline_submit(fslic_engine* e, const fslic_params* p, int H, int
         const size_t cap = 2 * e->slots.size();
         e->cv.wait(lk, [&] { return e->pipe_rc != FSLIC_OK || e->pipe_q.size() < cap; });
         if (e->pipe_rc != FSLIC_OK) { set_last_error(e->pipe_err); return e->pipe_rc; }   // reported once more by drain
-        e->pipe_q.emplace_back();
-        fslic_engine::PipeJob& j = e->pipe_q.back();
+        e->pipe_q.push_back(job);
         e->pipe_last_submit_us = now_us();
-        j.p = *p; j.H = H; j.W = W; j.K = K; j.n = n_frames;
-        for (int i = 0; i < n_frames; i++) { j.d_rgb[i] = d_rgb[i]; j.clusters[i] = clusters[i]; j.d_out[i] = d_labels[i]; }
     }
     e->cv_work.notify_all();          // the slot threads (and the one waiting for a companion)
     return FSLIC_OK;

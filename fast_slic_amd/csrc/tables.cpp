@@ -239,7 +239,7 @@ int configure_spatial(Slot& s, int S, const fslic_params* p) {
         };
         int w1 = 0, n1 = 0, d1 = 0, ws = 0, ns = 0, ds = 0;
         const int st3 = std::min(stride_it, 3);
-        if (build2d(1, 16, reinterpret_cast<uint32_t*>(s.h_tab), w1, n1, d1) &&
+        if (build2d(1, 16, reinterpret_cast<uint32_t*>(s.h_tab.get()), w1, n1, d1) &&
             build2d(st3, 8, reinterpret_cast<uint32_t*>(s.h_tab + kTabMaxBytes / 2), ws, ns, ds)) {
             f.tab_words = w1; f.tab_nrpad = n1; f.tab_dyoff = d1;
             f.tabs_words = ws; f.tabs_nrpad = ns; f.tabs_dyoff = ds;
