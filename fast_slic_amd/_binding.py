@@ -57,6 +57,8 @@ EXPORTS = [
     "fslic_hip_crf_expf_host", "fslic_hip_crf_expf_device",
     # superpixel pooling (fast_slic_amd/pool.py)
     "fslic_hip_pool_workspace_size", "fslic_hip_pool", "fslic_hip_pool_finalize", "fslic_hip_unpool",
+    # region adjacency graph (fast_slic_amd/rag.py)
+    "fslic_hip_rag_workspace_size", "fslic_hip_rag_accumulate", "fslic_hip_rag_compact",
 ]
 
 _lib = None
@@ -153,6 +155,8 @@ def load_library():
             _declare_crf(lib)
         if hasattr(lib, "fslic_hip_pool"):
             _declare_pool(lib)
+        if hasattr(lib, "fslic_hip_rag_accumulate"):
+            _declare_rag(lib)
         _lib = lib
         return lib
 
@@ -189,6 +193,16 @@ def _declare_pool(lib):
     lib.fslic_hip_pool_finalize.argtypes = [i32, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
     lib.fslic_hip_unpool.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, C.c_float, vp]
     for name in ("pool_workspace_size", "pool", "pool_finalize", "unpool"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
+
+
+def _declare_rag(lib):
+    """Signatures of the region adjacency graph entry points (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    lib.fslic_hip_rag_workspace_size.argtypes = [i32, i32, i32, i64, C.POINTER(sz)]
+    lib.fslic_hip_rag_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
+    lib.fslic_hip_rag_compact.argtypes = [i32, vp, i32, i32, i64, vp, sz, vp, vp, vp, i64]
+    for name in ("rag_workspace_size", "rag_accumulate", "rag_compact"):
         getattr(lib, "fslic_hip_" + name).restype = i32
 
 

@@ -17,6 +17,11 @@ constexpr int kPoolLsb = -96;          // weight of bit 0 of limb 0
 enum PoolReduce { kPoolSum = 0, kPoolMean = 1, kPoolMax = 2 };
 enum PoolLabel { kLabelU16 = 0, kLabelI32 = 1, kLabelI64 = 2 };
 
+// (kernels of pool.hip and rag.hip) a label as an index: K when it is not in [0, K) (the int16 map's -1 is 0xFFFF >= K, K <= 65534)
+static __device__ __forceinline__ uint32_t canon(uint16_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
+static __device__ __forceinline__ uint32_t canon(int32_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
+static __device__ __forceinline__ uint32_t canon(int64_t v, uint32_t K) { return (unsigned long long)v < (unsigned long long)K ? (uint32_t)v : K; }
+
 inline size_t pool_acc_bytes(int N, int C, int K, int reduce) {
     const size_t cells = (size_t)N * (size_t)C * (size_t)K;
     return reduce == kPoolMax ? cells * 8 : cells * 8 * kPoolLimbs;

@@ -18,11 +18,6 @@ namespace fslic {
 constexpr int kPoolRows = 16;          // rows of a tile (one label per lane and row held in registers)
 constexpr int kPoolMaxList = 64 * kPoolRows;
 
-// a label as an index: K when it is not in [0, K) (the int16 map's -1 is 0xFFFF >= K, K <= 65534)
-static __device__ __forceinline__ uint32_t canon(uint16_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
-static __device__ __forceinline__ uint32_t canon(int32_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
-static __device__ __forceinline__ uint32_t canon(int64_t v, uint32_t K) { return (unsigned long long)v < (unsigned long long)K ? (uint32_t)v : K; }
-
 // float -> uint32 whose unsigned order is the float order (-0.0 below +0.0), and back
 static __device__ __forceinline__ uint32_t ordered_bits(float x) {
     const uint32_t u = __float_as_uint(x);

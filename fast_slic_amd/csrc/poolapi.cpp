@@ -2,6 +2,7 @@
 // caller names the device and the stream and owns every buffer.  Every argument is checked before the first HIP call.
 #include "engine_internal.h"
 #include "pool.h"
+#include "streamapi.h"
 
 using namespace fslic;
 
@@ -15,31 +16,6 @@ int check_common(int device, int N, int C, int K, int reduce) {
     if ((long long)N * C * K >= (1ll << 40)) return fail(FSLIC_E_INVALID, "N * C * K must be below 2^40");
     return FSLIC_OK;
 }
-int check_map(int N, int H, int W, int label_type) {
-    if (H < 1 || W < 1) return fail(FSLIC_E_INVALID, "H and W must be positive");
-    if ((long long)H * W >= (1ll << 31)) return fail(FSLIC_E_INVALID, "H * W must be below 2^31");
-    if ((long long)N * ((long long)H * W / 1024 + 1) >= (1ll << 31)) return fail(FSLIC_E_INVALID, "too many frames");
-    if (label_type != kLabelU16 && label_type != kLabelI32 && label_type != kLabelI64) return fail(FSLIC_E_INVALID, "unknown label type");
-    return FSLIC_OK;
-}
-
-// Makes `device` current for the scope of a call and restores the calling thread's device afterwards.
-struct DeviceScope {
-    int prev = -1;
-    int enter(int device) {
-        int n = 0;
-        HIPCHK(hipGetDeviceCount(&n));
-        if (device >= n) return fail(FSLIC_E_INVALID, "no such HIP device");
-        HIPCHK(hipGetDevice(&prev));
-        HIPCHK(hipSetDevice(device));
-        (void)hipGetLastError();               // a stale error of an earlier call on this thread is not ours to report
-        return FSLIC_OK;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 int launched() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("pool launch: ") + hipGetErrorString(e));
@@ -60,7 +36,7 @@ int fslic_hip_pool_workspace_size(int N, int C, int K, int reduce, size_t* bytes
 int fslic_hip_pool(int device, void* stream, int N, int C, int H, int W, int K, int reduce, const float* features,
                    const void* labels, int label_type, void* workspace, size_t workspace_bytes) {
     int rc = check_common(device, N, C, K, reduce);
-    if (rc || (rc = check_map(N, H, W, label_type))) return rc;
+    if (rc || (rc = check_label_map(N, H, W, label_type))) return rc;
     if (!features || !labels || !workspace) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     const size_t need = pool_workspace_bytes(N, C, K, reduce);
     if (workspace_bytes < need) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
@@ -88,7 +64,7 @@ int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int r
 int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
                      int label_type, const int32_t* argmax, float fill, float* out) {
     int rc = check_common(device, N, C, K, kPoolSum);
-    if (rc || (rc = check_map(N, H, W, label_type))) return rc;
+    if (rc || (rc = check_label_map(N, H, W, label_type))) return rc;
     if (!values || !labels || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;

@@ -351,6 +351,29 @@ int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int r
 int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
                      int label_type, const int32_t* argmax, float fill, float* out);
 
+/* ---- Region adjacency graph of a label map (NEW surface, no counterpart in the reference; Python: fast_slic_amd/rag.py) ----
+ * Every unordered pair of labels that touch, with the number of neighbouring pixel pairs across their boundary and, with an image, per
+ * channel the sum of |difference| over those pixel pairs.  connectivity 4 looks at every pixel's right and down neighbour, 8 also
+ * down-right and down-left: every pixel pair of the whole plane once.  A pixel whose label is outside [0, K) is in no pair.  Entries
+ * as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device restored, every argument checked
+ * before the first HIP call (FSLIC_E_INVALID).
+ *   labels : [N][H][W] of label_type (FSLIC_LABEL_*), H * W < 2^29        image : uint8 [N][H][W][C], C in 1 .. 4, or NULL with C == 0
+ * Pairs are collected per frame in an open-addressing table of `capacity` slots (a power of two in [64, 2^31]); the workspace holds a
+ * header of 16 + 4 N bytes (rounded up to 16) and N * capacity * (8 + 8 C) bytes of tables.  Header: uint32 overflow flag, uint32
+ * unused, uint64 used by compact, then uint32 [N]: the distinct pairs of each frame.  The flag is set when a frame's table got more
+ * than half full or a probe run exceeded its bound; the tables are then incomplete and the caller starts over with a larger capacity
+ * (2 * min(K (K - 1) / 2, 4 H W) pairs rounded up to a power of two always suffice for the load).  All integer arithmetic: the
+ * result does not depend on the capacity or on the order of execution. */
+int fslic_hip_rag_workspace_size(int N, int K, int C, long long capacity, size_t* bytes);
+/* Clears the workspace, then fills the tables and the header. */
+int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int K, int connectivity, const void* labels, int label_type,
+                             const uint8_t* image, int C, long long capacity, void* workspace, size_t workspace_bytes);
+/* The occupied slots of the workspace of a completed fslic_hip_rag_accumulate (same stream, same N, C, capacity), densely and in NO
+ * specified order: keys[i] = frame << 32 | lo << 16 | hi (lo < hi), boundary[i] its pixel pairs, contrast[i][C] (optional) its channel
+ * sums.  At most max_edges rows are written (the sum of the header's counts is what there is). */
+int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capacity, void* workspace, size_t workspace_bytes,
+                          int64_t* keys, int32_t* boundary, int64_t* contrast, long long max_edges);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 
