@@ -7,7 +7,11 @@
 `features` is a float32 tensor on a ROCm GPU, channel-first.  `labels` is the int16 map Slic.iterate returns (numpy or torch; -1 means
 "no label") or an int32 / int64 torch tensor; labels outside [0, K) are ignored.  The work runs on torch's current stream of the
 features' device, without host synchronisation; scratch memory comes from torch's caching allocator.  Results are bitwise reproducible
-(no float atomics: per-tile partials are combined exactly in fixed point and rounded once) and differentiable (sum, mean, max, unpool).
+(no float atomics) and differentiable (sum, mean, max, unpool).  The sum: one f32 partial per tile of 16 x 64 pixels and label; every
+partial is truncated towards zero to a multiple of 2^-96 (partials and inputs below 2^-96 vanish; from 2^-73 on nothing is lost), the
+truncated partials are added exactly in fixed point and the total is rounded once to f32, ties to even.  A zero total is +0.0; a total
+of magnitude 2^128 - 2^103 or more is +-inf; an in-tile partial that overflows f32 leaves its segment's entry unspecified, like an Inf
+input.
 [C, K] is SimpleCRFFrame's [num_classes, num_nodes]: `v.cpu().numpy()` goes straight into set_proba.  This module imports torch; the
 package itself does not import it.
 """

@@ -331,8 +331,15 @@ int fslic_hip_crf_expf_device(fslic_engine* e, const float* in, float* out, size
  * the first HIP call (FSLIC_E_INVALID).
  *   features : float [N][C][H][W], contiguous          labels : [N][H][W] of label_type; values outside [0, K) belong to no segment
  *   values   : float [N][C][K]                          counts : int32 [N][K]              argmax : int32 [N][C][K]
- * Results are bitwise reproducible: per-tile float partials in a fixed order, combined exactly in a fixed-point accumulator with
- * integer atomics and rounded once (sum within 4e-6 of the sum of |x|; exact when every partial sum is exact in f32).
+ * Results are bitwise reproducible: per-tile float partials in a fixed order (a tile is 16 rows x 64 columns, aligned at the frame's
+ * origin), combined in a fixed-point accumulator with integer atomics and rounded once (sum within 4e-6 of the sum of |x|).  Every
+ * partial enters the accumulator truncated towards zero to a multiple of 2^-96, so partials (and inputs) below 2^-96 in magnitude,
+ * subnormal ones included, vanish; the truncated partials are added exactly and the total is rounded once to f32, nearest with ties
+ * to even.  Hence the sum is the correctly rounded sum of the partials when every partial is a multiple of 2^-96 (any f32 of
+ * magnitude 2^-73 or more is), and the correctly rounded sum of the pixels when in addition every partial is exact in f32.  A
+ * total of zero is +0.0; a total of magnitude 2^128 - 2^103 or more (FLT_MAX plus half an ulp) is +-inf, while partials that
+ * pass 2^128 on the way and cancel again do no harm.  An in-tile f32 partial that overflows leaves its segment's entry unspecified,
+ * like an Inf input.
  * The workspace holds N * C * K * 56 bytes (sum, mean) or N * C * K * 8 bytes (max), plus N * K * 4 bytes of counts (rounded up to 8). */
 enum { FSLIC_POOL_SUM = 0, FSLIC_POOL_MEAN = 1, FSLIC_POOL_MAX = 2 };
 enum { FSLIC_LABEL_U16 = 0 /* the int16 map of iterate(), -1 = 0xFFFF */, FSLIC_LABEL_I32 = 1, FSLIC_LABEL_I64 = 2 };
