@@ -59,6 +59,8 @@ EXPORTS = [
     "fslic_hip_pool_workspace_size", "fslic_hip_pool", "fslic_hip_pool_finalize", "fslic_hip_unpool",
     # region adjacency graph (fast_slic_amd/rag.py)
     "fslic_hip_rag_workspace_size", "fslic_hip_rag_accumulate", "fslic_hip_rag_compact",
+    # SimpleCRF inference on torch tensors (fast_slic_amd/crf_torch.py)
+    "fslic_hip_crf_tensor_workspace_size", "fslic_hip_crf_tensor_inference",
 ]
 
 _lib = None
@@ -157,6 +159,8 @@ def load_library():
             _declare_pool(lib)
         if hasattr(lib, "fslic_hip_rag_accumulate"):
             _declare_rag(lib)
+        if hasattr(lib, "fslic_hip_crf_tensor_inference"):
+            _declare_crf_tensor(lib)
         _lib = lib
         return lib
 
@@ -203,6 +207,15 @@ def _declare_rag(lib):
     lib.fslic_hip_rag_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
     lib.fslic_hip_rag_compact.argtypes = [i32, vp, i32, i32, i64, vp, sz, vp, vp, vp, i64]
     for name in ("rag_workspace_size", "rag_accumulate", "rag_compact"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
+
+
+def _declare_crf_tensor(lib):
+    """Signatures of the entry points of SimpleCRF inference on device tensors (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    lib.fslic_hip_crf_tensor_workspace_size.argtypes = [i32, i32, i32, i64, C.POINTER(sz)]
+    lib.fslic_hip_crf_tensor_inference.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
+    for name in ("crf_tensor_workspace_size", "crf_tensor_inference"):
         getattr(lib, "fslic_hip_" + name).restype = i32
 
 

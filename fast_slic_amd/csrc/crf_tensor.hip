@@ -1,0 +1,169 @@
+// crf_tensor.hip -- SimpleCRF inference (src/simple-crf.cpp:62-153) on device tensors the caller owns (crf_tensor.h; the C ABI is in
+// crfapi.cpp).  The arithmetic is crf.hip's, operation by operation; the layout of the sweep is not.
+//   k_crf_tensor_start  the starting q: q0, or crf_expf(-unaries) (SimpleCRF::initialize).
+//   k_crf_tensor_edges  once per call, one thread per (frame, node): the row's bounds clamped into [0, nnz] and to non-decreasing,
+//                       per neighbour entry the spatial energy and the member factor (an index outside [0, K) makes the entry dead),
+//                       per node the temporal energies and factors towards t-1 and t+1.  Clusters are built in registers from the
+//                       channel-first yxrgb planes and the member counts.
+//   k_crf_tensor_sweep  one Jacobi sweep.  A block is 64 consecutive nodes of one frame (the lanes) times one wavefront per class
+//                       slice (wave v does classes v, v + waves, ...), so every [N][C][K] plane is read and written coalesced.
+//                       Messages of (node, class) -> LDS [C][64]; barrier; the compatibility sum of (node, class) over the other
+//                       classes from LDS and its crf_expf -> LDS [C][64]; barrier; every thread adds its node's C exponentials in
+//                       ascending order itself (C LDS reads, no third barrier) and divides its own.  Above kCrfTensorLdsClasses
+//                       classes the messages go to a plane of the workspace and the exponentials to q_out, with one more barrier
+//                       between the sums and the in-place division.
+// Every grid is exact (one trip): blocks of 256 over N * C * K (start) and N * K (edges), N * ceil(K / 64) blocks (sweep); all of
+// them are below 2^31 because N * C * K and N * K are.
+#include "crf.h"
+#include "crf_tensor.h"
+
+// The roundings are crf.hip's (see there and crf.h): products fused exactly where the reference build fuses them, nothing else.
+#pragma clang fp contract(off)
+
+namespace fslic {
+
+__global__ __launch_bounds__(256) void k_crf_tensor_start(const float* __restrict__ unaries, const float* __restrict__ q0,
+                                                          float* __restrict__ out, size_t n) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    out[p] = q0 ? q0[p] : crf_expf(-unaries[p]);
+}
+
+// The Cluster of node i from a frame's planes: y, x, r, g, b of yxrgb[5][K] and the 32 bits of members[K].
+static __device__ __forceinline__ fslic_cluster crf_tensor_cluster(const float* __restrict__ planes, const int32_t* __restrict__ members,
+                                                                   size_t K, int i) {
+    fslic_cluster c = {};
+    c.y = planes[i];
+    c.x = planes[K + i];
+    c.r = planes[2 * K + i];
+    c.g = planes[3 * K + i];
+    c.b = planes[4 * K + i];
+    c.num_members = (uint32_t)members[i];
+    return c;
+}
+
+__global__ __launch_bounds__(256) void k_crf_tensor_edges(CrfTensorParams dp, const float* __restrict__ yxrgb, const int32_t* __restrict__ members,
+                                                          const int64_t* __restrict__ offsets, const int32_t* __restrict__ idx,
+                                                          uint2* __restrict__ rows, float2* __restrict__ edge, float4* __restrict__ temporal) {
+    const int n = dp.N * dp.K;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const int K = dp.K;
+    const int w = g / K, i = g - w * K;
+    const float* planes = yxrgb + (size_t)w * 5 * K;
+    const int32_t* mem = members + (size_t)w * K;
+    const fslic_cluster ci = crf_tensor_cluster(planes, mem, K, i);
+    // whatever the offsets hold, 0 <= k0 <= k1 <= nnz: idx[k] and edge[k] are touched for k0 <= k < k1 only, here and in the sweep
+    long long k0 = offsets[g], k1 = offsets[g + 1];
+    k0 = k0 < 0 ? 0 : (k0 > dp.nnz ? dp.nnz : k0);
+    k1 = k1 < 0 ? 0 : (k1 > dp.nnz ? dp.nnz : k1);
+    if (k1 < k0) k1 = k0;
+    rows[g] = make_uint2((uint32_t)k0, (uint32_t)k1);
+    for (uint32_t k = (uint32_t)k0; k < (uint32_t)k1; ++k) {
+        const int32_t j = idx[k];
+        if ((uint32_t)j >= (uint32_t)K) {              // contributes nothing, as pooling treats a label outside [0, K)
+            edge[k] = make_float2(0.0f, kCrfDeadEntry);
+            continue;
+        }
+        const fslic_cluster cj = crf_tensor_cluster(planes, mem, K, j);
+        // calc_spatial_pairwise_energy(neighbor, i) (simple-crf.cpp:86): 0 for a self-loop
+        const float e = j == i ? 0.0f : crf_spatial_energy(dp.p, cj, ci);
+        edge[k] = make_float2(e, crf_member_factor(cj.num_members, ci.num_members));
+    }
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (dp.temporal && w > 0) {                        // simple-crf.cpp:90-93
+        const fslic_cluster cp = crf_tensor_cluster(planes - (size_t)5 * K, mem - K, K, i);
+        t.x = crf_temporal_energy(dp.p, ci, cp);
+        t.y = crf_member_factor(cp.num_members, ci.num_members);
+    }
+    if (dp.temporal && w < dp.N - 1) {                 // :95-99
+        const fslic_cluster cn = crf_tensor_cluster(planes + (size_t)5 * K, mem + K, K, i);
+        t.z = crf_temporal_energy(dp.p, ci, cn);
+        t.w = crf_member_factor(cn.num_members, ci.num_members);
+    }
+    temporal[g] = t;
+}
+
+// m[cls * stride] and ex[cls * stride] are the message and the exponential of (the thread's node, cls): LDS, or the workspace's
+// message plane and q_out itself above kCrfTensorLdsClasses classes.
+template <bool LDS>
+__global__ __launch_bounds__(kCrfTensorNodes * kCrfTensorWaves) void k_crf_tensor_sweep(
+        CrfTensorParams dp, const uint2* __restrict__ rows, const int32_t* __restrict__ idx, const float2* __restrict__ edge,
+        const float4* __restrict__ temporal, const float* __restrict__ unary, const float* __restrict__ compat,
+        const float* __restrict__ q_in, float* q_out, float* msg) {
+    extern __shared__ float s_crf[];
+    const int C = dp.C, K = dp.K;
+    const int tiles = (K + kCrfTensorNodes - 1) / kCrfTensorNodes;
+    const int w = blockIdx.x / tiles;                                          // the frame
+    const int lane = threadIdx.x % kCrfTensorNodes, wave = threadIdx.x / kCrfTensorNodes, waves = blockDim.x / kCrfTensorNodes;
+    const int i = (blockIdx.x - w * tiles) * kCrfTensorNodes + lane;           // the node
+    const bool live = i < K;                                                   // (a lane past the frame's end only keeps the barriers)
+    const size_t CK = (size_t)C * K, base = (size_t)w * CK;
+    float* m = LDS ? s_crf + lane : msg + base + i;
+    float* ex = LDS ? s_crf + (size_t)C * kCrfTensorNodes + lane : q_out + base + i;
+    const size_t stride = LDS ? (size_t)kCrfTensorNodes : (size_t)K;
+    const bool has_prev = dp.temporal && w > 0, has_next = dp.temporal && w < dp.N - 1;
+
+    // message passing (simple-crf.cpp:71-102): neighbours in list order, then t-1, then t+1; each term fma(e * q, factor, message)
+    if (live) {
+        const uint2 r = rows[(size_t)w * K + i];
+        const float4 t = temporal[(size_t)w * K + i];
+        for (int cls = wave; cls < C; cls += waves) {
+            const float* qc = q_in + base + (size_t)cls * K;
+            float message = 0.0f;
+            for (uint32_t k = r.x; k < r.y; ++k) {
+                const float2 es = edge[k];
+                if (es.y == kCrfDeadEntry) continue;                           // idx[k] is outside [0, K)
+                message = __builtin_fmaf(es.x * qc[idx[k]], es.y, message);
+            }
+            if (has_prev) message = __builtin_fmaf(t.x * qc[i - (ptrdiff_t)CK], t.y, message);
+            if (has_next) message = __builtin_fmaf(t.z * qc[i + CK], t.w, message);
+            m[cls * stride] = message;
+        }
+    }
+    __syncthreads();
+    // compatibility transform (:104-114): the Potts sum over the other classes in ascending order (fused), then expf
+    if (live) {
+        for (int cls = wave; cls < C; cls += waves) {
+            float gathered = 0.0f;
+            for (int o = 0; o < cls; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
+            for (int o = cls + 1; o < C; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
+            ex[cls * stride] = crf_expf(-(unary[base + (size_t)cls * K + i] + gathered));
+        }
+    }
+    __syncthreads();
+    // normalisation (:116-133): the sum over classes in ascending order from 0.0f, clamped at 1e-5 (a double comparison, as written there)
+    float sum = 0.0f;
+    if (live) {
+        for (int cls = 0; cls < C; ++cls) sum += ex[cls * stride];
+        if ((double)sum < 1e-5) sum = (float)1e-5;
+    }
+    if (!LDS) __syncthreads();                                                 // ex is q_out: every sum is taken before a division lands
+    if (live)
+        for (int cls = wave; cls < C; cls += waves) q_out[base + (size_t)cls * K + i] = ex[cls * stride] / sum;
+}
+
+void launch_crf_tensor_start(const float* unaries, const float* q0, float* out, size_t n, hipStream_t st) {
+    launch(k_crf_tensor_start, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, unaries, q0, out, n);
+}
+
+void launch_crf_tensor_edges(const CrfTensorParams& dp, const float* yxrgb, const int32_t* members, const int64_t* offsets,
+                             const int32_t* indices, uint2* rows, float2* edge, float4* temporal, hipStream_t st) {
+    const unsigned n = (unsigned)dp.N * (unsigned)dp.K;
+    launch(k_crf_tensor_edges, dim3((n + 255) / 256), dim3(256), 0, st, dp, yxrgb, members, offsets, indices, rows, edge, temporal);
+}
+
+void launch_crf_tensor_sweep(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
+                             const float4* temporal, const float* unaries, const float* compat, const float* q_in, float* q_out,
+                             float* msg, hipStream_t st) {
+    // the fewest equal class slices that fit kCrfTensorWaves wavefronts: 21 classes -> 11 waves of 2 classes (the last of 1)
+    const int per = (dp.C + kCrfTensorWaves - 1) / kCrfTensorWaves, waves = (dp.C + per - 1) / per;
+    const dim3 grid((unsigned)dp.N * (unsigned)((dp.K + kCrfTensorNodes - 1) / kCrfTensorNodes)), block(kCrfTensorNodes * waves);
+    if (dp.C <= kCrfTensorLdsClasses)
+        launch(k_crf_tensor_sweep<true>, grid, block, (unsigned)(2 * sizeof(float) * kCrfTensorNodes * dp.C), st,
+               dp, rows, indices, edge, temporal, unaries, compat, q_in, q_out, msg);
+    else
+        launch(k_crf_tensor_sweep<false>, grid, block, 0, st, dp, rows, indices, edge, temporal, unaries, compat, q_in, q_out, msg);
+}
+
+}  // namespace fslic

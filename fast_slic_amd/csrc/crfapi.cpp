@@ -1,0 +1,78 @@
+// crfapi.cpp -- the C ABI of SimpleCRF inference on device tensors (include/fslic_hip.h, fslic_hip_crf_tensor_*; kernels in
+// crf_tensor.hip).  No engine: the caller names the device and the stream and owns every buffer.  Every argument is checked before the
+// first HIP call; the call enqueues and returns.
+#include "engine_internal.h"
+#include "crf_tensor.h"
+#include "streamapi.h"
+
+using namespace fslic;
+
+namespace {
+
+int check_sizes(int N, int C, int K, long long nnz) {
+    if (N < 1 || C < 1 || K < 1) return fail(FSLIC_E_INVALID, "N, C and K must be positive");
+    if (nnz < 0 || nnz >= (1ll << 31)) return fail(FSLIC_E_INVALID, "nnz must be in [0, 2^31)");
+    if ((long long)N * C * K >= (1ll << 31) || (long long)N * K + 1 >= (1ll << 31))
+        return fail(FSLIC_E_INVALID, "N * C * K and N * K + 1 must be below 2^31");
+    return FSLIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslic_hip_crf_tensor_workspace_size(int N, int C, int K, long long nnz, size_t* bytes) {
+    if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const int rc = check_sizes(N, C, K, nnz);
+    if (rc) return rc;
+    *bytes = crf_tensor_workspace(N, C, K, nnz).bytes;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                   const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                   const int64_t* offsets, const int32_t* indices, long long nnz, const float* unaries, const float* q0,
+                                   float* q_out, void* workspace, size_t workspace_bytes) {
+    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
+    int rc = check_sizes(N, C, K, nnz);
+    if (rc) return rc;
+    if (temporal != 0 && temporal != 1) return fail(FSLIC_E_INVALID, "temporal must be 0 or 1");
+    if (max_iter < 0) return fail(FSLIC_E_INVALID, "max_iter must be >= 0");
+    if (!params || !compat || !yxrgb || !members || !offsets || !unaries || !q_out || !workspace || (!indices && nnz > 0))
+        return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(FSLIC_E_INVALID, "workspace must be 16-byte aligned");
+    const CrfTensorWorkspace ws = crf_tensor_workspace(N, C, K, nnz);
+    if (workspace_bytes < ws.bytes) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(ws.bytes) + " bytes needed");
+    DeviceScope scope;
+    if ((rc = scope.enter(device))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(workspace);
+    float* buf[2] = {q_out, reinterpret_cast<float*>(base + ws.q)};
+    // sweep `it` writes buf[(max_iter - 1 - it) & 1], so that the last one writes q_out; the starting q sits where the first sweep
+    // does not write: q0 itself when it is given (it is only read), buf[max_iter & 1] otherwise
+    const size_t cells = (size_t)N * C * K;
+    const float* q_in = q0;
+    if (!q0 || max_iter == 0) {
+        float* start = buf[max_iter & 1];
+        launch_crf_tensor_start(unaries, q0, start, cells, st);
+        q_in = start;
+    }
+    if (max_iter > 0) {
+        CrfTensorParams dp;
+        dp.N = N; dp.C = C; dp.K = K; dp.temporal = temporal; dp.nnz = nnz; dp.p = *params;
+        uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
+        float2* edge = reinterpret_cast<float2*>(base + ws.edge);
+        float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
+        float* msg = reinterpret_cast<float*>(base + ws.msg);
+        launch_crf_tensor_edges(dp, yxrgb, members, offsets, indices, rows, edge, tmp, st);
+        for (int it = 0; it < max_iter; it++) {
+            float* out = buf[(max_iter - 1 - it) & 1];
+            launch_crf_tensor_sweep(dp, rows, indices, edge, tmp, unaries, compat, q_in, out, msg, st);
+            q_in = out;
+        }
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
+}
+
+}  // extern "C"

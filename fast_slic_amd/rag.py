@@ -75,6 +75,23 @@ class SuperpixelGraph(object):
         offsets[1:] = torch.bincount(rows, minlength=K).cumsum(0)
         return offsets, (flat - rows * K).to(torch.int32)
 
+    def to_batch_csr(self):
+        """The neighbour lists of every frame as one CSR over (frame, node): (offsets int64 [N * K + 1], indices int32 [2 E]); the
+        neighbours of node k of frame n are indices[offsets[n * K + k]:offsets[n * K + k + 1]], node numbers inside the frame,
+        ascending and symmetric: the concatenation of to_csr(n) over the frames with the offsets shifted.  Unlike to_csr, which
+        slices by offsets[frame], it does not synchronise the host."""
+        K, N, E = self.num_components, self.num_frames, self.edge_index.shape[1]
+        dev = self.edge_index.device
+        # the frame of edge e: how many frames end at or before e
+        frame = torch.searchsorted(self.offsets[1:].contiguous(), torch.arange(E, dtype=torch.int64, device=dev), right=True)
+        a, b = self.edge_index[0], self.edge_index[1]
+        # key = (row over (frame, node)) * K + neighbour; unique, so any sort gives this order
+        flat = torch.cat([(frame * K + a) * K + b, (frame * K + b) * K + a]).sort().values
+        rows = torch.div(flat, K, rounding_mode="floor")
+        # offsets[r] = the entries of the rows before r (bincount would read its size back from the device)
+        offsets = torch.searchsorted(rows, torch.arange(N * K + 1, dtype=torch.int64, device=dev))
+        return offsets, (flat - rows * K).to(torch.int32)
+
 
 # ---- argument checks: all of them run before any device work ----
 def _check_image(image, shape):

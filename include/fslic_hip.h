@@ -381,6 +381,29 @@ int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int 
 int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capacity, void* workspace, size_t workspace_bytes,
                           int64_t* keys, int32_t* boundary, int64_t* contrast, long long max_edges);
 
+/* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
+ * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
+ * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
+ * restored, every argument checked before the first HIP call (FSLIC_E_INVALID).  Every pointer but `params` is device memory:
+ *   unaries, q0, q_out : float [N][C][K] (energies; q0 NULL: crf_expf(-unaries), what fslic_hip_crf_initialize sets; q0 is only read;
+ *                        q_out overlaps no input)             compat : float [C]
+ *   yxrgb   : float [N][5][K], the Cluster's y, x, r, g, b   members : int32 [N][K], the 32 bits of the Cluster's num_members
+ *   offsets : int64 [N * K + 1], indices : int32 [nnz] (NULL only with nnz == 0): one CSR over (frame, node); an index is a node
+ *             number inside its frame.  Rows may be empty, of any length, asymmetric, and hold duplicates and self-loops.  An index
+ *             outside [0, K) contributes nothing.  Row bounds are clamped into [0, nnz] and to end >= begin before use, so no offset
+ *             or index of any value leads to an access out of range (rows that overlap after that give unspecified energies).
+ * temporal 0: N independent frames.  temporal 1: N consecutive times of one window, node i of frame n linked to node i of n - 1 and
+ * n + 1 as in SimpleCRF.  max_iter Jacobi sweeps; the result is in q_out whatever max_iter is (0: the starting q).
+ * Limits: N * C * K, N * K + 1 and nnz below 2^31.  The workspace (16-byte aligned) holds 24 N K + 8 nnz + 4 N C K bytes, and
+ * 4 N C K more above 128 classes (each part rounded up to 16): row bounds, temporal and neighbour energies, the second q buffer,
+ * and the message plane of the sweeps whose classes do not fit LDS. */
+int fslic_hip_crf_tensor_workspace_size(int N, int C, int K, long long nnz, size_t* bytes);
+int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                   const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                   const int64_t* offsets, const int32_t* indices, long long nnz,
+                                   const float* unaries, const float* q0 /* NULL: expf(-unaries) */, float* q_out,
+                                   void* workspace, size_t workspace_bytes);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 
