@@ -61,6 +61,7 @@ EXPORTS = [
     "fslic_hip_rag_workspace_size", "fslic_hip_rag_accumulate", "fslic_hip_rag_compact",
     # SimpleCRF inference on torch tensors (fast_slic_amd/crf_torch.py)
     "fslic_hip_crf_tensor_workspace_size", "fslic_hip_crf_tensor_inference",
+    "fslic_hip_crf_tensor_grad_workspace_size", "fslic_hip_crf_tensor_inference_saved", "fslic_hip_crf_tensor_backward",
 ]
 
 _lib = None
@@ -217,6 +218,13 @@ def _declare_crf_tensor(lib):
     lib.fslic_hip_crf_tensor_inference.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
     for name in ("crf_tensor_workspace_size", "crf_tensor_inference"):
         getattr(lib, "fslic_hip_" + name).restype = i32
+    if hasattr(lib, "fslic_hip_crf_tensor_backward"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks the differentiable path)
+        lib.fslic_hip_crf_tensor_grad_workspace_size.argtypes = [i32, i32, i32, i64, i32, i32, C.POINTER(sz)]
+        lib.fslic_hip_crf_tensor_inference_saved.argtypes = lib.fslic_hip_crf_tensor_inference.argtypes
+        lib.fslic_hip_crf_tensor_backward.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                      vp, vp, vp, sz]
+        for name in ("crf_tensor_grad_workspace_size", "crf_tensor_inference_saved", "crf_tensor_backward"):
+            getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _raise(rc):

@@ -12,18 +12,24 @@ pool's counts are.  The result is a new float32 tensor of the unaries' shape, bi
 same inputs.  The work runs on torch's current stream of the unaries' device without host synchronisation; scratch memory comes from
 torch's caching allocator.  SimpleCRF (fast_slic_amd.crf) remains the reference-shaped surface.  This module imports torch; the
 package itself does not import it.
+
+The call is differentiable (csrc/crf_tensor_grad.hip): when gradients are enabled and `unaries`, `q0` or a tensor `compat` requires
+one, the same sweeps run with every iterate kept ((max_iter + 1) * 4 * N * C * K bytes), the result has the same bits, and backward()
+gives deterministic gradients for those three.  Nothing flows to `yxrgb`, `members`, the graph or `params`: learning the kernel
+weights is out of scope.
 """
 import ctypes as C
 import numbers
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _binding as B
 from .crf import _PARAMS, _Params
 from .pool import _check_device, _check_float_map, _stream
 from .rag import SuperpixelGraph
 
-__all__ = ["superpixel_crf", "DEFAULT_PARAMS"]
+__all__ = ["superpixel_crf", "transpose_batch_csr", "DEFAULT_PARAMS"]
 
 # a fresh SimpleCRF's (src/simple-crf.hpp:81-87); its compat is 1.0 for every class
 DEFAULT_PARAMS = dict(spatial_w=10.0, temporal_w=10.0, spatial_srgb=13.0, temporal_srgb=13.0, spatial_sxy=80.0, spatial_smooth_w=0.0,
@@ -106,6 +112,77 @@ def _check_compat(compat, Cn):
     return [float(v) for v in values]
 
 
+# ---- the differentiable path ----
+def transpose_batch_csr(offsets, indices, N, K):
+    """The transposed lists of one CSR over (frame, node) -> (t_offsets int64 [N * K + 1], t_entries int32 [nnz], t_rows int32 [nnz]):
+    the neighbour entries whose target is node j of frame n are t_entries[t_offsets[n * K + j]:t_offsets[n * K + j + 1]], in ascending
+    entry order, and t_rows names the row over (frame, node) of each.  An entry whose index is outside [0, K), or that lies behind the
+    last row, is sorted behind every target and belongs to none.  Plain torch without a host synchronisation, on any device; nothing
+    is validated (the backward kernels check every entry against the row bounds they clamp themselves)."""
+    n, nnz = N * K, indices.shape[0]
+    dev = indices.device
+    # the row of entry k: how many rows end at or before k (n: behind the last row)
+    row = torch.searchsorted(offsets[1:].contiguous(), torch.arange(nnz, dtype=torch.int64, device=dev), right=True)
+    j = indices.to(torch.int64)
+    key = (torch.div(row, K, rounding_mode="floor") * K + j).masked_fill((j < 0) | (j >= K) | (row >= n), n)
+    key, entry = torch.sort(key, stable=True)              # stable: ascending entry order inside one target
+    t_offsets = torch.searchsorted(key, torch.arange(n + 1, dtype=torch.int64, device=dev))
+    return t_offsets, entry.to(torch.int32), row[entry].to(torch.int32)
+
+
+def _workspace(lib, dev, N, Cn, K, nnz, backward, with_compat):
+    nbytes = C.c_size_t()
+    B._check(lib.fslic_hip_crf_tensor_grad_workspace_size(N, Cn, K, nnz, int(backward), int(with_compat), C.byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value
+
+
+class _SuperpixelCRF(torch.autograd.Function):
+    """The sweeps with every iterate kept, and their adjoint.  Tensors are contiguous and on one GPU; `start` is q0 or None."""
+
+    @staticmethod
+    def forward(ctx, un, start, comp, yx, mem, offsets, indices, N, max_iter, temporal, p):
+        lib, dev = _lib(), un.device
+        if not hasattr(lib, "fslic_hip_crf_tensor_backward"):
+            raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor backward; rebuild it")
+        Cn, K = (int(v) for v in un.shape[-2:])
+        nnz = int(indices.shape[0])
+        with torch.cuda.device(dev):
+            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, False, False)
+            q_all = torch.empty((max_iter + 1,) + tuple(un.shape), dtype=torch.float32, device=dev)
+            B._check(lib.fslic_hip_crf_tensor_inference_saved(dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, C.byref(p),
+                                                              comp.data_ptr(), yx.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
+                                                              indices.data_ptr() if nnz else None, nnz, un.data_ptr(),
+                                                              start.data_ptr() if start is not None else None, q_all.data_ptr(),
+                                                              ws.data_ptr(), nbytes))
+        ctx.save_for_backward(un, comp, yx, mem, offsets, indices, q_all)
+        ctx.call = (N, max_iter, temporal, p, start is not None)
+        return q_all[max_iter]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        un, comp, yx, mem, offsets, indices, q_all = ctx.saved_tensors
+        N, max_iter, temporal, p, has_q0 = ctx.call
+        lib, dev = _lib(), un.device
+        Cn, K = (int(v) for v in un.shape[-2:])
+        nnz = int(indices.shape[0])
+        with torch.cuda.device(dev):
+            g = g.contiguous()
+            t_offsets, t_entries, t_rows = transpose_batch_csr(offsets, indices, N, K)
+            du = torch.empty_like(un)
+            dq0 = torch.empty_like(un) if has_q0 else None
+            dcompat = torch.empty_like(comp) if ctx.needs_input_grad[2] else None
+            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, True, dcompat is not None)
+            B._check(lib.fslic_hip_crf_tensor_backward(dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, C.byref(p),
+                                                       comp.data_ptr(), yx.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
+                                                       indices.data_ptr() if nnz else None, nnz, t_offsets.data_ptr(),
+                                                       t_entries.data_ptr() if nnz else None, t_rows.data_ptr() if nnz else None,
+                                                       un.data_ptr(), q_all.data_ptr(), g.data_ptr(), du.data_ptr(),
+                                                       dq0.data_ptr() if has_q0 else None,
+                                                       dcompat.data_ptr() if dcompat is not None else None, ws.data_ptr(), nbytes))
+        return du, dq0, dcompat, None, None, None, None, None, None, None, None
+
+
 def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, compat=None, temporal=False, q0=None):
     """`max_iter` mean-field sweeps of SimpleCRF over `unaries` ([C, K] or [N, C, K] float32 energies on a ROCm GPU) -> q, a new
     tensor of the same shape.
@@ -120,7 +197,13 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     temporal=False: the N frames are independent.  temporal=True: they are consecutive times of one window, node i of frame n
     linked to node i of n - 1 and n + 1, exactly as in SimpleCRF.
     q0: the starting q, float32 of the unaries' shape (never written); None: crf_expf(-unaries), which is SimpleCRF.initialize().
-    max_iter=0 returns the starting q."""
+    max_iter=0 returns the starting q.
+
+    Differentiable with respect to `unaries`, `q0` and a tensor `compat`: when gradients are enabled and one of them requires one,
+    q is part of the autograd graph (the same bits; every iterate is kept for the backward, (max_iter + 1) * 4 * N * C * K bytes) and
+    its backward is deterministic and once differentiable; q is then a view of the kept iterates, which autograd protects from
+    in-place changes.  `yxrgb`, `members`, the graph and `params` get no gradient: learning the
+    kernel weights (gradients with respect to params or the edge energies) is out of scope.  Otherwise q has no grad_fn."""
     _check_float_map(unaries, (2, 3), "unaries", "[C, K] or [N, C, K]")
     batched = unaries.dim() == 3
     N = unaries.shape[0] if batched else 1
@@ -164,6 +247,8 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
             compat = torch.tensor(compat, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
         un, yx, mem, comp = unaries.contiguous(), yxrgb.contiguous(), members.contiguous(), compat.contiguous()
         start = q0.contiguous() if q0 is not None else None
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unaries, q0, compat)):
+            return _SuperpixelCRF.apply(un, start, comp, yx.detach(), mem, offsets, indices, N, max_iter, temporal, p)
         nbytes = C.c_size_t()
         B._check(lib.fslic_hip_crf_tensor_workspace_size(N, Cn, K, nnz, C.byref(nbytes)))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)

@@ -1,8 +1,9 @@
 // crfapi.cpp -- the C ABI of SimpleCRF inference on device tensors (include/fslic_hip.h, fslic_hip_crf_tensor_*; kernels in
-// crf_tensor.hip).  No engine: the caller names the device and the stream and owns every buffer.  Every argument is checked before the
+// crf_tensor.hip, crf_tensor_grad.hip).  No engine: the caller names the device and the stream and owns every buffer.  Every argument is checked before the
 // first HIP call; the call enqueues and returns.
 #include "engine_internal.h"
 #include "crf_tensor.h"
+#include "crf_tensor_grad.h"
 #include "streamapi.h"
 
 using namespace fslic;
@@ -14,6 +15,22 @@ int check_sizes(int N, int C, int K, long long nnz) {
     if (nnz < 0 || nnz >= (1ll << 31)) return fail(FSLIC_E_INVALID, "nnz must be in [0, 2^31)");
     if ((long long)N * C * K >= (1ll << 31) || (long long)N * K + 1 >= (1ll << 31))
         return fail(FSLIC_E_INVALID, "N * C * K and N * K + 1 must be below 2^31");
+    return FSLIC_OK;
+}
+
+// What fslic_hip_crf_tensor_inference checks ahead of its pointers, for the entries of the differentiable path.
+int check_call(int device, int N, int C, int K, long long nnz, int temporal, int max_iter) {
+    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
+    const int rc = check_sizes(N, C, K, nnz);
+    if (rc) return rc;
+    if (temporal != 0 && temporal != 1) return fail(FSLIC_E_INVALID, "temporal must be 0 or 1");
+    if (max_iter < 0) return fail(FSLIC_E_INVALID, "max_iter must be >= 0");
+    return FSLIC_OK;
+}
+
+int check_workspace(const void* workspace, size_t workspace_bytes, size_t needed) {
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(FSLIC_E_INVALID, "workspace must be 16-byte aligned");
+    if (workspace_bytes < needed) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(needed) + " bytes needed");
     return FSLIC_OK;
 }
 
@@ -71,6 +88,94 @@ int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K
             q_in = out;
         }
     }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
+}
+
+int fslic_hip_crf_tensor_grad_workspace_size(int N, int C, int K, long long nnz, int backward, int with_compat, size_t* bytes) {
+    if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const int rc = check_sizes(N, C, K, nnz);
+    if (rc) return rc;
+    if ((backward != 0 && backward != 1) || (with_compat != 0 && with_compat != 1))
+        return fail(FSLIC_E_INVALID, "backward and with_compat must be 0 or 1");
+    *bytes = crf_tensor_grad_workspace(N, C, K, nnz, backward != 0, with_compat != 0).bytes;
+    return FSLIC_OK;
+}
+
+int fslic_hip_crf_tensor_inference_saved(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                         const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                         const int64_t* offsets, const int32_t* indices, long long nnz, const float* unaries,
+                                         const float* q0, float* q_all, void* workspace, size_t workspace_bytes) {
+    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
+    if (rc) return rc;
+    if (!params || !compat || !yxrgb || !members || !offsets || !unaries || !q_all || !workspace || (!indices && nnz > 0))
+        return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, false, false);
+    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
+    DeviceScope scope;
+    if ((rc = scope.enter(device))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(workspace);
+    const size_t cells = (size_t)N * C * K;
+    // plane 0 is the starting q, plane it + 1 what sweep `it` writes: the ping-pong of fslic_hip_crf_tensor_inference unrolled
+    launch_crf_tensor_start(unaries, q0, q_all, cells, st);
+    if (max_iter > 0) {
+        CrfTensorParams dp;
+        dp.N = N; dp.C = C; dp.K = K; dp.temporal = temporal; dp.nnz = nnz; dp.p = *params;
+        uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
+        float2* edge = reinterpret_cast<float2*>(base + ws.edge);
+        float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
+        float* msg = reinterpret_cast<float*>(base + ws.msg);
+        launch_crf_tensor_edges(dp, yxrgb, members, offsets, indices, rows, edge, tmp, st);
+        for (int it = 0; it < max_iter; it++)
+            launch_crf_tensor_sweep(dp, rows, indices, edge, tmp, unaries, compat, q_all + (size_t)it * cells,
+                                    q_all + (size_t)(it + 1) * cells, msg, st);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
+}
+
+int fslic_hip_crf_tensor_backward(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                  const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                  const int64_t* offsets, const int32_t* indices, long long nnz, const int64_t* t_offsets,
+                                  const int32_t* t_entries, const int32_t* t_rows, const float* unaries, const float* q_all,
+                                  const float* grad_q, float* grad_unaries, float* grad_q0, float* grad_compat, void* workspace,
+                                  size_t workspace_bytes) {
+    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
+    if (rc) return rc;
+    if (!params || !compat || !yxrgb || !members || !offsets || !t_offsets || !unaries || !q_all || !grad_q || !grad_unaries ||
+        !workspace || ((!indices || !t_entries || !t_rows) && nnz > 0))
+        return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, true, grad_compat != nullptr);
+    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
+    DeviceScope scope;
+    if ((rc = scope.enter(device))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* base = reinterpret_cast<char*>(workspace);
+    const size_t cells = (size_t)N * C * K, blocks = crf_tensor_grad_blocks(N, K);
+    CrfTensorParams dp;
+    dp.N = N; dp.C = C; dp.K = K; dp.temporal = temporal; dp.nnz = nnz; dp.p = *params;
+    uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
+    float2* edge = reinterpret_cast<float2*>(base + ws.edge);
+    float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
+    float* msg = reinterpret_cast<float*>(base + ws.msg);
+    float* dm[2] = {reinterpret_cast<float*>(base + ws.dm), reinterpret_cast<float*>(base + ws.dm) + cells};
+    float* x = reinterpret_cast<float*>(base + ws.x);
+    float* slots = grad_compat ? reinterpret_cast<float*>(base + ws.slots) : nullptr;
+    const CrfTensorTransposed tr = {t_offsets, t_entries, t_rows};
+    if (max_iter > 0) {
+        // the energies again rather than the forward's workspace: nothing but the iterates stays alive between the two calls
+        launch_crf_tensor_edges(dp, yxrgb, members, offsets, indices, rows, edge, tmp, st);
+        for (int it = max_iter - 1; it >= 0; it--) {
+            const bool first = it == max_iter - 1;
+            launch_crf_tensor_sweep_bwd(dp, rows, indices, edge, tmp, tr, unaries, compat, q_all + (size_t)it * cells,
+                                        q_all + (size_t)(it + 1) * cells, first ? grad_q : nullptr, dm[(it + 1) & 1], dm[it & 1],
+                                        grad_unaries, slots, msg, x, first, st);
+        }
+    }
+    launch_crf_tensor_grad_close(dp, rows, edge, tmp, tr, q_all, max_iter > 0 ? nullptr : grad_q, dm[0], grad_unaries, grad_q0,
+                                 max_iter == 0, st);
+    if (grad_compat) launch_crf_tensor_grad_compat(slots, max_iter > 0 ? blocks : 0, C, grad_compat, st);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
 }

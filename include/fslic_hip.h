@@ -404,6 +404,37 @@ int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K
                                    const float* unaries, const float* q0 /* NULL: expf(-unaries) */, float* q_out,
                                    void* workspace, size_t workspace_bytes);
 
+/* ---- The backward of that inference (kernels in csrc/crf_tensor_grad.hip; Python: the autograd path of superpixel_crf) ----
+ * fslic_hip_crf_tensor_inference_saved is fslic_hip_crf_tensor_inference with every iterate kept: q_all is float
+ * [max_iter + 1][N][C][K], plane 0 the starting q, plane t + 1 what sweep t writes (the same kernels: the last plane is bit-equal to
+ * q_out of the other entry).  fslic_hip_crf_tensor_backward takes that q_all, the same inputs and grad_q [N][C][K], the gradient of a
+ * scalar with respect to the last plane, and writes the gradient with respect to
+ *   unaries     -> grad_unaries [N][C][K] (always),
+ *   q0          -> grad_q0 [N][C][K]; NULL says that the forward had q0 == NULL, its start crf_expf(-unaries) then adds to grad_unaries,
+ *   compat      -> grad_compat [C], or NULL: that pass is skipped.
+ * Nothing flows to yxrgb, members, the graph or params.  One launch per sweep, last sweep first, gathers over the TRANSPOSED lists:
+ * t_offsets int64 [N * K + 1] over (frame, target node), and per transposed entry the neighbour entry t_entries int32 [nnz] and its
+ * row t_rows int32 [nnz] over (frame, node), in ascending entry order inside one target (both NULL only with nnz == 0).  No float
+ * atomics: every output cell has one owner and every sum a fixed order, so two calls give the same bits.  No transposed list of any
+ * content leads to an access out of range: bounds are clamped as a row's are, and an entry counts only when its row is a node of the
+ * target's frame, its number lies inside that row's clamped bounds, and its index is inside [0, K); lists that are not the transpose
+ * of the CSR give unspecified gradients.  Output buffers overlap no input and each other not.
+ * The workspace (16-byte aligned parts): 24 N K + 8 nnz bytes of row bounds and energies, and above 128 classes 4 N C K of messages;
+ * with backward == 1 also 8 N C K of message gradients, above 128 classes 4 N C K more, and with with_compat == 1 (grad_compat given)
+ * 4 C N ceil(K / 64) bytes of per-block sums. */
+int fslic_hip_crf_tensor_grad_workspace_size(int N, int C, int K, long long nnz, int backward, int with_compat, size_t* bytes);
+int fslic_hip_crf_tensor_inference_saved(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                         const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                         const int64_t* offsets, const int32_t* indices, long long nnz,
+                                         const float* unaries, const float* q0 /* NULL: expf(-unaries) */, float* q_all,
+                                         void* workspace, size_t workspace_bytes);
+int fslic_hip_crf_tensor_backward(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                  const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
+                                  const int64_t* offsets, const int32_t* indices, long long nnz,
+                                  const int64_t* t_offsets, const int32_t* t_entries, const int32_t* t_rows,
+                                  const float* unaries, const float* q_all, const float* grad_q,
+                                  float* grad_unaries, float* grad_q0, float* grad_compat, void* workspace, size_t workspace_bytes);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 

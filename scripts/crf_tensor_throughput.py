@@ -2,7 +2,9 @@
 8 independent 1280x720 frames at K = 1600, C = 21: device time between two events around one call (1 start + 1 edge launch + 10
 sweeps, the Python side included as far as it delays the stream), median of `--reps` calls after a warm-up, next to the host wall time
 of SimpleCRF.inference(10) on the same clusters, neighbour lists and unaries.  Neighbour lists are real: get_connectivity on
-1280x720 synthetic frames per K.
+1280x720 synthetic frames per K.  Beside the forward: the same call with the unaries and a compat tensor requiring a gradient (the
+saved-iterates forward) and the backward of q.sum() through it (the transposition of the lists, the edge pass again, 10 adjoint
+sweeps, the closing gather and the compat sum), each between two events.
     python scripts/crf_tensor_throughput.py [--reps 20]"""
 import argparse
 import json
@@ -91,8 +93,26 @@ def main():
             e1.synchronize()
             ts20.append(e0.elapsed_time(e1))
         sweep_us = (float(np.median(ts20)) - ms) * 100
+        # the differentiable call: the forward that keeps its iterates, and the backward
+        un_g, comp_g = un.clone().requires_grad_(True), torch.ones(Cn, device=dev).requires_grad_(True)
+        g_out = torch.ones_like(un)
+        fwd, bwd = [], []
+        for rep in range(3 + a.reps):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            un_g.grad = comp_g.grad = None
+            e0.record()
+            qg = superpixel_crf(un_g, graph, yxrgb, members, max_iter=10, compat=comp_g, temporal=temporal)
+            e1.record()
+            qg.backward(g_out)
+            e2.record()
+            e2.synchronize()
+            if rep >= 3:
+                fwd.append(e0.elapsed_time(e1))
+                bwd.append(e1.elapsed_time(e2))
         print(json.dumps(dict(K=K, classes=Cn, frames=N, temporal=temporal, entries=int(off[-1]), tensor_ms_per_call10=round(ms, 4),
-                              tensor_us_per_sweep=round(sweep_us, 2), simple_crf_ms_per_inference10=round(simple_ms, 4),
+                              tensor_us_per_sweep=round(sweep_us, 2),
+                              grad_forward_ms_per_call10=round(float(np.median(fwd)), 4),
+                              backward_ms_per_call10=round(float(np.median(bwd)), 4), simple_crf_ms_per_inference10=round(simple_ms, 4),
                               ratio=round(simple_ms / ms, 2))))
 
 
