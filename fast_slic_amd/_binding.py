@@ -44,7 +44,7 @@ EXPORTS = [
     "fslic_hip_last_device_times", "fslic_hip_set_launch_timing", "fslic_hip_last_assign_loop", "fslic_hip_last_group_frames", "fslic_hip_last_path", "fslic_hip_last_launch_mode", "fslic_hip_group_done", "fslic_hip_last_error", "fslic_hip_version",
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
-    "fslic_hip_separate_pass_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
+    "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
     # SimpleCRF (fast_slic_amd/crf.py)
     "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
     "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
@@ -128,6 +128,8 @@ def load_library():
         lib.fslic_hip_pipeline_batching.argtypes = [vp, i32]
         lib.fslic_hip_last_host_topk_frames.argtypes = [vp, i32]
         lib.fslic_hip_separate_pass_redos.argtypes = [vp, i32]
+        if hasattr(lib, "fslic_hip_uncovered_redos"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it: it has no label-free passes)
+            lib.fslic_hip_uncovered_redos.argtypes = [vp, i32]
         if hasattr(lib, "fslic_hip_copy_bandwidth"):      # (an A/B build of an earlier round, FSLIC_LIB, may lack it)
             lib.fslic_hip_copy_bandwidth.argtypes = [vp, C.c_size_t, i32, C.POINTER(C.c_double)]
         lib.fslic_hip_group_done.argtypes = [vp, i32]
@@ -385,6 +387,15 @@ class Engine(object):
     def separate_pass_redos(self):
         """Frames (all slots, since the engine was created) redone with the separate cluster pass because of a stale pixel."""
         return sum(int(load_library().fslic_hip_separate_pass_redos(self._h, s)) for s in range(self.n_slots))
+
+    def uncovered_redos(self, slot=None):
+        """Frames (one slot, or all of them; since the engine was created) redone with storing assign passes because a visited pixel
+        lay outside every cluster window while the group's subsampled passes ran label-free (include/fslic_hip.h)."""
+        lib = load_library()
+        if not hasattr(lib, "fslic_hip_uncovered_redos"):      # (FSLIC_LIB: a build without label-free passes never redoes for this reason)
+            return 0
+        slots = range(self.n_slots) if slot is None else [int(slot)]
+        return sum(int(lib.fslic_hip_uncovered_redos(self._h, s)) for s in slots)
 
     def copy_bandwidth(self, nbytes=1 << 30, reps=5):
         """Measured HBM rate of this GPU in GB/s: bytes read + written per second of a plain streaming copy of `nbytes`."""

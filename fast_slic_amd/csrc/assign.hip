@@ -352,7 +352,7 @@ typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 // No global atomic on the common path: device-scope atomics cost 21 of the 39 us of the per-wavefront-flush
 // version of this pass (8 x 720p frames).  Pixels that no window covers keep their label and reach the sums through
 // global atomics (rare).
-// Algorithmic traffic: 4 B read + 2 B written per visited pixel.
+// Algorithmic traffic: 4 B read + 2 B written per visited pixel; the fused passes of a label-free group (NOLAB below) write nothing.
 // =============================================================================================
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 // (Experiment builds -- make VAR=<name> DEFS=-DFSLIC_EXP=<bits>, kernels.h -- carry A/B forms of this kernel while they are being
@@ -554,10 +554,19 @@ static inline dim3 blk_grid(dim3 g) { return dim3(g.x, g.z, g.y); }
 // scatter over the active clusters (src/context.cpp:218); unless every cluster is active the fused sums take only the pixels of active
 // (2S x 2S) cells (src/context.cpp:304-343: the row-by-row epilogue with the cell test), and the block's sums leave through global
 // atomics into FrameDev::sums, where k_preempt_update reads them (no partial-sum entries, no slot geometry).
-template <int R, bool FUSE, int STRIDE, bool VT, bool FBIN = false, bool PRE = false>
+// NOLAB: the label-free form of the fused pass (a label-free group, FrameDev::fv_mod; DESIGN.md "Deferred labels").  The sums of update()
+// work on ranks and the full pass that closes the group overwrites every pixel some window covers, so the labels of a subsampled pass are
+// needed only where a LATER pass finds a pixel no window covers.  This form stores no label and reads none: no cluster-number table, no
+// look-ups and no stores in the fast epilogue; a visited pixel no window covers raises kFlagUncoveredPixel (the host redoes the frame
+// with storing passes) and stays out of the sums.
+template <int R, bool FUSE, int STRIDE, bool VT, bool FBIN = false, bool PRE = false, bool NOLAB = false>
 static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, int Hv, const BlkMap& bm) {
     static_assert(!FBIN || FUSE, "the cluster pass rides on the fused centroid sums");
     static_assert(!PRE || (FUSE && !FBIN), "preemptive mode: the fused pass with its own flush");
+    static_assert(!NOLAB || (!FBIN && !PRE), "label-free groups: the separate cluster pass only");
+    // The full pass that closes a label-free group (NOLAB without FUSE) stores as ever; no earlier pass has written the plane, so every
+    // pixel no window covers gets its 0xFFFF here (the host states every row a first visit, FrameDev::fv_mod) and raises the flag too.
+    constexpr bool NOSTORE = NOLAB && FUSE, CLOSING = NOLAB && !FUSE;
     const uint32_t bxi = blockIdx.x, byi = blockIdx.z, bzi = blockIdx.y;      // (tile column, tile row, frame): see blk_grid
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];   // spatial table (u16), whole KB (LDS-DMA lands 1 KB per wavefront instruction); 16-byte aligned: the row-vector reads are ds_read_b128
     __shared__ __attribute__((aligned(16))) uint4 s_raw[kWavesPerBlock][64];       // every wavefront's kept records {yx, lab, tag, -}
@@ -571,7 +580,7 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
     // met on one bank at different addresses, and the sixteen look-ups of a wavefront cost 120 LDS cycles, 90 of them bank conflicts,
     // and 8 % of the fused launch's duration: scripts/gpu_knock.sh, profiles/r04_assign_experiments.txt.  The 64 entries are one
     // pass over the banks: equal ranks read one address, different ranks different banks.)
-    __shared__ __attribute__((aligned(16))) uint16_t s_klab[64];
+    __shared__ __attribute__((aligned(16))) uint16_t s_klab[NOSTORE ? 2 : 64];      // (label-free form: never touched)
     // centroid accumulators: per (candidate, copy) two 64-bit words of three 20-bit-spaced fields each,
     //   A = sum L | sum a << 20 | sum b << 40        B = sum (x - x0) | sum (y - y0) << 20 | count << 40
     __shared__ __attribute__((aligned(16))) unsigned long long s_acc[FUSE ? 64 * kBlkCopies * 2 : 2];
@@ -734,11 +743,12 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
             // The plane is reset lazily (FrameDev::fv_mod): rows this launch is the first to look at hold whatever the arena's previous
             // geometry left there.  The frame is redone, but a later pass of THIS run whose list fits again would take that for the
             // pixels' old labels (sums of a cluster number beyond K), and the connectivity pass runs before the host sees the flag.
-            if constexpr (!FBIN) {
+            // (label-free form: nothing to store -- no pass of the group reads the plane before the full pass has written all of it)
+            if constexpr (!FBIN && !NOSTORE) {
                 if (okx) {
                     uint16_t* rowp = f.labels + (size_t)yw_lo * W + (uint32_t)x;
                     for (int r = 0; r < nrows; ++r, rowp += (size_t)STRIDE * W)
-                        if (FUSE ? f.fv_mod == 1 : f.first_visit(yw_lo + r * STRIDE)) st_stream(rowp, (uint16_t)0xFFFFu);
+                        if (CLOSING || (FUSE ? f.fv_mod == 1 : f.first_visit(yw_lo + r * STRIDE))) st_stream(rowp, (uint16_t)0xFFFFu);
                 }
             }
             return;
@@ -762,7 +772,7 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
         const uint4 pr = *reinterpret_cast<const uint4*>(s_part[lane]);
         rank_j = pr.x + pr.y + pr.z + pr.w;
     }
-    if (lane < bn) s_klab[(int)rank_j] = (uint16_t)(mine.z & 0xFFFFu);
+    if constexpr (!NOSTORE) { if (lane < bn) s_klab[(int)rank_j] = (uint16_t)(mine.z & 0xFFFFu); }
     uint32_t fin_nx = 0, fin_ny = 0, fin_b0 = 0; // FBIN, wavefront 0, lane j: blocks that deliver sums of candidate j (0: not this block), the first of them (row << 16 | column)
     if (PRE && wave == 0) {
         if (lane < bn) s_entry[rank_j] = mine.z & 0xFFFFu;
@@ -1082,19 +1092,21 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
             ASG_MARK("labels");
             epilogue_done = true;
             if (okx) {
-                uint32_t kk[R];
-                const char* const ktab = reinterpret_cast<const char*>(s_klab);
+                if constexpr (!NOSTORE) {      // (label-free form: from the argmin straight to the sums)
+                    uint32_t kk[R];
+                    const char* const ktab = reinterpret_cast<const char*>(s_klab);
 #pragma unroll
-                for (int q = 0; q < R / 2; ++q) {
-                    const uint32_t b = __builtin_bit_cast(uint32_t, best[q]) & 0x003F003Fu;       // (the fused sums below need the ranks alone as well)
-                    kk[2 * q] = *reinterpret_cast<const uint16_t*>(ktab + ((b & 0xFFu) << 1));
-                    kk[2 * q + 1] = *reinterpret_cast<const uint16_t*>(ktab + (((b >> 16) & 0xFFu) << 1));
+                    for (int q = 0; q < R / 2; ++q) {
+                        const uint32_t b = __builtin_bit_cast(uint32_t, best[q]) & 0x003F003Fu;       // (the fused sums below need the ranks alone as well)
+                        kk[2 * q] = *reinterpret_cast<const uint16_t*>(ktab + ((b & 0xFFu) << 1));
+                        kk[2 * q + 1] = *reinterpret_cast<const uint16_t*>(ktab + (((b >> 16) & 0xFFu) << 1));
+                    }
+                    const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(f.labels, 0, (int)((uint32_t)f.N * 2u), kRawBuffer);
+                    const uint32_t so0 = (uint32_t)yw_lo * (uint32_t)W * 2u, pitch2 = (uint32_t)(STRIDE * W) * 2u;
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        __builtin_amdgcn_raw_buffer_store_b16((uint16_t)kk[r], ws, (int)((uint32_t)x * 2u), (int)(so0 + (uint32_t)r * pitch2), kAuxSc1);
                 }
-                const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc(f.labels, 0, (int)((uint32_t)f.N * 2u), kRawBuffer);
-                const uint32_t so0 = (uint32_t)yw_lo * (uint32_t)W * 2u, pitch2 = (uint32_t)(STRIDE * W) * 2u;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)kk[r], ws, (int)((uint32_t)x * 2u), (int)(so0 + (uint32_t)r * pitch2), kAuxSc1);
                 ASG_STAMP(5, wave == 0);
                 ASG_MARK("sums");
                 if (FUSE) {
@@ -1167,19 +1179,30 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
         uint32_t slot[R];
         uint16_t* rowp = f.labels + (size_t)yw_lo * W;
         const uint32_t xo = (uint32_t)x;
+        [[maybe_unused]] bool uncovered = false;      // label-free form: this lane met a visited pixel no window covers
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const bool ok = okx && r < nrows;
             const uint32_t key = (r & 1) ? (uint32_t)best[r / 2].y : (uint32_t)best[r / 2].x;
             const bool found = key != 0xFFFFu;
             slot[r] = kNoSlot;
+            if constexpr (NOSTORE) {
+                // the plane is neither read nor written: where a storing pass would have needed it (the pixel's label of an earlier
+                // pass, or the 0xFFFF a later pass may meet) the frame is flagged and redone, so the pixel simply stays out of the sums
+                if (ok && found) slot[r] = key & 63u;
+                uncovered = uncovered || (ok && !found);
+                continue;
+            }
             if (ok && found) st_stream(rowp + xo, s_klab[key & 63u]);
             // lazy reset of the plane (FrameDev::fv_mod): the first pass to look at a row stores the 0xFFFF of pixels no window covers
             // (a fused pass is a subsampled pass: ALL of its rows are first visits or none is, one scalar test; only the full pass
             // has to look at the row's residue)
             // (the launches that carry the cluster pass -- FBIN -- belong to groups whose plane the LAB kernel still fills, group.cpp: compiled out there)
-            const bool unlabelled = !FBIN && ok && !found && (FUSE ? f.fv_mod == 1 : f.first_visit(yw_lo + r * STRIDE));
-            if (unlabelled) st_stream(rowp + xo, (uint16_t)0xFFFFu);
+            const bool unlabelled = !FBIN && ok && !found && (CLOSING || (FUSE ? f.fv_mod == 1 : f.first_visit(yw_lo + r * STRIDE)));
+            if (unlabelled) {
+                st_stream(rowp + xo, (uint16_t)0xFFFFu);
+                if constexpr (CLOSING) atomicOr(f.err_flag, kFlagUncoveredPixel);      // (rare, and such a frame is computed again: no care taken to save atomics)
+            }
             bool summed = FUSE && ok && !unlabelled;
             if constexpr (PRE) summed = summed && in_update(f, yw_lo + r * STRIDE, x);
             if (summed) {
@@ -1195,6 +1218,9 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
                 }
             }
             rowp += (size_t)STRIDE * W;
+        }
+        if constexpr (NOSTORE) {
+            if (ballot(uncovered) != 0ull && lane == 0) atomicOr(f.err_flag, kFlagUncoveredPixel);      // (one atomic per wavefront, nothing waits for it)
         }
         ASG_STAMP(5, wave == 0);
         if (FUSE) {
@@ -1270,17 +1296,17 @@ static __device__ __forceinline__ void assign_blk2_body(FrameDev& f, int rem, in
 // The kernels proper.  Register budgets are part of the design (amdgpu_waves_per_eu): the bodies need 24 - 48 VGPRs with 8 rows per
 // wavefront (8 wavefronts per SIMD), 38 - 40 for the 16-row full pass (8) and 74 for the 16-row fused pass (6); left to itself the
 // compiler schedules them into more (at 3840x2160 that cost 17 % with the first form: 51 vs 60 us per fused launch of eight frames).
-template <int R, bool FUSE, int STRIDE, bool VT>
+template <int R, bool FUSE, int STRIDE, bool VT, bool NOLAB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(7, 8))) void k_assign_blk2(FrameDev f, int rem, int Hv, BlkMap bm) {
-    assign_blk2_body<R, FUSE, STRIDE, VT>(f, rem, Hv, bm);
+    assign_blk2_body<R, FUSE, STRIDE, VT, false, false, NOLAB>(f, rem, Hv, bm);
 }
-template <int R, bool FUSE, int STRIDE, bool VT>
+template <int R, bool FUSE, int STRIDE, bool VT, bool NOLAB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void k_assign_blk2_w8(FrameDev f, int rem, int Hv, BlkMap bm) {
-    assign_blk2_body<R, FUSE, STRIDE, VT>(f, rem, Hv, bm);
+    assign_blk2_body<R, FUSE, STRIDE, VT, false, false, NOLAB>(f, rem, Hv, bm);
 }
-template <int R, bool FUSE, int STRIDE, bool VT>
+template <int R, bool FUSE, int STRIDE, bool VT, bool NOLAB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(6, 8))) void k_assign_blk2_w6(FrameDev f, int rem, int Hv, BlkMap bm) {
-    assign_blk2_body<R, FUSE, STRIDE, VT>(f, rem, Hv, bm);
+    assign_blk2_body<R, FUSE, STRIDE, VT, false, false, NOLAB>(f, rem, Hv, bm);
 }
 
 template <int R, int STRIDE, bool VT>
@@ -1303,7 +1329,7 @@ static FrameDev with_subsampled_table(FrameDev f) {
     return f;
 }
 
-template <int R, bool FUSE, int STRIDE>
+template <int R, bool FUSE, int STRIDE, bool NOLAB = false>
 static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
     FrameDev f = FUSE ? with_subsampled_table(f_) : f_;
     if (FUSE && R == 16 && !f.tab_vmode) { f.tab = f.tabs16; f.tab_words = f.tabs16_words; f.tab_dyoff = f.tabs16_dyoff; f.tab_nrpad = f.tabs16_nrpad; }
@@ -1313,16 +1339,16 @@ static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;       // whole KB: what the LDS-DMA pieces fill
     if constexpr (R == 32) {
         static_assert(!FUSE, "32 rows per wavefront: full pass only");
-        launch((k_assign_blk2_w6<R, FUSE, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        launch((k_assign_blk2_w6<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     } else if constexpr (R == 16 && !FUSE) {
-        if (f.tab_vmode) launch((k_assign_blk2_w8<R, FUSE, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2_w8<R, FUSE, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        if (f.tab_vmode) launch((k_assign_blk2_w8<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        else launch((k_assign_blk2_w8<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     } else if constexpr (R == 16 && FUSE) {
-        if (f.tab_vmode) launch((k_assign_blk2_w6<R, FUSE, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2_w6<R, FUSE, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        if (f.tab_vmode) launch((k_assign_blk2_w6<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        else launch((k_assign_blk2_w6<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     } else {
-        if (f.tab_vmode) launch((k_assign_blk2<R, FUSE, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2<R, FUSE, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        if (f.tab_vmode) launch((k_assign_blk2<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+        else launch((k_assign_blk2<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     }
 }
 
@@ -1410,7 +1436,21 @@ static void launch_assign_r(const FrameDev& f, int nframes, int rem, int stride,
     }
 }
 
-PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf) {
+// the fused pass of the block kernel, R rows per wavefront, storing or label-free
+template <int R>
+static void launch_assign_fused_t(const FrameDev& f, int nframes, int rem, int stride, int Hv, bool label_free, hipStream_t st) {
+    if (label_free) {
+        if (stride == 1) launch_assign_blk_t<R, true, 1, true>(f, nframes, rem, Hv, st);
+        else if (stride == 2) launch_assign_blk_t<R, true, 2, true>(f, nframes, rem, Hv, st);
+        else launch_assign_blk_t<R, true, 3, true>(f, nframes, rem, Hv, st);
+    } else {
+        if (stride == 1) launch_assign_blk_t<R, true, 1>(f, nframes, rem, Hv, st);
+        else if (stride == 2) launch_assign_blk_t<R, true, 2>(f, nframes, rem, Hv, st);
+        else launch_assign_blk_t<R, true, 3>(f, nframes, rem, Hv, st);
+    }
+}
+
+PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf, bool label_free) {
     const FrameDev f = rotated(f_, buf, sbuf, obuf);
     const int Hv = visited_rows(f.H, rem, stride);
     PassGeom pg;
@@ -1419,6 +1459,12 @@ PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int
     if (blk_kernel_applies(f, stride)) {       // block-level packed kernel
         if (!fuse_update && stride == 1) {
             const int rpw = assign_rows_per_wave(f, nframes, Hv, false);
+            if (label_free) {      // the full pass that closes a label-free group
+                if (rpw == 32) launch_assign_blk_t<32, false, 1, true>(f, nframes, rem, Hv, st);
+                else if (rpw == 16) launch_assign_blk_t<16, false, 1, true>(f, nframes, rem, Hv, st);
+                else launch_assign_blk_t<8, false, 1, true>(f, nframes, rem, Hv, st);
+                return pg;
+            }
             if (rpw == 32) launch_assign_blk_t<32, false, 1>(f, nframes, rem, Hv, st);
             else if (rpw == 16) launch_assign_blk_t<16, false, 1>(f, nframes, rem, Hv, st);
             else launch_assign_blk_t<8, false, 1>(f, nframes, rem, Hv, st);
@@ -1435,14 +1481,10 @@ PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int
             const bool r16 = (f.tab_vmode && fblocks8 > 3072) || (!f.tab_vmode && f.tabs16_words > 0 && fblocks8 > 2048);
             if (r16) {
                 pg.BH = kWavesPerBlock * 16;
-                if (stride == 1) launch_assign_blk_t<16, true, 1>(f, nframes, rem, Hv, st);
-                else if (stride == 2) launch_assign_blk_t<16, true, 2>(f, nframes, rem, Hv, st);
-                else launch_assign_blk_t<16, true, 3>(f, nframes, rem, Hv, st);
+                launch_assign_fused_t<16>(f, nframes, rem, stride, Hv, label_free, st);
                 return pg;
             }
-            if (stride == 1) launch_assign_blk_t<8, true, 1>(f, nframes, rem, Hv, st);
-            else if (stride == 2) launch_assign_blk_t<8, true, 2>(f, nframes, rem, Hv, st);
-            else launch_assign_blk_t<8, true, 3>(f, nframes, rem, Hv, st);
+            launch_assign_fused_t<8>(f, nframes, rem, stride, Hv, label_free, st);
             return pg;
         }
     }

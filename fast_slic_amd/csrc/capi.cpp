@@ -298,6 +298,11 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot) {
     return __atomic_load_n(&e->slots[slot].n_separate_redo, __ATOMIC_RELAXED);
 }
 
+int fslic_hip_uncovered_redos(fslic_engine* e, int slot) {
+    if (!e || slot < 0 || slot >= (int)e->slots.size()) return -1;
+    return __atomic_load_n(&e->slots[slot].n_uncovered_redo, __ATOMIC_RELAXED);
+}
+
 // ---- SimpleCRF (src/simple-crf.{h,hpp,cpp}): host state and bookkeeping here, inference in crf.hip --------------------------------
 // Every entry holds the CRF's mutex (a frame's: its parent's) for its duration; the numerics of the setters are the reference's
 // expressions (host libm logf, crf_expf for expf).

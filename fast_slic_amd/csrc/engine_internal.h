@@ -197,6 +197,14 @@ struct Slot {
     int last_path = 0;
     int n_host_topk = 0;             // frames of the last group whose top-K step ran on the host
     int n_separate_redo = 0;         // (accessed with __atomic builtins) frames (since the slot was created) redone with the separate cluster pass because of a stale pixel
+    // Label-free passes (group.cpp, enqueue_frames): once a frame of this slot had to be redone because a visited pixel lay outside every
+    // window, the slot keeps to the storing passes for that work (H, W, K, params: same_work's notion) -- a stream of scattered warm
+    // starts pays the redo once, not in every group; another work starts afresh.
+    int n_uncovered_redo = 0;        // (accessed with __atomic builtins) frames (since the slot was created) redone with storing passes because of kFlagUncoveredPixel
+    bool store_labels = false;       // the sticky fallback is in force for (store_H, store_W, store_K, store_p)
+    bool store_seen_credit = false;  // the fallback has just begun: the group that caused it counts as the first sighting of the storing sequence (launch_group)
+    int store_H = 0, store_W = 0, store_K = 0;
+    fslic_params store_p{};
     bool have_pre = false;
     // Ownership (guarded by fslic_engine::mu): `busy` while a synchronous call or a stage utility runs on the slot,
     // `pending` from the submission of an asynchronous group until it has been collected.

@@ -226,6 +226,10 @@ static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, 
     return fuse_wanted && !separate_cluster_pass && plain_slic && !generic && every_pass_has_rows && blk_kernel_applies(f, stride);
 }
 
+// Whether the slot's current work may take the label-free passes at all: not under the sticky fallback of a slot that has had to redo a
+// frame of this work (Slot::store_labels).  An input of enqueue_frames' choice that no launch argument shows: in the graph key.
+static bool label_free_allowed(const Slot& s) { return !s.store_labels; }
+
 // enforce_connectivity's minimum component size of the slot's current call, src/context.cpp:14-20
 static int min_size_threshold(const Slot& s) { return (int)round((double)(s.S * s.S) * (double)s.p.min_size_factor); }
 
@@ -260,7 +264,8 @@ static RecLayout rec_layout(const Slot& s) {
 // connectivity, export of the cluster state.  Pure
 // stream work with no per-call values in any launch argument (caller pointers sit in the device pointer table, bin
 // generations come from device memory), so the same sequence can be recorded once as a graph and replayed (launch_group).
-int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool timed, bool separate_cluster_pass = false) {
+// store_labels: never the label-free passes (a frame redone because of kFlagUncoveredPixel).
+int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool timed, bool separate_cluster_pass = false, bool store_labels = false) {
     const fslic_params* p = &s.p;
     const int K = s.K, S = s.S;
     FrameDev f = s.f;
@@ -309,6 +314,10 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // (8.54 against 8.18 us, same-box A/B, profiles/r06_experiments.txt) for the 0.6 us the LAB kernel saves once.
     const bool fusebin = cluster_pass_fused(f, *p, n, s.W, s.H, generic, separate_cluster_pass);      // (see the fused loop below)
     const bool lazy_labels = p->variant == FSLIC_VARIANT_SLIC && !generic && p->preemptive == 0 && !fusebin;
+    // Label-free group (DESIGN.md "Deferred labels"; FrameDev::fv_mod): the subsampled passes store no labels, the full pass defines the
+    // whole plane.  The ONE place where this is decided; what it depends on beyond the launch arguments (the slot's sticky fallback,
+    // label_free_allowed) is part of the graph key.
+    const bool label_free = lazy_labels && !store_labels && label_free_allowed(s) && p->max_iter >= 1 && !s.recording && blk_kernel_applies(f, p->subsample_stride);
     launch_rgb_to_lab(f, n, p->convert_to_lab, e->tables, !lazy_labels, s.st, s.gen_step,
                       s.at(s.zero_block, i0), s.zero_bytes, f.cl_n, 2 * (size_t)K, s.h_cl + (size_t)i0 * 4 * K, 4 * (size_t)K);      // (+ the staged centres -> cl_yx)
     if (timed) HIPCHK(hipEventRecord(s.ev[1], s.st));
@@ -437,7 +446,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         f.fv_mod = lazy_labels && it < stride ? 1 : 0; f.fv_from = 0;
         if (rec) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st, static_cast<uint16_t*>(rec_dist(it + 1)));     // (rec: generic)
         else if (generic || (pre && !launch_assign_pre(f, n, rem, stride, it & 1, it & 1, s.st))) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st);
-        else if (!pre) pg = launch_assign(f, n, rem, stride, it & 1, it & 1, true, s.st);
+        else if (!pre) pg = launch_assign(f, n, rem, stride, it & 1, it & 1, true, s.st, -1, label_free);
         if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
         f.gen_off++;
         f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
@@ -457,13 +466,16 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     if (timed) HIPCHK(hipEventRecord(s.ev[2], s.st));
     // (lazy reset: the rows of the residues no subsampled pass came to are first looked at by the full pass)
     f.fv_mod = lazy_labels && p->max_iter < stride ? stride : 0; f.fv_from = p->max_iter < stride ? std::max(p->max_iter, 0) : 0;
+    // (label-free group: no pass has written the plane, EVERY row is a first visit; an uncovered pixel gets its 0xFFFF -- the plane is
+    // defined before the connectivity kernels run -- and flags the frame)
+    if (label_free) { f.fv_mod = 1; f.fv_from = 0; }
     f.fv_rcp = f.fv_mod > 1 ? 0xFFFFFFFFu / (uint32_t)f.fv_mod : 0u;
     // full_assign: stride 1, rem 0, no update afterwards (src/context.cpp:246-256)
     if (lsc) { f.cl_yx = yx_cur; launch_lsc_assign(f, l, n, 0, 1, full_buf, 0, false, s.st); }
     else if (noq) { f.cl_yx = yx_cur; launch_noq_assign(f, noq_coef, noq_manhattan, n, 0, 1, full_buf, 0, false, s.st); }
     else if (rd) { f.cl_yx = yx_cur; launch_rd_assign(f, s.d_patchf, rd_l2, n, 0, 1, full_buf, 0, false, s.st); }
     else if (generic) launch_assign_generic(f, n, 0, 1, full_buf, 0, false, s.st);
-    else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf);      // (full_buf: the bins of all clusters; max_iter & 1 unless preemptive)
+    else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf, label_free);      // (full_buf: the bins of all clusters; max_iter & 1 unless preemptive)
     if (timed) HIPCHK(hipEventRecord(s.ev[3], s.st));
     const CcaDev c = cca_view(s, i0, s.f.labels, fb, K, min_size_threshold(s));
     // cluster state, overflow flag and connectivity status back to the host: the last kernel of the connectivity pass
@@ -511,7 +523,7 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
     // everything a launch argument can depend on
     std::vector<unsigned char> key;
     auto put = [&](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; key.insert(key.end(), b, b + bytes); };
-    const int hdr[8] = {s.H, s.W, s.K, s.S, n, s.generic ? 1 : 0, (int)s.gen_step, s.sp_patch_uploaded ? 1 : 0};
+    const int hdr[9] = {s.H, s.W, s.K, s.S, n, s.generic ? 1 : 0, (int)s.gen_step, s.sp_patch_uploaded ? 1 : 0, label_free_allowed(s) ? 1 : 0};
     const void* const ptrs[9] = {s.h_cl, s.h_misc, s.d_ptrs, s.h_patch, s.d_gen, s.lsc_zero, s.d_patchf, s.h_clf, s.h_upd};   // baked into copy nodes / arguments
     put(hdr, sizeof hdr); put(ptrs, sizeof ptrs); put(&s.p, sizeof s.p); put(&s.f, sizeof s.f); put(&s.c, sizeof s.c);
     if (s.p.variant == FSLIC_VARIANT_LSC) put(&s.l, sizeof s.l);
@@ -526,6 +538,11 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
         s.graphs.emplace_back();
         ge = &s.graphs.back();
         ge->key = key;
+        // The sticky fallback of the label-free passes changes the key.  The group that caused it was enqueued directly and its flagged
+        // frames were redone with the storing kernels, which is all a first sighting is for: the storing sequence of the same work is
+        // recorded on its first group, not on its second (a slot that serves three groups of such a work still reaches the replay).
+        if (s.store_seen_credit && s.store_labels) ge->seen = 1;
+        s.store_seen_credit = false;
     }
     if (!ge->exec) {
         if (ge->failed || ge->seen++ == 0) return enqueue_frames(e, s, 0, n, s.generic, true);   // first sighting: direct (also warms one-time setup)
@@ -567,6 +584,8 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     if (rc) return rc;
     const int cap_frames = s.cap_frames;
     s.H = H; s.W = W; s.K = K; s.S = S; s.p = *p; s.nframes = n;
+    // the sticky fallback of the label-free passes belongs to one work
+    if (s.store_labels && !(H == s.store_H && W == s.store_W && K == s.store_K && memcmp(&s.store_p, p, sizeof(fslic_params)) == 0)) { s.store_labels = false; s.store_seen_credit = false; }
     std::copy(job.clusters, job.clusters + n, s.clusters);
     rc = configure_spatial(s, S, p);
     if (rc) return rc;
@@ -670,20 +689,28 @@ int group_finish(fslic_engine* e, Slot& s) {
         // Flags of the tiled kernels.  kFlagStalePixel: a visited pixel that no window covered kept its label while the cluster pass was
         // fused into the assign kernel (its sums reached the owner through global atomics that nothing orders before the owner's
         // finaliser): that frame alone is redone with the separate cluster pass.  kFlagListOverflow: a block's candidate list overflowed: that
-        // frame alone is redone with the generic kernel.
+        // frame alone is redone with the generic kernel.  kFlagUncoveredPixel: a pass of a label-free group met a visited pixel no window
+        // covered (the one place where an earlier pass's label is needed): that frame alone is redone with storing passes, and the slot keeps
+        // to them for this work.
         for (int attempt = 0; attempt < 2 && !s.generic && hm[kStFlags] != 0; attempt++) {
             const bool overflow = (hm[kStFlags] & kFlagListOverflow) != 0;
-            if (knobs().host_timing) fprintf(stderr, "[fslic host] frame %d redone with %s\n", i, overflow ? "the generic kernel (candidate-list overflow)" : "the separate cluster pass (stale pixel)");
+            const bool uncovered = (hm[kStFlags] & kFlagUncoveredPixel) != 0;
+            if (uncovered) {
+                if (!s.store_labels) s.store_seen_credit = true;
+                s.store_labels = true; s.store_H = H; s.store_W = W; s.store_K = K; s.store_p = s.p;
+                __atomic_fetch_add(&s.n_uncovered_redo, 1, __ATOMIC_RELAXED);      // (read by fslic_hip_uncovered_redos without the engine lock)
+            }
+            if (knobs().host_timing) fprintf(stderr, "[fslic host] frame %d redone with %s\n", i, overflow ? "the generic kernel (candidate-list overflow)" : uncovered ? "storing assign passes (uncovered pixel)" : "the separate cluster pass (stale pixel)");
             stage_group(e, s, i, 1, false);
             s.gen_step = s.gen_span_prev;                 // past the stamps of the pass just made (same span)
             s.gen_host += s.gen_step;
-            int rc = enqueue_frames(e, s, i, 1, overflow, false, true);
+            int rc = enqueue_frames(e, s, i, 1, overflow, false, true, true);
             if (rc) return rc;
             HIPCHK(hipStreamSynchronize(s.st));
             if (overflow) {
                 if (hm[kStFlags] != 0) return fail(FSLIC_E_INTERNAL, "generic path reported a candidate overflow");
                 s.last_path = 1;
-            } else {
+            } else if (!uncovered) {
                 __atomic_fetch_add(&s.n_separate_redo, 1, __ATOMIC_RELAXED);      // (read by fslic_hip_separate_pass_redos without the engine lock)
             }
         }

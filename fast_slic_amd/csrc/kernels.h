@@ -46,6 +46,7 @@ enum StatusWord {
 constexpr int kStatusWords = 16;
 constexpr uint32_t kFlagListOverflow = 1u;   // a block's LDS candidate list overflowed: the host redoes the frame with the generic kernel
 constexpr uint32_t kFlagStalePixel = 2u;     // a visited pixel no window covered kept its label under the fused cluster pass: redone with the separate pass
+constexpr uint32_t kFlagUncoveredPixel = 4u; // a label-free group (FrameDev::fv_mod) met a visited pixel no window covered: the host redoes the frame with storing passes
 constexpr uint32_t kSelectDone = 0u;         // the device resolved the top-K step
 constexpr uint32_t kSelectTie = 1u;          // area tie at the cut, candidates left sorted by leader (k_cca_select; resolved on the device since)
 constexpr uint32_t kSelectHost = 2u;         // more candidates than the device sorts: the host gathers and sorts (cca_finish_group)
@@ -152,6 +153,11 @@ struct FrameDev {
     // iff fv_mod != 0 && y % fv_mod >= fv_from: subsampled pass it < stride: (1, 0), i.e. all of its rows; later subsampled passes:
     // (0, -); the full pass: (stride, min(max_iter, stride)), i.e. the residues no subsampled pass came to.  fv_mod == 0 everywhere
     // (and the plane filled by the LAB kernel) for the kernels that do not implement it: the variants, the generic kernel, preemptive mode.
+    // Label-free groups (round 10, DESIGN.md "Deferred labels"): the subsampled passes of such a group store no label at all (the NOLAB
+    // form of the block kernel: their sums work on ranks, and the full pass overwrites every pixel some window covers), so the plane is
+    // undefined until the full pass, which therefore runs with (1, 0) -- EVERY row is a first visit, a pixel no window covers gets 0xFFFF --
+    // in its own NOLAB form: such a pixel (in any pass of the group) is where an earlier pass's label would have been needed, the
+    // kernel raises kFlagUncoveredPixel in err_flag and the host redoes the frame with storing passes.
     int fv_mod, fv_from;
     uint32_t fv_rcp;     // floor((2^32 - 1) / fv_mod) (fv_mod > 1): y % fv_mod without a division (the test sits in the kernels' rare paths, but a 32-bit division is ~40 instructions each time it is inlined)
     __device__ __forceinline__ bool first_visit(int y) const {
@@ -302,7 +308,10 @@ bool blk_kernel_applies(const FrameDev& f, int stride);
 // One assign pass over rows == rem (mod stride); fuse_update also accumulates the centroid sums
 // of src/context.cpp:301-354 for the same rows.  Returns the geometry the following cluster pass needs.
 // obuf: which of the three spill lists the pass reads (buf for the two-buffer rotation of the separate cluster pass).
-PassGeom launch_assign(const FrameDev& f, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf = -1);
+// label_free (block kernel only, see FrameDev::fv_mod): a pass of a label-free group -- a fused pass neither reads nor writes the label
+// plane, the full pass (fv_mod == 1 there) writes all of it and reports the pixels no window covers.
+PassGeom launch_assign(const FrameDev& f, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf = -1,
+                       bool label_free = false);
 // The same with the cluster pass fused in (src/context.cpp:356-373 + the binning of src/context.cpp:214-221): the LAST assign block
 // that delivers partial sums of a cluster finalises it (integer means, re-binning for the next pass) -- no k_bin_clusters<1> launch
 // between two passes.  Pass `it` reads bins [it & 1] / spill list [it % 3], appends to [(it+1) & 1] / [(it+1) % 3].  Only for

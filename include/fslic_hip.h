@@ -249,6 +249,14 @@ int fslic_hip_last_host_topk_frames(fslic_engine* e, int slot);
  * FSLIC_FUSEBIN=0 (the separate cluster pass everywhere: +8 % latency per one-frame call, no redo).  Diagnostics aid. */
 int fslic_hip_separate_pass_redos(fslic_engine* e, int slot);
 
+/* Frames redone on `slot` since it was created because a visited pixel lay outside every cluster window while the group's subsampled
+ * assign passes ran in their label-free form (they store no labels: the full pass at the end overwrites every covered pixel, and only an
+ * uncovered pixel ever needs the label of an earlier pass).  Such a frame is recomputed with storing passes, the results are those of
+ * the reference either way, and the slot keeps to the storing passes for that work (H, W, K, params) from then on, so a stream of such
+ * inputs pays the redo once.  Grid-seeded and warm-started centres never leave a pixel uncovered; arbitrary caller-supplied centres
+ * can.  Diagnostics aid. */
+int fslic_hip_uncovered_redos(fslic_engine* e, int slot);
+
 /* Measurement aid (no counterpart in the reference): bytes read + written per second, in GB/s, of a plain streaming copy of
  * `bytes` on the engine's GPU (best of `reps` launches, HIP events) -- the measured HBM rate that bench.py prints next to the 8 TB/s of
  * the specification.  Allocates and frees 2 x `bytes` of device memory. */
