@@ -62,6 +62,8 @@ EXPORTS = [
     # SimpleCRF inference on torch tensors (fast_slic_amd/crf_torch.py)
     "fslic_hip_crf_tensor_workspace_size", "fslic_hip_crf_tensor_inference",
     "fslic_hip_crf_tensor_grad_workspace_size", "fslic_hip_crf_tensor_inference_saved", "fslic_hip_crf_tensor_backward",
+    "fslic_hip_crf_tensor_energies", "fslic_hip_crf_tensor_energies_backward_workspace_size", "fslic_hip_crf_tensor_energies_backward",
+    "fslic_hip_crf_tensor_inference_energies", "fslic_hip_crf_tensor_inference_saved_energies", "fslic_hip_crf_tensor_backward_energies",
 ]
 
 _lib = None
@@ -227,6 +229,17 @@ def _declare_crf_tensor(lib):
                                                       vp, vp, vp, sz]
         for name in ("crf_tensor_grad_workspace_size", "crf_tensor_inference_saved", "crf_tensor_backward"):
             getattr(lib, "fslic_hip_" + name).restype = i32
+    if hasattr(lib, "fslic_hip_crf_tensor_energies"):      # (likewise: the energies as tensors)
+        lib.fslic_hip_crf_tensor_energies.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+        lib.fslic_hip_crf_tensor_energies_backward_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
+        lib.fslic_hip_crf_tensor_energies_backward.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
+        lib.fslic_hip_crf_tensor_inference_energies.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, sz]
+        lib.fslic_hip_crf_tensor_inference_saved_energies.argtypes = lib.fslic_hip_crf_tensor_inference_energies.argtypes
+        lib.fslic_hip_crf_tensor_backward_energies.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                               vp, vp, vp, vp, vp, vp, vp, sz]
+        for name in ("energies", "energies_backward_workspace_size", "energies_backward", "inference_energies", "inference_saved_energies",
+                     "backward_energies"):
+            getattr(lib, "fslic_hip_crf_tensor_" + name).restype = i32
 
 
 def _raise(rc):

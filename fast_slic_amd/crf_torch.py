@@ -15,8 +15,13 @@ package itself does not import it.
 
 The call is differentiable (csrc/crf_tensor_grad.hip): when gradients are enabled and `unaries`, `q0` or a tensor `compat` requires
 one, the same sweeps run with every iterate kept ((max_iter + 1) * 4 * N * C * K bytes), the result has the same bits, and backward()
-gives deterministic gradients for those three.  Nothing flows to `yxrgb`, `members`, the graph or `params`: learning the kernel
-weights is out of scope.
+gives deterministic gradients for those three.
+
+The edge energies can be learnt.  `params` may be a float32 [7] tensor on the GPU in PARAM_NAMES order (an nn.Parameter): backward()
+then fills its gradient.  crf_edge_energies(graph, yxrgb, members, params, temporal) returns the energies themselves, one per
+neighbour entry and two per node, and `energies=(edge, links)` runs the sweeps on energies a caller (a network) provides; the result
+is differentiable with respect to both.  A tensor `params` is the composition of the two.  Nothing flows to `yxrgb`, `members` or the
+graph.
 """
 import ctypes as C
 import numbers
@@ -29,7 +34,9 @@ from .crf import _PARAMS, _Params
 from .pool import _check_device, _check_float_map, _stream
 from .rag import SuperpixelGraph
 
-__all__ = ["superpixel_crf", "transpose_batch_csr", "DEFAULT_PARAMS"]
+__all__ = ["superpixel_crf", "crf_edge_energies", "transpose_batch_csr", "DEFAULT_PARAMS", "PARAM_NAMES"]
+
+PARAM_NAMES = _PARAMS                 # the order of fslic_crf_params and of a params tensor
 
 # a fresh SimpleCRF's (src/simple-crf.hpp:81-87); its compat is 1.0 for every class
 DEFAULT_PARAMS = dict(spatial_w=10.0, temporal_w=10.0, spatial_srgb=13.0, temporal_srgb=13.0, spatial_sxy=80.0, spatial_smooth_w=0.0,
@@ -75,6 +82,32 @@ def _check_graph(graph, N, K):
     if indices.dim() != 1:
         raise ValueError("graph indices must be one-dimensional, got shape %s" % (tuple(indices.shape),))
     return int(indices.shape[0])
+
+
+def _check_params_tensor(params):
+    if params.dtype != torch.float32:
+        raise ValueError("a params tensor must be float32, got %s" % params.dtype)
+    if tuple(params.shape) != (len(_PARAMS),):
+        raise ValueError("a params tensor must have shape (%d,) in the order %s, got %s" % (len(_PARAMS), _PARAMS, tuple(params.shape)))
+
+
+def _check_energies(energies, nnz, lead, K, temporal):
+    """-> (edge, links or None)."""
+    if not isinstance(energies, (tuple, list)) or len(energies) != 2:
+        raise ValueError("energies must be a pair (edge, links)")
+    edge, links = energies
+    if not isinstance(edge, torch.Tensor):
+        raise ValueError("energies: edge must be a torch tensor")
+    if edge.dtype != torch.float32:
+        raise ValueError("energies: edge must be float32, got %s" % edge.dtype)
+    if tuple(edge.shape) != (nnz,):
+        raise ValueError("energies: edge must have shape (%d,) (one value per neighbour entry), got %s" % (nnz, tuple(edge.shape)))
+    if links is None:
+        if temporal:
+            raise ValueError("energies: links must be given with temporal=True")
+        return edge, None
+    _check_tensor(links, torch.float32, lead + (2, K), "energies: links", "[2, K] or [N, 2, K]")
+    return edge, links
 
 
 def _check_params(params):
@@ -183,7 +216,175 @@ class _SuperpixelCRF(torch.autograd.Function):
         return du, dq0, dcompat, None, None, None, None, None, None, None, None
 
 
-def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, compat=None, temporal=False, q0=None):
+class _SuperpixelCRFEnergies(torch.autograd.Function):
+    """_SuperpixelCRF with the energies given: `edge` [nnz] and `links` [N, 2, K] or None get gradients too."""
+
+    @staticmethod
+    def forward(ctx, un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal):
+        lib, dev = _lib_energies(), un.device
+        Cn, K = (int(v) for v in un.shape[-2:])
+        nnz = int(indices.shape[0])
+        with torch.cuda.device(dev):
+            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, False, False)
+            q_all = torch.empty((max_iter + 1,) + tuple(un.shape), dtype=torch.float32, device=dev)
+            B._check(lib.fslic_hip_crf_tensor_inference_saved_energies(
+                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
+                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if links is not None else None,
+                un.data_ptr(), start.data_ptr() if start is not None else None, q_all.data_ptr(), ws.data_ptr(), nbytes))
+        ctx.save_for_backward(un, comp, edge, mem, offsets, indices, q_all, *(() if links is None else (links,)))
+        ctx.call = (N, max_iter, temporal, start is not None, links is not None)
+        return q_all[max_iter]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        un, comp, edge, mem, offsets, indices, q_all = ctx.saved_tensors[:7]
+        N, max_iter, temporal, has_q0, has_links = ctx.call
+        links = ctx.saved_tensors[7] if has_links else None
+        lib, dev = _lib_energies(), un.device
+        Cn, K = (int(v) for v in un.shape[-2:])
+        nnz = int(indices.shape[0])
+        with torch.cuda.device(dev):
+            g = g.contiguous()
+            t_offsets, t_entries, t_rows = transpose_batch_csr(offsets, indices, N, K)
+            du = torch.empty_like(un)
+            dq0 = torch.empty_like(un) if has_q0 else None
+            dcompat = torch.empty_like(comp) if ctx.needs_input_grad[2] else None
+            dedge = torch.empty_like(edge) if ctx.needs_input_grad[3] else None
+            dlinks = torch.empty_like(links) if has_links and ctx.needs_input_grad[4] else None
+            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, True, dcompat is not None)
+            B._check(lib.fslic_hip_crf_tensor_backward_energies(
+                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
+                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if has_links else None,
+                t_offsets.data_ptr(), t_entries.data_ptr() if nnz else None, t_rows.data_ptr() if nnz else None, un.data_ptr(),
+                q_all.data_ptr(), g.data_ptr(), du.data_ptr(), dq0.data_ptr() if has_q0 else None,
+                dcompat.data_ptr() if dcompat is not None else None, dedge.data_ptr() if dedge is not None and nnz else None,
+                dlinks.data_ptr() if dlinks is not None else None, ws.data_ptr(), nbytes))
+        return du, dq0, dcompat, dedge, dlinks, None, None, None, None, None, None
+
+
+def _lib_energies():
+    lib = _lib()
+    if not hasattr(lib, "fslic_hip_crf_tensor_backward_energies"):
+        raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor energies entry points; rebuild it")
+    return lib
+
+
+def _energies_raw(theta, yx, mem, offsets, indices, N, K, temporal):
+    """edge [nnz] and links [N, 2, K] from contiguous tensors on one GPU."""
+    lib, dev = _lib_energies(), yx.device
+    nnz = int(indices.shape[0])
+    with torch.cuda.device(dev):
+        edge = torch.empty(nnz, dtype=torch.float32, device=dev)
+        links = torch.empty((N, 2, K), dtype=torch.float32, device=dev)
+        B._check(lib.fslic_hip_crf_tensor_energies(dev.index, _stream(dev), N, K, int(temporal), theta.data_ptr(), yx.data_ptr(),
+                                                   mem.data_ptr(), offsets.data_ptr(), indices.data_ptr() if nnz else None, nnz,
+                                                   edge.data_ptr() if nnz else None, links.data_ptr()))
+    return edge, links
+
+
+class _EdgeEnergies(torch.autograd.Function):
+    """The energies from a params tensor, and their backward to it."""
+
+    @staticmethod
+    def forward(ctx, theta, yx, mem, offsets, indices, N, K, temporal):
+        edge, links = _energies_raw(theta, yx, mem, offsets, indices, N, K, temporal)
+        ctx.save_for_backward(theta, yx, offsets, indices)
+        ctx.call = (N, K, temporal)
+        return edge, links
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_edge, g_links):
+        theta, yx, offsets, indices = ctx.saved_tensors
+        N, K, temporal = ctx.call
+        lib, dev = _lib_energies(), yx.device
+        nnz = int(indices.shape[0])
+        with torch.cuda.device(dev):
+            g_edge = g_edge.contiguous() if g_edge is not None and nnz else None
+            g_links = g_links.contiguous() if g_links is not None else None
+            nbytes = C.c_size_t()
+            B._check(lib.fslic_hip_crf_tensor_energies_backward_workspace_size(N, K, C.byref(nbytes)))
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            dtheta = torch.empty_like(theta)
+            B._check(lib.fslic_hip_crf_tensor_energies_backward(
+                dev.index, _stream(dev), N, K, int(temporal), theta.data_ptr(), yx.data_ptr(), offsets.data_ptr(),
+                indices.data_ptr() if nnz else None, nnz, g_edge.data_ptr() if g_edge is not None else None,
+                g_links.data_ptr() if g_links is not None else None, dtheta.data_ptr(), ws.data_ptr(), nbytes.value))
+        return dtheta, None, None, None, None, None, None, None
+
+
+def _params_on(params, dev):
+    """A dict or None -> the seven float32 values on `dev`, through pinned memory (no host synchronisation)."""
+    p = _check_params(params)
+    return torch.tensor([getattr(p, n) for n in _PARAMS], dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+
+
+def _energies(theta, yx, mem, offsets, indices, N, K, temporal):
+    if torch.is_grad_enabled() and theta.requires_grad:
+        return _EdgeEnergies.apply(theta.contiguous(), yx.detach(), mem, offsets, indices, N, K, temporal)
+    return _energies_raw(theta.detach().contiguous(), yx.detach(), mem, offsets, indices, N, K, temporal)
+
+
+def _batch_csr(graph):
+    if isinstance(graph, SuperpixelGraph):
+        return graph.to_batch_csr()
+    return graph[0].contiguous(), graph[1].contiguous()
+
+
+def _check_same_device(dev, named):
+    for what, t in named:
+        if isinstance(t, torch.Tensor):
+            _check_device(t, what)
+            if t.device != dev:
+                raise ValueError("%s must be on the unaries' GPU %s, got %s" % (what, dev, t.device))
+
+
+def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
+    """The pairwise energies superpixel_crf computes for itself -> (edge float32 [nnz], links float32 [N, 2, K], or [2, K] for
+    unbatched clusters).
+
+    edge[k] is the spatial energy of neighbour entry k of the batch CSR (the pair as given, or graph.to_batch_csr()): 0.0 for a
+    self-loop and for an entry whose index is outside [0, K).  links[n, 0, i] is the temporal energy of node i of frame n towards
+    n - 1, links[n, 1, i] the one towards n + 1; 0.0 where there is no such frame or `temporal` is false.  The values are the very
+    floats of the sweeps.  yxrgb [5, K] / [N, 5, K] float32 and members [K] / [N, K] int32 as for superpixel_crf.
+    params: None, a dict, or a float32 [7] tensor on the clusters' GPU in PARAM_NAMES order, read on the device.  With a tensor that
+    requires a gradient the result is differentiable with respect to it (terms and sums in double, a fixed order, no atomics); it is
+    not differentiable with respect to yxrgb.  Runs on the current stream without host synchronisation."""
+    _check_float_map(yxrgb, (2, 3), "yxrgb", "[5, K] or [N, 5, K]")
+    batched = yxrgb.dim() == 3
+    N = yxrgb.shape[0] if batched else 1
+    if yxrgb.shape[-2] != 5:
+        raise ValueError("yxrgb must be [5, K] or [N, 5, K], got shape %s" % (tuple(yxrgb.shape),))
+    K = int(yxrgb.shape[-1])
+    lead = (N,) if batched else ()
+    _check_tensor(members, torch.int32, lead + (K,), "members", "[K] or [N, K]")
+    nnz = _check_graph(graph, N, K)
+    if isinstance(params, torch.Tensor):
+        _check_params_tensor(params)
+    else:
+        _check_params(params)
+    if not isinstance(temporal, bool):
+        raise ValueError("temporal must be True or False, got %r" % (temporal,))
+    if N * K + 1 >= _LIMIT or nnz >= _LIMIT:
+        raise ValueError("N * K + 1 and the number of neighbour entries must be below 2^31")
+    _check_device(yxrgb, "yxrgb")
+    dev = yxrgb.device
+    on_graph = (("graph.edge_index", graph.edge_index), ("graph.offsets", graph.offsets)) if isinstance(graph, SuperpixelGraph) \
+        else (("graph offsets", graph[0]), ("graph indices", graph[1]))
+    for what, t in (("members", members), ("params", params)) + on_graph:
+        if isinstance(t, torch.Tensor):
+            _check_device(t, what)
+            if t.device != dev:
+                raise ValueError("%s must be on yxrgb's GPU %s, got %s" % (what, dev, t.device))
+    with torch.cuda.device(dev):
+        offsets, indices = _batch_csr(graph)
+        theta = params if isinstance(params, torch.Tensor) else _params_on(params, dev)
+        edge, links = _energies(theta, yxrgb.contiguous(), members.contiguous(), offsets, indices, N, K, temporal)
+    return edge, (links if batched else links[0])
+
+
+def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, compat=None, temporal=False, q0=None, energies=None):
     """`max_iter` mean-field sweeps of SimpleCRF over `unaries` ([C, K] or [N, C, K] float32 energies on a ROCm GPU) -> q, a new
     tensor of the same shape.
 
@@ -192,8 +393,12 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     non-decreasing on the device (nothing is validated on the host: that would synchronise).
     yxrgb [5, K] / [N, 5, K] float32, members [K] / [N, K] int32: the clusters.
     params: None or a dict over spatial_w, temporal_w, spatial_srgb, temporal_srgb, spatial_sxy, spatial_smooth_w,
-    spatial_smooth_sxy (a fresh SimpleCRF's values for the names left out).  compat: None (1.0 per class), C floats, or a float32
-    [C] tensor on the same GPU.
+    spatial_smooth_sxy (a fresh SimpleCRF's values for the names left out), or a float32 [7] tensor on the same GPU in PARAM_NAMES
+    order, read on the device: the energies of crf_edge_energies, then the sweeps on them; q has the bits of the dict call with the
+    same seven values.  compat: None (1.0 per class), C floats, or a float32 [C] tensor on the same GPU.
+    energies: None, or (edge float32 [nnz], links float32 [N, 2, K] / [2, K]) on the same GPU in the layout of crf_edge_energies:
+    the sweeps use them in place of computed ones, the weight of entry k being edge[k] times the member factor, also for a
+    self-loop.  links may be None when temporal is false.  params must then be None and yxrgb may be None.
     temporal=False: the N frames are independent.  temporal=True: they are consecutive times of one window, node i of frame n
     linked to node i of n - 1 and n + 1, exactly as in SimpleCRF.
     q0: the starting q, float32 of the unaries' shape (never written); None: crf_expf(-unaries), which is SimpleCRF.initialize().
@@ -202,14 +407,19 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     Differentiable with respect to `unaries`, `q0` and a tensor `compat`: when gradients are enabled and one of them requires one,
     q is part of the autograd graph (the same bits; every iterate is kept for the backward, (max_iter + 1) * 4 * N * C * K bytes) and
     its backward is deterministic and once differentiable; q is then a view of the kept iterates, which autograd protects from
-    in-place changes.  `yxrgb`, `members`, the graph and `params` get no gradient: learning the
-    kernel weights (gradients with respect to params or the edge energies) is out of scope.  Otherwise q has no grad_fn."""
+    in-place changes.  So is it with respect to a tensor `params` and to both `energies`: behind each sweep's adjoint one launch adds
+    the sweep's part of the energy gradients, one owner thread per cell, and a params tensor receives the energies' backward of them.
+    An entry whose index is outside [0, K), the link cells at the window's ends and all of links with temporal false get 0.0.
+    `yxrgb`, `members` and the graph get no gradient.  Otherwise q has no grad_fn."""
     _check_float_map(unaries, (2, 3), "unaries", "[C, K] or [N, C, K]")
     batched = unaries.dim() == 3
     N = unaries.shape[0] if batched else 1
     Cn, K = (int(v) for v in unaries.shape[-2:])
     lead = (N,) if batched else ()
-    _check_tensor(yxrgb, torch.float32, lead + (5, K), "yxrgb", "[5, K] or [N, 5, K]")
+    if yxrgb is not None or energies is None:
+        if yxrgb is None:
+            raise ValueError("yxrgb must be given unless energies are")
+        _check_tensor(yxrgb, torch.float32, lead + (5, K), "yxrgb", "[5, K] or [N, 5, K]")
     _check_tensor(members, torch.int32, lead + (K,), "members", "[K] or [N, K]")
     if q0 is not None:
         _check_tensor(q0, torch.float32, tuple(unaries.shape), "q0", "the unaries' shape")
@@ -219,34 +429,54 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     max_iter = int(max_iter)
     if max_iter >= _LIMIT:
         raise ValueError("max_iter must be below 2^31")
-    p = _check_params(params)
+    p = edge = links = None
+    if energies is not None and params is not None:
+        raise ValueError("params must be None when energies are given")
+    if isinstance(params, torch.Tensor):
+        _check_params_tensor(params)
+    elif energies is None:
+        p = _check_params(params)
     compat = _check_compat(compat, Cn)
     if not isinstance(temporal, bool):
         raise ValueError("temporal must be True or False, got %r" % (temporal,))
+    if energies is not None:
+        edge, links = _check_energies(energies, nnz, lead, K, temporal)
     if N * Cn * K >= _LIMIT or N * K + 1 >= _LIMIT or nnz >= _LIMIT:
         raise ValueError("N * C * K, N * K + 1 and the number of neighbour entries must be below 2^31")
     _check_device(unaries, "unaries")
     dev = unaries.device
     on_graph = (("graph.edge_index", graph.edge_index), ("graph.offsets", graph.offsets)) if isinstance(graph, SuperpixelGraph) \
         else (("graph offsets", graph[0]), ("graph indices", graph[1]))
-    for what, t in (("yxrgb", yxrgb), ("members", members), ("q0", q0), ("compat", compat)) + on_graph:
-        if isinstance(t, torch.Tensor):
-            _check_device(t, what)
-            if t.device != dev:
-                raise ValueError("%s must be on the unaries' GPU %s, got %s" % (what, dev, t.device))
+    _check_same_device(dev, (("yxrgb", yxrgb), ("members", members), ("q0", q0), ("compat", compat), ("params", params),
+                             ("energies: edge", edge), ("energies: links", links)) + on_graph)
 
     lib = _lib()
     with torch.cuda.device(dev):
-        if isinstance(graph, SuperpixelGraph):
-            offsets, indices = graph.to_batch_csr()
-        else:
-            offsets, indices = graph[0].contiguous(), graph[1].contiguous()
+        offsets, indices = _batch_csr(graph)
         if compat is None:
             compat = torch.ones(Cn, dtype=torch.float32, device=dev)
         elif isinstance(compat, list):       # through pinned memory: an asynchronous copy, no host synchronisation
             compat = torch.tensor(compat, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
-        un, yx, mem, comp = unaries.contiguous(), yxrgb.contiguous(), members.contiguous(), compat.contiguous()
+        un, mem, comp = unaries.contiguous(), members.contiguous(), compat.contiguous()
         start = q0.contiguous() if q0 is not None else None
+        if p is None:
+            if energies is None:         # the composition: the energies from the params on the device, then the sweeps on them
+                edge, links = _energies(params, yxrgb.contiguous(), mem, offsets, indices, N, K, temporal)
+            edge = edge.contiguous()
+            links = links.contiguous().view(N, 2, K) if links is not None else None
+            if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unaries, q0, compat, edge, links)):
+                return _SuperpixelCRFEnergies.apply(un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal)
+            lib = _lib_energies()
+            nbytes = C.c_size_t()
+            B._check(lib.fslic_hip_crf_tensor_workspace_size(N, Cn, K, nnz, C.byref(nbytes)))
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            q = torch.empty(tuple(unaries.shape), dtype=torch.float32, device=dev)
+            B._check(lib.fslic_hip_crf_tensor_inference_energies(
+                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
+                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if links is not None else None,
+                un.data_ptr(), start.data_ptr() if start is not None else None, q.data_ptr(), ws.data_ptr(), nbytes.value))
+            return q
+        yx = yxrgb.contiguous()
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unaries, q0, compat)):
             return _SuperpixelCRF.apply(un, start, comp, yx.detach(), mem, offsets, indices, N, max_iter, temporal, p)
         nbytes = C.c_size_t()

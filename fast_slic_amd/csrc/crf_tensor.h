@@ -28,6 +28,16 @@ struct CrfTensorParams {
     fslic_crf_params p;
 };
 
+// The forms of the edge pass (k_crf_tensor_edges) and the caller tensors of the two that have some.
+enum { kCrfEdgesHost = 0, kCrfEdgesOut = 1, kCrfEdgesGiven = 2 };
+struct CrfEdgeTensors {
+    const float* params;        // kCrfEdgesOut: the seven params in the order of fslic_crf_params, device memory
+    float* edge_out;            //               [nnz]
+    float* links_out;           //               [N][2][K]: towards n - 1, towards n + 1
+    const float* edge_in;       // kCrfEdgesGiven: [nnz]
+    const float* links_in;      //                 [N][2][K], or NULL: no temporal energy
+};
+
 struct CrfTensorWorkspace {
     size_t rows, temporal, edge, q, msg, bytes;
 };
@@ -48,6 +58,14 @@ inline CrfTensorWorkspace crf_tensor_workspace(int N, int C, int K, long long nn
 void launch_crf_tensor_start(const float* unaries, const float* q0, float* out, size_t n, hipStream_t st);
 void launch_crf_tensor_edges(const CrfTensorParams& dp, const float* yxrgb, const int32_t* members, const int64_t* offsets,
                              const int32_t* indices, uint2* rows, float2* edge, float4* temporal, hipStream_t st);
+// The energies alone, from params in device memory: edge_out[k] for the entries inside the clamped rows (the caller zeroes the rest),
+// every cell of links_out.  dp.p is not read.
+void launch_crf_tensor_energies(const CrfTensorParams& dp, const float* params, const float* yxrgb, const int32_t* members,
+                                const int64_t* offsets, const int32_t* indices, float* edge_out, float* links_out, hipStream_t st);
+// launch_crf_tensor_edges with the energies taken from edge_in [nnz] and links_in [N][2][K] (NULL: none).  dp.p is not read.
+void launch_crf_tensor_edges_given(const CrfTensorParams& dp, const float* edge_in, const float* links_in, const int32_t* members,
+                                   const int64_t* offsets, const int32_t* indices, uint2* rows, float2* edge, float4* temporal,
+                                   hipStream_t st);
 void launch_crf_tensor_sweep(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
                              const float4* temporal, const float* unaries, const float* compat, const float* q_in, float* q_out,
                              float* msg, hipStream_t st);

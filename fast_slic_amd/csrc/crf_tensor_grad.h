@@ -12,6 +12,13 @@
 //   x[N * C * K]         float   -- exponentials, then G' q', then da, only for C > kCrfTensorLdsClasses
 //   slots[blocks][C]     float   -- per block of the sweep its part of the gradient of compat, blocks = N * ceil(K / 64); only
 //                                   when that gradient is asked for
+// With given energies (fslic_hip_crf_tensor_*_energies) the layout is the same: rows, temporal and edge are filled from the caller's
+// edge [nnz] and links [N][2][K] with the member factors and dead flags computed on the device; the gradients of the energies go to
+// caller tensors and need no part of their own.
+//
+// Workspace of one fslic_hip_crf_tensor_energies_backward call:
+//   slots[blocks][7]     double  -- per block of 256 (frame, node) threads its part of the gradient of the seven params,
+//                                   blocks = ceil(N * K / 256)
 #pragma once
 #include "crf_tensor.h"
 
@@ -37,6 +44,13 @@ inline CrfTensorGradWorkspace crf_tensor_grad_workspace(int N, int C, int K, lon
     return w;
 }
 
+constexpr int kCrfParamCount = 7;             // the floats of fslic_crf_params
+constexpr int kCrfParamGradBlock = 256;       // (frame, node) threads per block of k_crf_tensor_param_grad
+inline size_t crf_tensor_param_grad_blocks(int N, int K) { return ((size_t)N * (size_t)K + kCrfParamGradBlock - 1) / kCrfParamGradBlock; }
+inline size_t crf_tensor_param_grad_workspace(int N, int K) {
+    return (crf_tensor_param_grad_blocks(N, K) * kCrfParamCount * sizeof(double) + 15) & ~(size_t)15;
+}
+
 // The transposed neighbour lists: for (frame, node) g the entries t_offsets[g] <= t < t_offsets[g + 1] name the neighbour entries
 // t_entries[t] of the rows t_rows[t] whose target g is, in ascending entry order.
 struct CrfTensorTransposed {
@@ -60,5 +74,17 @@ void launch_crf_tensor_grad_close(const CrfTensorParams& dp, const uint2* rows, 
                                   float* grad_unaries, float* grad_q0, bool first, hipStream_t st);
 // grad_compat[c] = the sum of slots[b][c] over the blocks in ascending order (blocks == 0: zero).
 void launch_crf_tensor_grad_compat(const float* slots, size_t blocks, int C, float* grad_compat, hipStream_t st);
+// The gradient of the energies from one sweep, behind its launch_crf_tensor_sweep_bwd: dm is what that launch left in dm_out, q_in
+// the sweep's input iterate.  Adds to grad_edge [nnz] (live entries inside the clamped rows, each found through its position in the
+// transposed lists) and to grad_links [N][2][K] (cells with a neighbouring frame, only with dp.temporal); either may be NULL.  The
+// caller zeroes both before the first launch.
+void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
+                                   const float4* temporal, const CrfTensorTransposed& tr, const float* dm, const float* q_in,
+                                   float* grad_edge, float* grad_links, hipStream_t st);
+// The backward of launch_crf_tensor_energies: grad_params[7] from grad_edge [nnz] and grad_links [N][2][K] (either may be NULL: zero)
+// and the params in device memory; slots is the workspace above.  Nothing flows to yxrgb.
+void launch_crf_tensor_param_grad(const CrfTensorParams& dp, const float* params, const float* yxrgb, const int64_t* offsets,
+                                  const int32_t* indices, const float* grad_edge, const float* grad_links, double* slots,
+                                  float* grad_params, hipStream_t st);
 
 }  // namespace fslic

@@ -17,6 +17,20 @@
 //                            kCrfTensorLdsClasses classes both planes are the workspace's.
 //   k_crf_tensor_grad_close  one thread per cell: the last gather, then dq0 = G or du += -q_start G.
 //   k_crf_tensor_grad_compat one thread per class: the blocks' slots added in ascending block order.
+// The gradients of the energies and of the seven params:
+//   k_crf_tensor_energy_grad one launch behind each k_crf_tensor_sweep_bwd launch.  One thread per neighbour entry, named by its
+//                            position in the transposed lists (a permutation of the entries, checked as crf_grad_gather checks it):
+//                            ge[k] += f_k sum_c dm[row(k),c] q[j_k,c]; behind them one thread per (frame, node):
+//                            gl[n,0,i] += f_prev sum_c dm[n,c,i] q[n-1,c,i] and gl[n,1,i] likewise with n + 1.  Classes in ascending
+//                            order, the sweeps last to first, the cells zeroed on the stream before the first launch.  Neighbouring
+//                            threads share their target, so q[j_k,c] is one address per run and dm a gather.  A thread per
+//                            (frame, node) walking its row, the first design, had 25 wavefronts at K = 1600 and took longer
+//                            than the sweep's adjoint itself.
+//   k_crf_tensor_param_grad  the energies' backward: one thread per (frame, node) over its row and its two links, every term formed in
+//                            double from the float inputs and added in entry order; a butterfly over the wavefront (every lane the same
+//                            fixed order), lane 0 of each wavefront into LDS, one thread per name adding the four wavefronts in
+//                            ascending order into the block's slot row of seven doubles.
+//   k_crf_tensor_param_grad_close  one thread per name: the slot rows in ascending block order, in double, stored as float.
 // Determinism: no atomics.  Every output cell and every slot has one owner thread, every sum one fixed order: du and dm belong to
 // thread (node, class), a slot to lane 0 of the wavefront of (block, class) after the fixed-order wave_reduce_add, the launches of a
 // call follow each other on one stream.  That is why G is a gather over the transposed lists and not a scatter.
@@ -198,6 +212,135 @@ __global__ __launch_bounds__(256) void k_crf_tensor_grad_compat(const float* __r
     float s = 0.0f;
     for (size_t b = 0; b < blocks; ++b) s += slots[b * C + c];
     out[c] = s;
+}
+
+// The sum over the classes of dm[w, c, i] * q[c * K] in ascending order: d = dm + w * C * K + i, q the other node's column.
+static __device__ __forceinline__ float crf_class_dot(const float* __restrict__ d, const float* __restrict__ q, int C, int K) {
+    float s = 0.0f;
+    for (int c = 0; c < C; ++c) s = __builtin_fmaf(d[(size_t)c * K], q[(size_t)c * K], s);
+    return s;
+}
+
+__global__ __launch_bounds__(256) void k_crf_tensor_energy_grad(CrfTensorParams dp, CrfGradLists L, const int32_t* __restrict__ idx,
+                                                                const float* __restrict__ dm, const float* __restrict__ q_in,
+                                                                float* __restrict__ ge, float* __restrict__ gl, uint32_t entries) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const int C = dp.C, K = dp.K;
+    const uint32_t n = (uint32_t)dp.N * (uint32_t)K;
+    const size_t CK = (size_t)C * K;
+    if (p < entries) {
+        // one neighbour entry, named by position p of the transposed lists (a permutation of the entries): the check of crf_grad_gather
+        const uint32_t row = (uint32_t)L.tr.rows[p];
+        if (row >= n) return;                                                  // behind the last row
+        const uint32_t k = (uint32_t)L.tr.entries[p];
+        const uint2 r = L.rows[row];
+        if (k < r.x || k >= r.y) return;                                       // r.y <= nnz: edge[k], idx[k] and ge[k] exist
+        const float2 es = L.edge[k];
+        if (es.y == kCrfDeadEntry) return;                                     // idx[k] is outside [0, K): its gradient stays 0.0
+        const uint32_t w = row / (uint32_t)K, i = row - w * (uint32_t)K;
+        ge[k] += es.y * crf_class_dot(dm + (size_t)w * CK + i, q_in + (size_t)w * CK + idx[k], C, K);
+        return;
+    }
+    const uint32_t g = p - entries;                                            // one (frame, node): its two link cells
+    if (g >= n || !gl || !dp.temporal) return;
+    const int w = (int)(g / (uint32_t)K), i = (int)(g - (uint32_t)w * (uint32_t)K);
+    const float* d = dm + (size_t)w * CK + i;
+    const float* q = q_in + (size_t)w * CK + i;
+    const float4 t = L.temporal[g];
+    const size_t link = ((size_t)w * 2) * K + i;
+    if (w > 0) gl[link] += t.y * crf_class_dot(d, q - (ptrdiff_t)CK, C, K);
+    if (w < dp.N - 1) gl[link + K] += t.w * crf_class_dot(d, q + CK, C, K);
+}
+
+// The sum over the wavefront in every lane: a butterfly, so each lane adds the same pairs in the same order.
+static __device__ __forceinline__ double crf_wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(kCrfParamGradBlock) void k_crf_tensor_param_grad(
+        CrfTensorParams dp, const float* __restrict__ params, const float* __restrict__ yxrgb, const int64_t* __restrict__ offsets,
+        const int32_t* __restrict__ idx, const float* __restrict__ ge, const float* __restrict__ gl, double* __restrict__ slots) {
+    __shared__ double s_part[kCrfParamGradBlock / 64][kCrfParamCount];
+    const int n = dp.N * dp.K;
+    const int g = blockIdx.x * kCrfParamGradBlock + threadIdx.x;
+    double acc[kCrfParamCount] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};         // in the order of fslic_crf_params
+    if (g < n) {
+        const int K = dp.K;
+        const int w = g / K, i = g - w * K;
+        const float* planes = yxrgb + (size_t)w * 5 * K;
+        const double yi = planes[i], xi = planes[K + i], ri = planes[2 * (size_t)K + i], gi = planes[3 * (size_t)K + i], bi = planes[4 * (size_t)K + i];
+        if (ge) {
+            const double sw = params[0], srgb = params[2], sxy = params[4], ssw = params[5], ssxy = params[6];
+            const uint2 r = crf_grad_bounds(dp, offsets, (size_t)g);           // the row's bounds as k_crf_tensor_edges clamps them
+            for (uint32_t k = r.x; k < r.y; ++k) {
+                const int32_t j = idx[k];
+                if ((uint32_t)j >= (uint32_t)K || j == i) continue;            // a dead entry, a self-loop: the energy is the constant 0
+                const double dy = yi - (double)planes[j], dx = xi - (double)planes[K + j];
+                const double dr = ri - (double)planes[2 * (size_t)K + j], dg = gi - (double)planes[3 * (size_t)K + j], db = bi - (double)planes[4 * (size_t)K + j];
+                const double Drgb = dr * dr + dg * dg + db * db, Dxy = dx * dx + dy * dy;
+                const double E1 = exp(-(Drgb / (srgb * srgb) + Dxy / (sxy * sxy)) * 0.5), E2 = exp(-(Dxy / (ssxy * ssxy)) * 0.5);
+                const double up = ge[k];
+                acc[0] += up * E1;
+                acc[2] += up * (sw * E1 * Drgb / (srgb * srgb * srgb));
+                acc[4] += up * (sw * E1 * Dxy / (sxy * sxy * sxy));
+                acc[5] += up * E2;
+                acc[6] += up * (ssw * E2 * Dxy / (ssxy * ssxy * ssxy));
+            }
+        }
+        if (gl && dp.temporal) {
+            const double tw = params[1], tsrgb = params[3];
+            const size_t link = ((size_t)w * 2) * K + i;
+            for (int side = 0; side < 2; ++side) {                             // towards w - 1, then towards w + 1
+                if (side == 0 ? w == 0 : w == dp.N - 1) continue;
+                const float* other = side == 0 ? planes - (size_t)5 * K : planes + (size_t)5 * K;
+                const double dr = ri - (double)other[2 * (size_t)K + i], dg = gi - (double)other[3 * (size_t)K + i], db = bi - (double)other[4 * (size_t)K + i];
+                const double Drgb = dr * dr + dg * dg + db * db;
+                const double Et = exp(-(Drgb / (tsrgb * tsrgb)) * 0.5);
+                const double up = gl[link + (size_t)side * K];
+                acc[1] += up * Et;
+                acc[3] += up * (tw * Et * Drgb / (tsrgb * tsrgb * tsrgb));
+            }
+        }
+    }
+    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+    for (int p = 0; p < kCrfParamCount; ++p) {
+        const double total = crf_wave_sum(acc[p]);
+        if (lane == 0) s_part[wave][p] = total;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCrfParamCount) {
+        double s = 0.0;
+        for (int v = 0; v < kCrfParamGradBlock / 64; ++v) s += s_part[v][threadIdx.x];
+        slots[(size_t)blockIdx.x * kCrfParamCount + threadIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_crf_tensor_param_grad_close(const double* __restrict__ slots, size_t blocks, float* __restrict__ out) {
+    if (threadIdx.x >= kCrfParamCount) return;
+    double s = 0.0;
+    for (size_t b = 0; b < blocks; ++b) s += slots[b * kCrfParamCount + threadIdx.x];
+    out[threadIdx.x] = (float)s;
+}
+
+void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
+                                   const float4* temporal, const CrfTensorTransposed& tr, const float* dm, const float* q_in,
+                                   float* grad_edge, float* grad_links, hipStream_t st) {
+    // one thread per neighbour entry (none without grad_edge), then one per (frame, node) for the links; below 2^32 because nnz and N * K are below 2^31
+    const uint32_t entries = grad_edge ? (uint32_t)dp.nnz : 0u;
+    const uint32_t n = entries + (grad_links && dp.temporal ? (uint32_t)dp.N * (uint32_t)dp.K : 0u);
+    if (n == 0) return;
+    const CrfGradLists L = {rows, edge, temporal, tr};
+    launch(k_crf_tensor_energy_grad, dim3((n + 255) / 256), dim3(256), 0, st, dp, L, indices, dm, q_in, grad_edge, grad_links, entries);
+}
+
+void launch_crf_tensor_param_grad(const CrfTensorParams& dp, const float* params, const float* yxrgb, const int64_t* offsets,
+                                  const int32_t* indices, const float* grad_edge, const float* grad_links, double* slots,
+                                  float* grad_params, hipStream_t st) {
+    const size_t blocks = crf_tensor_param_grad_blocks(dp.N, dp.K);
+    launch(k_crf_tensor_param_grad, dim3((unsigned)blocks), dim3(kCrfParamGradBlock), 0, st, dp, params, yxrgb, offsets, indices, grad_edge,
+           grad_links, slots);
+    launch(k_crf_tensor_param_grad_close, dim3(1), dim3(64), 0, st, (const double*)slots, blocks, grad_params);
 }
 
 void launch_crf_tensor_sweep_bwd(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,

@@ -420,7 +420,7 @@ int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K
  *   unaries     -> grad_unaries [N][C][K] (always),
  *   q0          -> grad_q0 [N][C][K]; NULL says that the forward had q0 == NULL, its start crf_expf(-unaries) then adds to grad_unaries,
  *   compat      -> grad_compat [C], or NULL: that pass is skipped.
- * Nothing flows to yxrgb, members, the graph or params.  One launch per sweep, last sweep first, gathers over the TRANSPOSED lists:
+ * Nothing flows to yxrgb, members or the graph (for params and the energies see the _energies entries below).  One launch per sweep, last sweep first, gathers over the TRANSPOSED lists:
  * t_offsets int64 [N * K + 1] over (frame, target node), and per transposed entry the neighbour entry t_entries int32 [nnz] and its
  * row t_rows int32 [nnz] over (frame, node), in ascending entry order inside one target (both NULL only with nnz == 0).  No float
  * atomics: every output cell has one owner and every sum a fixed order, so two calls give the same bits.  No transposed list of any
@@ -442,6 +442,53 @@ int fslic_hip_crf_tensor_backward(int device, void* stream, int N, int C, int K,
                                   const int64_t* t_offsets, const int32_t* t_entries, const int32_t* t_rows,
                                   const float* unaries, const float* q_all, const float* grad_q,
                                   float* grad_unaries, float* grad_q0, float* grad_compat, void* workspace, size_t workspace_bytes);
+
+/* ---- The energies of that inference as tensors (kernels in csrc/crf_tensor.hip, csrc/crf_tensor_grad.hip; Python: crf_edge_energies
+ * and the params tensor and energies arguments of superpixel_crf) ----
+ * fslic_hip_crf_tensor_energies writes what the inference above computes for itself: edge float [nnz], the spatial energy of every
+ * neighbour entry of the CSR (0.0 for a self-loop, for an index outside [0, K) and for an entry outside every clamped row), and links
+ * float [N][2][K], the temporal energy of node i of frame n towards n - 1 (links[n][0][i]) and n + 1 (links[n][1][i]), 0.0 where there
+ * is no such frame or temporal is 0.  params is DEVICE memory here: the seven floats of fslic_crf_params in its order; the values are
+ * the very floats of the inference with the same params.  edge may be NULL only with nnz == 0.
+ * fslic_hip_crf_tensor_energies_backward takes grad_edge [nnz] and grad_links [N][2][K], the gradients of a scalar with respect to
+ * those two (either may be NULL: zero), and writes its gradient with respect to the params, grad_params float [7]: every term in
+ * double, added in a fixed order (per row in entry order, a fixed tree per block of 256 rows, the blocks in ascending order), rounded
+ * once.  Self-loops and dead entries contribute nothing; nothing flows to yxrgb.  Its workspace (16-byte aligned) holds
+ * 56 ceil(N K / 256) bytes rounded up to 16.
+ * The three _energies entries are fslic_hip_crf_tensor_inference, _inference_saved and _backward with the energies given: edge [nnz]
+ * (NULL only with nnz == 0) and links [N][2][K] (NULL: no temporal energy) take the place of params and yxrgb; the weight of entry k
+ * is edge[k] times the member factor, also for a self-loop.  Workspaces are those of the entries they mirror
+ * (fslic_hip_crf_tensor_workspace_size, fslic_hip_crf_tensor_grad_workspace_size).  The backward also writes, when the pointer is
+ * given, grad_edge [nnz] and grad_links [N][2][K]: zeroed on the stream, then behind each sweep's adjoint one launch adds
+ *   grad_edge[k] += f_k sum_c dm[row(k)][c] q[j_k][c],   grad_links[n][0][i] += f sum_c dm[n][c][i] q[n - 1][c][i]   ([n][1][i]: n + 1)
+ * with dm the gradient of that sweep's messages, q its input iterate and f the member factor (no gradient flows through it); classes
+ * in ascending order, sweeps last to first, one owner thread per cell, no atomics.  An index outside [0, K), an entry outside every
+ * clamped row, the link cells at the window's ends and all of grad_links with temporal == 0 get 0.0. */
+int fslic_hip_crf_tensor_energies(int device, void* stream, int N, int K, int temporal, const float* params /* device, [7] */,
+                                  const float* yxrgb, const int32_t* members, const int64_t* offsets, const int32_t* indices,
+                                  long long nnz, float* edge, float* links);
+int fslic_hip_crf_tensor_energies_backward_workspace_size(int N, int K, size_t* bytes);
+int fslic_hip_crf_tensor_energies_backward(int device, void* stream, int N, int K, int temporal, const float* params /* device, [7] */,
+                                           const float* yxrgb, const int64_t* offsets, const int32_t* indices, long long nnz,
+                                           const float* grad_edge, const float* grad_links, float* grad_params,
+                                           void* workspace, size_t workspace_bytes);
+int fslic_hip_crf_tensor_inference_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                            const float* compat, const int32_t* members, const int64_t* offsets, const int32_t* indices,
+                                            long long nnz, const float* edge, const float* links,
+                                            const float* unaries, const float* q0 /* NULL: expf(-unaries) */, float* q_out,
+                                            void* workspace, size_t workspace_bytes);
+int fslic_hip_crf_tensor_inference_saved_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                                  const float* compat, const int32_t* members, const int64_t* offsets,
+                                                  const int32_t* indices, long long nnz, const float* edge, const float* links,
+                                                  const float* unaries, const float* q0 /* NULL: expf(-unaries) */, float* q_all,
+                                                  void* workspace, size_t workspace_bytes);
+int fslic_hip_crf_tensor_backward_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
+                                           const float* compat, const int32_t* members, const int64_t* offsets, const int32_t* indices,
+                                           long long nnz, const float* edge, const float* links,
+                                           const int64_t* t_offsets, const int32_t* t_entries, const int32_t* t_rows,
+                                           const float* unaries, const float* q_all, const float* grad_q,
+                                           float* grad_unaries, float* grad_q0, float* grad_compat, float* grad_edge, float* grad_links,
+                                           void* workspace, size_t workspace_bytes);
 
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
