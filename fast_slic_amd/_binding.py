@@ -45,6 +45,7 @@ EXPORTS = [
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
     "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
+    "fslic_hip_debug_lsc_state",
     # SimpleCRF (fast_slic_amd/crf.py)
     "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
     "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
@@ -140,6 +141,8 @@ def load_library():
         if hasattr(lib, "fslic_hip_enforce_connectivity_nodes"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
             lib.fslic_hip_enforce_connectivity_nodes.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_uint32)]
         lib.fslic_hip_last_prelabels.argtypes = [vp, i32, vp]
+        if hasattr(lib, "fslic_hip_debug_lsc_state"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
+            lib.fslic_hip_debug_lsc_state.argtypes = [vp, i32, i32, i32, vp, vp]
         lib.fslic_hip_last_timing_report.argtypes = [vp]
         lib.fslic_hip_last_timing_report.restype = C.c_char_p
         if hasattr(lib, "fslic_hip_last_recorder_report"):
@@ -428,6 +431,13 @@ class Engine(object):
         out = np.empty((H, W), np.uint16)
         _check(load_library().fslic_hip_last_prelabels(self._h, int(slot), out.ctypes.data))
         return out
+
+    def debug_lsc_state(self, K, z=0, slot=0):
+        """Debug entry (tests): frame z's LSC state of the last group on `slot` -- the ten feature means (float32[10]) and the K
+        feature-space centroids (float32[K, 10]; NaN rows: clusters without a member in the last update)."""
+        means, cfeat = np.empty(10, np.float32), np.empty((int(K), 10), np.float32)
+        _check(load_library().fslic_hip_debug_lsc_state(self._h, int(slot), int(z), int(K), means.ctypes.data, cfeat.ctypes.data))
+        return means, cfeat
 
     def last_timing_report(self):
         return load_library().fslic_hip_last_timing_report(self._h).decode("utf-8")

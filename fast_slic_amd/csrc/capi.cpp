@@ -241,6 +241,27 @@ int fslic_hip_last_prelabels(fslic_engine* e, int slot, uint16_t* prelabels) {
     return FSLIC_OK;
 }
 
+// Debug entry (tests only, read-only): frame z's feature means and feature-space centroids of the slot's last LSC group, from the
+// slot's LSC arena (a synchronous call has completed when it returns; the lease waits for an asynchronous group to be collected)
+int fslic_hip_debug_lsc_state(fslic_engine* e, int slot, int z, int K, float* means10, float* cfeat) {
+    if (!e || !means10 || !cfeat) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    if (slot < 0 || slot >= (int)e->slots.size()) return fail(FSLIC_E_INVALID, "slot out of range");
+    HIPCHK(hipSetDevice(e->device));
+    SlotLease lease(e);
+    int rc = lease.take(slot);
+    if (rc) return rc;
+    Slot& s = e->slots[slot];
+    if (!s.have_pre || s.keyH == 0 || s.p.variant != FSLIC_VARIANT_LSC) return fail(FSLIC_E_INVALID, "the slot's last group was not an LSC one");
+    if (z < 0 || z >= s.nframes) return fail(FSLIC_E_INVALID, "no such frame in the slot's last group");
+    if (K != s.K) return fail(FSLIC_E_INVALID, "K is not that of the slot's last group");
+    HIPCHK(hipStreamSynchronize(s.st));
+    LscDev l = s.l;
+    l.select(z);
+    HIPCHK(hipMemcpy(means10, l.means, sizeof(float) * kLscFeat, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(cfeat, sizeof(float) * kLscFeat, l.cfeat, sizeof(float) * kLscCfPitch, sizeof(float) * kLscFeat, (size_t)s.K, hipMemcpyDeviceToHost));
+    return FSLIC_OK;
+}
+
 // The report of the calling thread's last synchronous call or fslic_hip_wait_group (thread-local, like the reference's
 // timer, src/timer.cpp:45); the engine argument is kept for the shape of the reference interface.
 const char* fslic_hip_last_timing_report(fslic_engine* e) { return e ? thread_timing_report().c_str() : ""; }

@@ -533,6 +533,14 @@ static __device__ __forceinline__ void lsc_assign_body(FrameDev& f, LscDev& l, i
         // labels out; with an update following (stale_sums), also the label each visited pixel carries into update(): the new
         // one, or the one it keeps when nothing accepted it (src/lsc.cpp:217-220 never touches such a pixel; 0xFFFF: none yet)
         uint32_t lbl[2], slot[2];
+        // REC: the recorder wants the distance itself, sum (G - C)^2 (src/lsc.cpp:212-215).  A listed candidate's `best` is the part of it
+        // that differs between candidates; |G - O|^2, the same for all of them, is added here (the walk over every cluster subtracts and
+        // squares: its `best` is complete).  Until tests/test_gpu_lsc_stages.py compared them, the recorded min-dists lacked this term.
+        f2 gn2 = {0.0f, 0.0f};
+        if (REC && listed) {
+#pragma unroll
+            for (int q = 0; q < kLscFeat; ++q) gn2 = __builtin_elementwise_fma(G[q], G[q], gn2);
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int r = 2 * h + u;
@@ -540,7 +548,7 @@ static __device__ __forceinline__ void lsc_assign_body(FrameDev& f, LscDev& l, i
             if (!xok || vw + r >= Hv) continue;
             const uint32_t bk = u ? bk1 : bk0;
             const size_t p = (size_t)yr[r] * W + x;
-            if (REC) dist[p] = best[u];
+            if (REC) dist[p] = best[u] < FLT_MAX ? best[u] + gn2[u] : best[u];
             if (best[u] < FLT_MAX) {
                 lbl[u] = listed ? s_k[bk] : bk;
                 st_stream(f.labels + p, (uint16_t)lbl[u]);

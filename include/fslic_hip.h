@@ -198,6 +198,12 @@ int fslic_hip_cluster_density_to_mask(fslic_engine* e, int H, int W, int K, cons
  * src/context.cpp:182-190) of the last fslic_hip_iterate*() call on `slot`; host pointer, H*W. */
 int fslic_hip_last_prelabels(fslic_engine* e, int slot, uint16_t* prelabels);
 
+/* Debug entry, for tests only (read-only): the LSC state of frame `z` of the last group on `slot`, read back once the slot is idle --
+ * the ten feature means (src/lsc.cpp:143-149) into means10[10] and the K feature-space centroids as they stand behind the last update
+ * (the seed centroids with max_iter = 0) into cfeat[K * 10], ten floats per cluster, NaN for a cluster without a member.  Host
+ * pointers.  FSLIC_E_INVALID when the slot's last group was not of FSLIC_VARIANT_LSC, `z` is not one of its frames or K is not its K. */
+int fslic_hip_debug_lsc_state(fslic_engine* e, int slot, int z, int K, float* means10, float* cfeat);
+
 /* Replaces BaseContext::get_timing_report (src/context.h:74): JSON with the fstimer schema
  * {"name","duration"(us),"children"} (src/timer.cpp:4-18), durations from HIP events of the CALLING THREAD's last
  * fslic_hip_iterate* / fslic_hip_wait_group (thread-local like the reference's timer, src/timer.cpp:45).  Pointer
