@@ -60,6 +60,8 @@ EXPORTS = [
     "fslic_hip_pool_workspace_size", "fslic_hip_pool", "fslic_hip_pool_finalize", "fslic_hip_unpool",
     # region adjacency graph (fast_slic_amd/rag.py)
     "fslic_hip_rag_workspace_size", "fslic_hip_rag_accumulate", "fslic_hip_rag_compact",
+    # two label maps against each other (fast_slic_amd/compare.py)
+    "fslic_hip_overlap_workspace_size", "fslic_hip_overlap_accumulate", "fslic_hip_overlap_compact", "fslic_hip_boundary_match",
     # SimpleCRF inference on torch tensors (fast_slic_amd/crf_torch.py)
     "fslic_hip_crf_tensor_workspace_size", "fslic_hip_crf_tensor_inference",
     "fslic_hip_crf_tensor_grad_workspace_size", "fslic_hip_crf_tensor_inference_saved", "fslic_hip_crf_tensor_backward",
@@ -167,6 +169,8 @@ def load_library():
             _declare_pool(lib)
         if hasattr(lib, "fslic_hip_rag_accumulate"):
             _declare_rag(lib)
+        if hasattr(lib, "fslic_hip_overlap_accumulate"):
+            _declare_compare(lib)
         if hasattr(lib, "fslic_hip_crf_tensor_inference"):
             _declare_crf_tensor(lib)
         _lib = lib
@@ -215,6 +219,17 @@ def _declare_rag(lib):
     lib.fslic_hip_rag_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
     lib.fslic_hip_rag_compact.argtypes = [i32, vp, i32, i32, i64, vp, sz, vp, vp, vp, i64]
     for name in ("rag_workspace_size", "rag_accumulate", "rag_compact"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
+
+
+def _declare_compare(lib):
+    """Signatures of the entry points that compare two label maps (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    lib.fslic_hip_overlap_workspace_size.argtypes = [i32, i64, C.POINTER(sz)]
+    lib.fslic_hip_overlap_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
+    lib.fslic_hip_overlap_compact.argtypes = [i32, vp, i32, i64, vp, sz, vp, vp, i64]
+    lib.fslic_hip_boundary_match.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
+    for name in ("overlap_workspace_size", "overlap_accumulate", "overlap_compact", "boundary_match"):
         getattr(lib, "fslic_hip_" + name).restype = i32
 
 

@@ -395,6 +395,35 @@ int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int 
 int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capacity, void* workspace, size_t workspace_bytes,
                           int64_t* keys, int32_t* boundary, int64_t* contrast, long long max_edges);
 
+/* ---- Two label maps against each other (NEW surface, no counterpart in the reference; Python: fast_slic_amd/compare.py) ----
+ * The overlap table: every pair (a, b) = (labels[p], other[p]) that shares a pixel, with the number of its pixels.  A pixel takes part
+ * when 0 <= labels[p] < K and 0 <= other[p] < M, decided on the value at its own width; K and M in [1, 65534].  Entries as for the
+ * graph: a device index and a stream, no synchronisation, no allocation, the caller's device restored, every argument checked before
+ * the first HIP call (FSLIC_E_INVALID).
+ *   labels, other : [N][H][W] of label_type / other_type (FSLIC_LABEL_*, they may differ), H * W < 2^31
+ * Pairs are collected per frame in an open-addressing table of `capacity` slots (a power of two in [64, 2^31]); the workspace holds a
+ * header of 16 + 4 N bytes (rounded up to 16) and N * capacity * 8 bytes of tables: uint32 keys [N][capacity], (a << 16 | b) + 1 and 0
+ * for an empty slot, then uint32 pixels [N][capacity].  Header: uint32 overflow flag, uint32 unused, uint64 used by compact, then
+ * uint32 [N]: the distinct pairs of each frame.  The flag is set when a frame's table got more than half full or a probe run exceeded
+ * its bound; the tables are then incomplete and the caller starts over with a larger capacity (2 * min(K M, H W) pairs rounded up to
+ * a power of two always suffice for the load).  All integer arithmetic: the result does not depend on the capacity or on the order
+ * of execution. */
+int fslic_hip_overlap_workspace_size(int N, long long capacity, size_t* bytes);
+/* Clears the workspace, then fills the tables and the header. */
+int fslic_hip_overlap_accumulate(int device, void* stream, int N, int H, int W, int K, int M, const void* labels, int label_type,
+                                 const void* other, int other_type, long long capacity, void* workspace, size_t workspace_bytes);
+/* The occupied slots of the workspace of a completed fslic_hip_overlap_accumulate (same stream, same N, capacity), densely and in NO
+ * specified order: keys[i] = frame << 32 | a << 16 | b, count[i] its pixels.  At most max_pairs rows are written (the sum of the
+ * header's counts is what there is). */
+int fslic_hip_overlap_compact(int device, void* stream, int N, long long capacity, void* workspace, size_t workspace_bytes,
+                              int64_t* keys, int32_t* count, long long max_pairs);
+/* The boundary match.  A boundary pixel of a map is one whose value differs from its right or its lower neighbour's, where the image
+ * has that neighbour (values compared as stored: no K).  counts[n] = { boundary pixels of other[n] that have a boundary pixel of
+ * labels[n] within Chebyshev distance `tolerance` (0 .. 15), boundary pixels of other[n], boundary pixels of labels[n] }.  Clears
+ * counts (int64 [N][3], device memory), then adds into it with integer atomics: exact whatever the order.  No workspace. */
+int fslic_hip_boundary_match(int device, void* stream, int N, int H, int W, const void* labels, int label_type,
+                             const void* other, int other_type, int tolerance, int64_t* counts);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
