@@ -44,11 +44,28 @@ DEFAULT_PARAMS = dict(spatial_w=10.0, temporal_w=10.0, spatial_srgb=13.0, tempor
 _LIMIT = 1 << 31
 
 
-def _lib():
+def _lib(entry="fslic_hip_crf_tensor_inference", what="entry points"):
     lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_crf_tensor_inference"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor entry points; rebuild it")
+    if not hasattr(lib, entry):
+        raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor %s; rebuild it" % what)
     return lib
+
+
+def _lib_energies():
+    _lib()
+    return _lib("fslic_hip_crf_tensor_backward_energies", "energies entry points")
+
+
+def _ptr(t, cond=True):
+    """The device pointer of `t`; None (NULL) without a tensor or where `cond` does not hold."""
+    return t.data_ptr() if t is not None and cond else None
+
+
+def _scratch(dev, size_entry, *sizes):
+    """Scratch memory from torch's caching allocator, as many bytes as the library's `size_entry` asks for `sizes`."""
+    nbytes = C.c_size_t()
+    B._check(size_entry(*sizes, C.byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
 
 
 # ---- argument checks: all of them run before any device work ----
@@ -163,10 +180,72 @@ def transpose_batch_csr(offsets, indices, N, K):
     return t_offsets, entry.to(torch.int32), row[entry].to(torch.int32)
 
 
-def _workspace(lib, dev, N, Cn, K, nnz, backward, with_compat):
-    nbytes = C.c_size_t()
-    B._check(lib.fslic_hip_crf_tensor_grad_workspace_size(N, Cn, K, nnz, int(backward), int(with_compat), C.byref(nbytes)))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value
+class _Call(object):
+    """What every sweep entry of the library is given, from contiguous tensors on one GPU."""
+
+    def __init__(self, un, comp, mem, offsets, indices, N, max_iter, temporal):
+        self.un, self.comp, self.mem, self.offsets, self.indices = un, comp, mem, offsets, indices
+        self.N, self.max_iter, self.temporal = N, max_iter, temporal
+        self.dev = un.device
+        self.Cn, self.K = (int(v) for v in un.shape[-2:])
+        self.nnz = int(indices.shape[0])
+
+    def _head(self):
+        return (self.dev.index, _stream(self.dev), self.N, self.Cn, self.K, int(self.temporal), self.max_iter)
+
+    def _graph(self):
+        return (_ptr(self.mem), _ptr(self.offsets), _ptr(self.indices, self.nnz), self.nnz)
+
+    def from_params(self, p, yx):
+        """The arguments up to nnz of an entry that computes the energies from host params and yxrgb."""
+        return self._head() + (C.byref(p), _ptr(self.comp), _ptr(yx)) + self._graph()
+
+    def from_energies(self, edge, links):
+        """The arguments up to links of an _energies entry."""
+        return self._head() + (_ptr(self.comp),) + self._graph() + (_ptr(edge, self.nnz), _ptr(links))
+
+    def run(self, entry, lead, own, size_entry, *flags):
+        """entry(*lead, *own, workspace, bytes) with as much workspace as size_entry(N, C, K, nnz, *flags) asks for."""
+        ws = _scratch(self.dev, size_entry, self.N, self.Cn, self.K, self.nnz, *flags)
+        B._check(entry(*lead, *own, ws.data_ptr(), ws.numel()))
+
+
+def _plain(lib, entry, call, lead, start):
+    """The call outside autograd -> q."""
+    q = torch.empty_like(call.un)
+    call.run(entry, lead, (_ptr(call.un), _ptr(start), _ptr(q)), lib.fslic_hip_crf_tensor_workspace_size)
+    return q
+
+
+def _saved_forward(ctx, lib, entry, call, lead, start, kept):
+    """The sweeps with every iterate kept -> q, a view of them.  `kept`: the energy source's tensors, saved behind the call's."""
+    with torch.cuda.device(call.dev):
+        q_all = torch.empty((call.max_iter + 1,) + tuple(call.un.shape), dtype=torch.float32, device=call.dev)
+        call.run(entry, lead, (_ptr(call.un), _ptr(start), _ptr(q_all)), lib.fslic_hip_crf_tensor_grad_workspace_size, 0, 0)
+    ctx.save_for_backward(call.un, call.comp, call.mem, call.offsets, call.indices, q_all, *kept)
+    ctx.call = (call.N, call.max_iter, call.temporal, start is not None)
+    return q_all[call.max_iter]
+
+
+def _saved_call(ctx):
+    """What _saved_forward kept -> (the call, q_all, whether q0 was given, the energy source's tensors)."""
+    N, max_iter, temporal, has_q0 = ctx.call
+    return _Call(*ctx.saved_tensors[:5], N, max_iter, temporal), ctx.saved_tensors[5], has_q0, ctx.saved_tensors[6:]
+
+
+def _saved_backward(lib, entry, call, lead, q_all, has_q0, with_compat, g, energy_grads=()):
+    """The adjoint of _saved_forward -> (du, dq0, dcompat).  `energy_grads`: the pointers that follow dcompat's in the entry."""
+    un, nnz = call.un, call.nnz
+    with torch.cuda.device(call.dev):
+        g = g.contiguous()
+        t_offsets, t_entries, t_rows = transpose_batch_csr(call.offsets, call.indices, call.N, call.K)
+        du = torch.empty_like(un)
+        dq0 = torch.empty_like(un) if has_q0 else None
+        dcompat = torch.empty_like(call.comp) if with_compat else None
+        own = (_ptr(t_offsets), _ptr(t_entries, nnz), _ptr(t_rows, nnz), _ptr(un), _ptr(q_all), _ptr(g), _ptr(du), _ptr(dq0),
+               _ptr(dcompat)) + tuple(energy_grads)
+        call.run(entry, lead, own, lib.fslic_hip_crf_tensor_grad_workspace_size, 1, int(with_compat))
+    return du, dq0, dcompat
 
 
 class _SuperpixelCRF(torch.autograd.Function):
@@ -174,46 +253,18 @@ class _SuperpixelCRF(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, un, start, comp, yx, mem, offsets, indices, N, max_iter, temporal, p):
-        lib, dev = _lib(), un.device
-        if not hasattr(lib, "fslic_hip_crf_tensor_backward"):
-            raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor backward; rebuild it")
-        Cn, K = (int(v) for v in un.shape[-2:])
-        nnz = int(indices.shape[0])
-        with torch.cuda.device(dev):
-            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, False, False)
-            q_all = torch.empty((max_iter + 1,) + tuple(un.shape), dtype=torch.float32, device=dev)
-            B._check(lib.fslic_hip_crf_tensor_inference_saved(dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, C.byref(p),
-                                                              comp.data_ptr(), yx.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
-                                                              indices.data_ptr() if nnz else None, nnz, un.data_ptr(),
-                                                              start.data_ptr() if start is not None else None, q_all.data_ptr(),
-                                                              ws.data_ptr(), nbytes))
-        ctx.save_for_backward(un, comp, yx, mem, offsets, indices, q_all)
-        ctx.call = (N, max_iter, temporal, p, start is not None)
-        return q_all[max_iter]
+        lib = _lib("fslic_hip_crf_tensor_backward", "backward")
+        call = _Call(un, comp, mem, offsets, indices, N, max_iter, temporal)
+        ctx.p = p
+        return _saved_forward(ctx, lib, lib.fslic_hip_crf_tensor_inference_saved, call, call.from_params(p, yx), start, (yx,))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        un, comp, yx, mem, offsets, indices, q_all = ctx.saved_tensors
-        N, max_iter, temporal, p, has_q0 = ctx.call
-        lib, dev = _lib(), un.device
-        Cn, K = (int(v) for v in un.shape[-2:])
-        nnz = int(indices.shape[0])
-        with torch.cuda.device(dev):
-            g = g.contiguous()
-            t_offsets, t_entries, t_rows = transpose_batch_csr(offsets, indices, N, K)
-            du = torch.empty_like(un)
-            dq0 = torch.empty_like(un) if has_q0 else None
-            dcompat = torch.empty_like(comp) if ctx.needs_input_grad[2] else None
-            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, True, dcompat is not None)
-            B._check(lib.fslic_hip_crf_tensor_backward(dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, C.byref(p),
-                                                       comp.data_ptr(), yx.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
-                                                       indices.data_ptr() if nnz else None, nnz, t_offsets.data_ptr(),
-                                                       t_entries.data_ptr() if nnz else None, t_rows.data_ptr() if nnz else None,
-                                                       un.data_ptr(), q_all.data_ptr(), g.data_ptr(), du.data_ptr(),
-                                                       dq0.data_ptr() if has_q0 else None,
-                                                       dcompat.data_ptr() if dcompat is not None else None, ws.data_ptr(), nbytes))
-        return du, dq0, dcompat, None, None, None, None, None, None, None, None
+        lib = _lib()
+        call, q_all, has_q0, (yx,) = _saved_call(ctx)
+        return _saved_backward(lib, lib.fslic_hip_crf_tensor_backward, call, call.from_params(ctx.p, yx), q_all, has_q0,
+                               ctx.needs_input_grad[2], g) + (None,) * 8
 
 
 class _SuperpixelCRFEnergies(torch.autograd.Function):
@@ -221,53 +272,22 @@ class _SuperpixelCRFEnergies(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal):
-        lib, dev = _lib_energies(), un.device
-        Cn, K = (int(v) for v in un.shape[-2:])
-        nnz = int(indices.shape[0])
-        with torch.cuda.device(dev):
-            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, False, False)
-            q_all = torch.empty((max_iter + 1,) + tuple(un.shape), dtype=torch.float32, device=dev)
-            B._check(lib.fslic_hip_crf_tensor_inference_saved_energies(
-                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
-                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if links is not None else None,
-                un.data_ptr(), start.data_ptr() if start is not None else None, q_all.data_ptr(), ws.data_ptr(), nbytes))
-        ctx.save_for_backward(un, comp, edge, mem, offsets, indices, q_all, *(() if links is None else (links,)))
-        ctx.call = (N, max_iter, temporal, start is not None, links is not None)
-        return q_all[max_iter]
+        lib = _lib_energies()
+        call = _Call(un, comp, mem, offsets, indices, N, max_iter, temporal)
+        return _saved_forward(ctx, lib, lib.fslic_hip_crf_tensor_inference_saved_energies, call, call.from_energies(edge, links), start,
+                              (edge,) if links is None else (edge, links))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        un, comp, edge, mem, offsets, indices, q_all = ctx.saved_tensors[:7]
-        N, max_iter, temporal, has_q0, has_links = ctx.call
-        links = ctx.saved_tensors[7] if has_links else None
-        lib, dev = _lib_energies(), un.device
-        Cn, K = (int(v) for v in un.shape[-2:])
-        nnz = int(indices.shape[0])
-        with torch.cuda.device(dev):
-            g = g.contiguous()
-            t_offsets, t_entries, t_rows = transpose_batch_csr(offsets, indices, N, K)
-            du = torch.empty_like(un)
-            dq0 = torch.empty_like(un) if has_q0 else None
-            dcompat = torch.empty_like(comp) if ctx.needs_input_grad[2] else None
-            dedge = torch.empty_like(edge) if ctx.needs_input_grad[3] else None
-            dlinks = torch.empty_like(links) if has_links and ctx.needs_input_grad[4] else None
-            ws, nbytes = _workspace(lib, dev, N, Cn, K, nnz, True, dcompat is not None)
-            B._check(lib.fslic_hip_crf_tensor_backward_energies(
-                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
-                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if has_links else None,
-                t_offsets.data_ptr(), t_entries.data_ptr() if nnz else None, t_rows.data_ptr() if nnz else None, un.data_ptr(),
-                q_all.data_ptr(), g.data_ptr(), du.data_ptr(), dq0.data_ptr() if has_q0 else None,
-                dcompat.data_ptr() if dcompat is not None else None, dedge.data_ptr() if dedge is not None and nnz else None,
-                dlinks.data_ptr() if dlinks is not None else None, ws.data_ptr(), nbytes))
-        return du, dq0, dcompat, dedge, dlinks, None, None, None, None, None, None
-
-
-def _lib_energies():
-    lib = _lib()
-    if not hasattr(lib, "fslic_hip_crf_tensor_backward_energies"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor energies entry points; rebuild it")
-    return lib
+        lib = _lib_energies()
+        call, q_all, has_q0, kept = _saved_call(ctx)
+        edge, links = (kept + (None,))[:2]
+        dedge = torch.empty_like(edge) if ctx.needs_input_grad[3] else None
+        dlinks = torch.empty_like(links) if links is not None and ctx.needs_input_grad[4] else None
+        grads = _saved_backward(lib, lib.fslic_hip_crf_tensor_backward_energies, call, call.from_energies(edge, links), q_all, has_q0,
+                                ctx.needs_input_grad[2], g, (_ptr(dedge, call.nnz), _ptr(dlinks)))
+        return grads + (dedge, dlinks) + (None,) * 6
 
 
 def _energies_raw(theta, yx, mem, offsets, indices, N, K, temporal):
@@ -277,9 +297,8 @@ def _energies_raw(theta, yx, mem, offsets, indices, N, K, temporal):
     with torch.cuda.device(dev):
         edge = torch.empty(nnz, dtype=torch.float32, device=dev)
         links = torch.empty((N, 2, K), dtype=torch.float32, device=dev)
-        B._check(lib.fslic_hip_crf_tensor_energies(dev.index, _stream(dev), N, K, int(temporal), theta.data_ptr(), yx.data_ptr(),
-                                                   mem.data_ptr(), offsets.data_ptr(), indices.data_ptr() if nnz else None, nnz,
-                                                   edge.data_ptr() if nnz else None, links.data_ptr()))
+        B._check(lib.fslic_hip_crf_tensor_energies(dev.index, _stream(dev), N, K, int(temporal), _ptr(theta), _ptr(yx), _ptr(mem),
+                                                   _ptr(offsets), _ptr(indices, nnz), nnz, _ptr(edge, nnz), _ptr(links)))
     return edge, links
 
 
@@ -303,14 +322,11 @@ class _EdgeEnergies(torch.autograd.Function):
         with torch.cuda.device(dev):
             g_edge = g_edge.contiguous() if g_edge is not None and nnz else None
             g_links = g_links.contiguous() if g_links is not None else None
-            nbytes = C.c_size_t()
-            B._check(lib.fslic_hip_crf_tensor_energies_backward_workspace_size(N, K, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            ws = _scratch(dev, lib.fslic_hip_crf_tensor_energies_backward_workspace_size, N, K)
             dtheta = torch.empty_like(theta)
             B._check(lib.fslic_hip_crf_tensor_energies_backward(
-                dev.index, _stream(dev), N, K, int(temporal), theta.data_ptr(), yx.data_ptr(), offsets.data_ptr(),
-                indices.data_ptr() if nnz else None, nnz, g_edge.data_ptr() if g_edge is not None else None,
-                g_links.data_ptr() if g_links is not None else None, dtheta.data_ptr(), ws.data_ptr(), nbytes.value))
+                dev.index, _stream(dev), N, K, int(temporal), _ptr(theta), _ptr(yx), _ptr(offsets), _ptr(indices, nnz), nnz, _ptr(g_edge),
+                _ptr(g_links), _ptr(dtheta), ws.data_ptr(), ws.numel()))
         return dtheta, None, None, None, None, None, None, None
 
 
@@ -332,12 +348,15 @@ def _batch_csr(graph):
     return graph[0].contiguous(), graph[1].contiguous()
 
 
-def _check_same_device(dev, named):
-    for what, t in named:
+def _check_same_device(dev, owner, graph, named):
+    """Every tensor of `named` and of the graph is on the GPU `dev`, which is `owner`'s."""
+    on_graph = (("graph.edge_index", graph.edge_index), ("graph.offsets", graph.offsets)) if isinstance(graph, SuperpixelGraph) \
+        else (("graph offsets", graph[0]), ("graph indices", graph[1]))
+    for what, t in named + on_graph:
         if isinstance(t, torch.Tensor):
             _check_device(t, what)
             if t.device != dev:
-                raise ValueError("%s must be on the unaries' GPU %s, got %s" % (what, dev, t.device))
+                raise ValueError("%s must be on %s GPU %s, got %s" % (what, owner, dev, t.device))
 
 
 def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
@@ -370,13 +389,7 @@ def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
         raise ValueError("N * K + 1 and the number of neighbour entries must be below 2^31")
     _check_device(yxrgb, "yxrgb")
     dev = yxrgb.device
-    on_graph = (("graph.edge_index", graph.edge_index), ("graph.offsets", graph.offsets)) if isinstance(graph, SuperpixelGraph) \
-        else (("graph offsets", graph[0]), ("graph indices", graph[1]))
-    for what, t in (("members", members), ("params", params)) + on_graph:
-        if isinstance(t, torch.Tensor):
-            _check_device(t, what)
-            if t.device != dev:
-                raise ValueError("%s must be on yxrgb's GPU %s, got %s" % (what, dev, t.device))
+    _check_same_device(dev, "yxrgb's", graph, (("members", members), ("params", params)))
     with torch.cuda.device(dev):
         offsets, indices = _batch_csr(graph)
         theta = params if isinstance(params, torch.Tensor) else _params_on(params, dev)
@@ -445,10 +458,8 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
         raise ValueError("N * C * K, N * K + 1 and the number of neighbour entries must be below 2^31")
     _check_device(unaries, "unaries")
     dev = unaries.device
-    on_graph = (("graph.edge_index", graph.edge_index), ("graph.offsets", graph.offsets)) if isinstance(graph, SuperpixelGraph) \
-        else (("graph offsets", graph[0]), ("graph indices", graph[1]))
-    _check_same_device(dev, (("yxrgb", yxrgb), ("members", members), ("q0", q0), ("compat", compat), ("params", params),
-                             ("energies: edge", edge), ("energies: links", links)) + on_graph)
+    _check_same_device(dev, "the unaries'", graph, (("yxrgb", yxrgb), ("members", members), ("q0", q0), ("compat", compat),
+                                                    ("params", params), ("energies: edge", edge), ("energies: links", links)))
 
     lib = _lib()
     with torch.cuda.device(dev):
@@ -459,32 +470,21 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
             compat = torch.tensor(compat, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
         un, mem, comp = unaries.contiguous(), members.contiguous(), compat.contiguous()
         start = q0.contiguous() if q0 is not None else None
-        if p is None:
-            if energies is None:         # the composition: the energies from the params on the device, then the sweeps on them
-                edge, links = _energies(params, yxrgb.contiguous(), mem, offsets, indices, N, K, temporal)
-            edge = edge.contiguous()
-            links = links.contiguous().view(N, 2, K) if links is not None else None
-            if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unaries, q0, compat, edge, links)):
-                return _SuperpixelCRFEnergies.apply(un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal)
-            lib = _lib_energies()
-            nbytes = C.c_size_t()
-            B._check(lib.fslic_hip_crf_tensor_workspace_size(N, Cn, K, nnz, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            q = torch.empty(tuple(unaries.shape), dtype=torch.float32, device=dev)
-            B._check(lib.fslic_hip_crf_tensor_inference_energies(
-                dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, comp.data_ptr(), mem.data_ptr(), offsets.data_ptr(),
-                indices.data_ptr() if nnz else None, nnz, edge.data_ptr() if nnz else None, links.data_ptr() if links is not None else None,
-                un.data_ptr(), start.data_ptr() if start is not None else None, q.data_ptr(), ws.data_ptr(), nbytes.value))
-            return q
-        yx = yxrgb.contiguous()
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (unaries, q0, compat)):
-            return _SuperpixelCRF.apply(un, start, comp, yx.detach(), mem, offsets, indices, N, max_iter, temporal, p)
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_crf_tensor_workspace_size(N, Cn, K, nnz, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        q = torch.empty(tuple(unaries.shape), dtype=torch.float32, device=dev)
-        B._check(lib.fslic_hip_crf_tensor_inference(dev.index, _stream(dev), N, Cn, K, int(temporal), max_iter, C.byref(p), comp.data_ptr(),
-                                                    yx.data_ptr(), mem.data_ptr(), offsets.data_ptr(), indices.data_ptr() if nnz else None,
-                                                    nnz, un.data_ptr(), start.data_ptr() if start is not None else None, q.data_ptr(),
-                                                    ws.data_ptr(), nbytes.value))
-    return q
+
+        def wants_grad(*tensors):
+            return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+        call = _Call(un, comp, mem, offsets, indices, N, max_iter, temporal)
+        if p is not None:
+            yx = yxrgb.contiguous()
+            if wants_grad(unaries, q0, compat):
+                return _SuperpixelCRF.apply(un, start, comp, yx.detach(), mem, offsets, indices, N, max_iter, temporal, p)
+            return _plain(lib, lib.fslic_hip_crf_tensor_inference, call, call.from_params(p, yx), start)
+        if energies is None:             # the composition: the energies from the params on the device, then the sweeps on them
+            edge, links = _energies(params, yxrgb.contiguous(), mem, offsets, indices, N, K, temporal)
+        edge = edge.contiguous()
+        links = links.contiguous().view(N, 2, K) if links is not None else None
+        if wants_grad(unaries, q0, compat, edge, links):
+            return _SuperpixelCRFEnergies.apply(un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal)
+        lib = _lib_energies()
+        return _plain(lib, lib.fslic_hip_crf_tensor_inference_energies, call, call.from_energies(edge, links), start)

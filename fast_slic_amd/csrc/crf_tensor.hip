@@ -15,8 +15,7 @@
 //                       between the sums and the in-place division.
 // Every grid is exact (one trip): blocks of 256 over N * C * K (start) and N * K (edges), N * ceil(K / 64) blocks (sweep); all of
 // them are below 2^31 because N * C * K and N * K are.
-#include "crf.h"
-#include "crf_tensor.h"
+#include "crf_tensor_sweep.h"
 
 // The roundings are crf.hip's (see there and crf.h): products fused exactly where the reference build fuses them, nothing else.
 #pragma clang fp contract(off)
@@ -75,13 +74,10 @@ __global__ __launch_bounds__(256) void k_crf_tensor_edges(CrfTensorParams dp, co
         return c;
     };
     const fslic_cluster ci = cluster(0, i);
-    // whatever the offsets hold, 0 <= k0 <= k1 <= nnz: idx[k] and edge[k] are touched for k0 <= k < k1 only, here and in the sweep
-    long long k0 = offsets[g], k1 = offsets[g + 1];
-    k0 = k0 < 0 ? 0 : (k0 > dp.nnz ? dp.nnz : k0);
-    k1 = k1 < 0 ? 0 : (k1 > dp.nnz ? dp.nnz : k1);
-    if (k1 < k0) k1 = k0;
-    if (MODE != kCrfEdgesOut) rows[g] = make_uint2((uint32_t)k0, (uint32_t)k1);
-    for (uint32_t k = (uint32_t)k0; k < (uint32_t)k1; ++k) {
+    // idx[k] and edge[k] are touched for r.x <= k < r.y only, here and in the sweep
+    const uint2 r = crf_clamped_bounds(offsets, (size_t)g, dp.nnz);
+    if (MODE != kCrfEdgesOut) rows[g] = r;
+    for (uint32_t k = r.x; k < r.y; ++k) {
         const int32_t j = idx[k];
         if ((uint32_t)j >= (uint32_t)K) {              // contributes nothing, as pooling treats a label outside [0, K)
             if (MODE == kCrfEdgesOut) io.edge_out[k] = 0.0f;
@@ -115,63 +111,32 @@ __global__ __launch_bounds__(256) void k_crf_tensor_edges(CrfTensorParams dp, co
     }
 }
 
-// m[cls * stride] and ex[cls * stride] are the message and the exponential of (the thread's node, cls): LDS, or the workspace's
-// message plane and q_out itself above kCrfTensorLdsClasses classes.
+// The second plane holds the exponentials: LDS, or q_out itself above kCrfTensorLdsClasses classes (crf_tensor_sweep.h).
 template <bool LDS>
 __global__ __launch_bounds__(kCrfTensorNodes * kCrfTensorWaves) void k_crf_tensor_sweep(
-        CrfTensorParams dp, const uint2* __restrict__ rows, const int32_t* __restrict__ idx, const float2* __restrict__ edge,
-        const float4* __restrict__ temporal, const float* __restrict__ unary, const float* __restrict__ compat,
-        const float* __restrict__ q_in, float* q_out, float* msg) {
+        CrfTensorParams dp, CrfTensorLists L, const int32_t* __restrict__ idx, const float* __restrict__ unary,
+        const float* __restrict__ compat, const float* __restrict__ q_in, float* q_out, float* msg) {
     extern __shared__ float s_crf[];
     const int C = dp.C, K = dp.K;
-    const int tiles = (K + kCrfTensorNodes - 1) / kCrfTensorNodes;
-    const int w = blockIdx.x / tiles;                                          // the frame
-    const int lane = threadIdx.x % kCrfTensorNodes, wave = threadIdx.x / kCrfTensorNodes, waves = blockDim.x / kCrfTensorNodes;
-    const int i = (blockIdx.x - w * tiles) * kCrfTensorNodes + lane;           // the node
-    const bool live = i < K;                                                   // (a lane past the frame's end only keeps the barriers)
-    const size_t CK = (size_t)C * K, base = (size_t)w * CK;
-    float* m = LDS ? s_crf + lane : msg + base + i;
-    float* ex = LDS ? s_crf + (size_t)C * kCrfTensorNodes + lane : q_out + base + i;
-    const size_t stride = LDS ? (size_t)kCrfTensorNodes : (size_t)K;
-    const bool has_prev = dp.temporal && w > 0, has_next = dp.temporal && w < dp.N - 1;
+    const CrfSweepThread t = crf_sweep_thread<LDS>(dp, s_crf, msg, q_out);
 
-    // message passing (simple-crf.cpp:71-102): neighbours in list order, then t-1, then t+1; each term fma(e * q, factor, message)
-    if (live) {
-        const uint2 r = rows[(size_t)w * K + i];
-        const float4 t = temporal[(size_t)w * K + i];
-        for (int cls = wave; cls < C; cls += waves) {
-            const float* qc = q_in + base + (size_t)cls * K;
-            float message = 0.0f;
-            for (uint32_t k = r.x; k < r.y; ++k) {
-                const float2 es = edge[k];
-                if (es.y == kCrfDeadEntry) continue;                           // idx[k] is outside [0, K)
-                message = __builtin_fmaf(es.x * qc[idx[k]], es.y, message);
-            }
-            if (has_prev) message = __builtin_fmaf(t.x * qc[i - (ptrdiff_t)CK], t.y, message);
-            if (has_next) message = __builtin_fmaf(t.z * qc[i + CK], t.w, message);
-            m[cls * stride] = message;
-        }
+    if (t.live) {
+        const uint2 r = L.rows[(size_t)t.w * K + t.i];
+        const float4 tl = L.temporal[(size_t)t.w * K + t.i];
+        for (int cls = t.wave; cls < C; cls += t.waves) t.m[cls * t.stride] = crf_sweep_message(t, K, r, tl, idx, L.edge, q_in, cls);
     }
     __syncthreads();
-    // compatibility transform (:104-114): the Potts sum over the other classes in ascending order (fused), then expf
-    if (live) {
-        for (int cls = wave; cls < C; cls += waves) {
-            float gathered = 0.0f;
-            for (int o = 0; o < cls; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
-            for (int o = cls + 1; o < C; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
-            ex[cls * stride] = crf_expf(-(unary[base + (size_t)cls * K + i] + gathered));
-        }
-    }
+    if (t.live)
+        for (int cls = t.wave; cls < C; cls += t.waves) t.x[cls * t.stride] = crf_sweep_exp(t, C, K, compat, unary, cls);
     __syncthreads();
-    // normalisation (:116-133): the sum over classes in ascending order from 0.0f, clamped at 1e-5 (a double comparison, as written there)
     float sum = 0.0f;
-    if (live) {
-        for (int cls = 0; cls < C; ++cls) sum += ex[cls * stride];
-        if ((double)sum < 1e-5) sum = (float)1e-5;
+    if (t.live) {
+        sum = crf_sweep_class_sum(t, C);
+        if (crf_sweep_clamps(sum)) sum = (float)1e-5;
     }
-    if (!LDS) __syncthreads();                                                 // ex is q_out: every sum is taken before a division lands
-    if (live)
-        for (int cls = wave; cls < C; cls += waves) q_out[base + (size_t)cls * K + i] = ex[cls * stride] / sum;
+    if (!LDS) __syncthreads();                                                 // x is q_out: every sum is taken before a division lands
+    if (t.live)
+        for (int cls = t.wave; cls < C; cls += t.waves) q_out[t.base + (size_t)cls * K + t.i] = t.x[cls * t.stride] / sum;
 }
 
 void launch_crf_tensor_start(const float* unaries, const float* q0, float* out, size_t n, hipStream_t st) {
@@ -204,17 +169,11 @@ void launch_crf_tensor_edges_given(const CrfTensorParams& dp, const float* edge_
            rows, edge, temporal, io);
 }
 
-void launch_crf_tensor_sweep(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
-                             const float4* temporal, const float* unaries, const float* compat, const float* q_in, float* q_out,
-                             float* msg, hipStream_t st) {
-    // the fewest equal class slices that fit kCrfTensorWaves wavefronts: 21 classes -> 11 waves of 2 classes (the last of 1)
-    const int per = (dp.C + kCrfTensorWaves - 1) / kCrfTensorWaves, waves = (dp.C + per - 1) / per;
-    const dim3 grid((unsigned)dp.N * (unsigned)((dp.K + kCrfTensorNodes - 1) / kCrfTensorNodes)), block(kCrfTensorNodes * waves);
-    if (dp.C <= kCrfTensorLdsClasses)
-        launch(k_crf_tensor_sweep<true>, grid, block, (unsigned)(2 * sizeof(float) * kCrfTensorNodes * dp.C), st,
-               dp, rows, indices, edge, temporal, unaries, compat, q_in, q_out, msg);
-    else
-        launch(k_crf_tensor_sweep<false>, grid, block, 0, st, dp, rows, indices, edge, temporal, unaries, compat, q_in, q_out, msg);
+void launch_crf_tensor_sweep(const CrfTensorParams& dp, const CrfTensorLists& lists, const int32_t* indices, const float* unaries,
+                             const float* compat, const float* q_in, float* q_out, float* msg, hipStream_t st) {
+    const CrfSweepShape sh = crf_tensor_sweep_shape(dp.N, dp.C, dp.K);
+    launch(sh.lds ? k_crf_tensor_sweep<true> : k_crf_tensor_sweep<false>, dim3(sh.grid), dim3(sh.block), sh.lds, st, dp, lists, indices,
+           unaries, compat, q_in, q_out, msg);
 }
 
 }  // namespace fslic

@@ -1,20 +1,5 @@
 // crf_tensor_grad.h -- the backward of SimpleCRF inference on device tensors (crf_tensor_grad.hip, crfapi.cpp).  Internal to the library.
-//
-// Workspace of one fslic_hip_crf_tensor_inference_saved call (backward == false) or one fslic_hip_crf_tensor_backward call
-// (backward == true); offsets from its start, every part 16-byte aligned.  The first three parts are crf_tensor.h's:
-//   rows[N * K]          uint2   -- the row bounds of (frame, node) after clamping: 0 <= x <= y <= nnz
-//   temporal[N * K]      float4  -- (energy, factor) towards t - 1 and t + 1
-//   edge[nnz]            float2  -- per neighbour entry (energy, factor); factor kCrfDeadEntry: the index is outside [0, K)
-//   msg[N * C * K]       float   -- the messages, only for C > kCrfTensorLdsClasses
-// and for the backward alone:
-//   dm[2][N * C * K]     float   -- the gradient with respect to the messages, ping-pong: sweep `it` writes dm[it & 1] and gathers
-//                                   from dm[(it + 1) & 1]
-//   x[N * C * K]         float   -- exponentials, then G' q', then da, only for C > kCrfTensorLdsClasses
-//   slots[blocks][C]     float   -- per block of the sweep its part of the gradient of compat, blocks = N * ceil(K / 64); only
-//                                   when that gradient is asked for
-// With given energies (fslic_hip_crf_tensor_*_energies) the layout is the same: rows, temporal and edge are filled from the caller's
-// edge [nnz] and links [N][2][K] with the member factors and dead flags computed on the device; the gradients of the energies go to
-// caller tensors and need no part of their own.
+// The workspace of a backward call is crf_tensor.h's.
 //
 // Workspace of one fslic_hip_crf_tensor_energies_backward call:
 //   slots[blocks][7]     double  -- per block of 256 (frame, node) threads its part of the gradient of the seven params,
@@ -23,26 +8,6 @@
 #include "crf_tensor.h"
 
 namespace fslic {
-
-struct CrfTensorGradWorkspace {
-    size_t rows, temporal, edge, msg, dm, x, slots, bytes;
-};
-inline size_t crf_tensor_grad_blocks(int N, int K) { return (size_t)N * (size_t)((K + kCrfTensorNodes - 1) / kCrfTensorNodes); }
-inline CrfTensorGradWorkspace crf_tensor_grad_workspace(int N, int C, int K, long long nnz, bool backward, bool with_compat) {
-    const auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t n = (size_t)N * (size_t)K, cells = n * (size_t)C;
-    const size_t plane = C > kCrfTensorLdsClasses ? up(cells * sizeof(float)) : 0;
-    CrfTensorGradWorkspace w;
-    w.rows = 0;
-    w.temporal = w.rows + up(n * sizeof(uint2));
-    w.edge = w.temporal + up(n * sizeof(float4));
-    w.msg = w.edge + up((size_t)nnz * sizeof(float2));
-    w.dm = w.msg + plane;
-    w.x = w.dm + (backward ? up(2 * cells * sizeof(float)) : 0);
-    w.slots = w.x + (backward ? plane : 0);
-    w.bytes = w.slots + (backward && with_compat ? up(crf_tensor_grad_blocks(N, K) * (size_t)C * sizeof(float)) : 0);
-    return w;
-}
 
 constexpr int kCrfParamCount = 7;             // the floats of fslic_crf_params
 constexpr int kCrfParamGradBlock = 256;       // (frame, node) threads per block of k_crf_tensor_param_grad
@@ -59,28 +24,30 @@ struct CrfTensorTransposed {
     const int32_t* rows;        // [nnz]
 };
 
+// What the adjoint kernels read: the prepared lists and the transposed ones.
+struct CrfGradLists : CrfTensorLists {
+    CrfTensorTransposed tr;
+};
+
 // The adjoint of the sweep q_in -> q_new.  grad_new: the gradient with respect to q_new (the first launch of a backward), or NULL:
 // it is gathered from dm_in.  Writes dm_out, stores (first) or adds da to grad_unaries, and with slots != NULL stores or adds the
 // block's part of the gradient of compat.
-void launch_crf_tensor_sweep_bwd(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
-                                 const float4* temporal, const CrfTensorTransposed& tr, const float* unaries, const float* compat,
-                                 const float* q_in, const float* q_new, const float* grad_new, const float* dm_in, float* dm_out,
-                                 float* grad_unaries, float* slots, float* msg, float* x, bool first, hipStream_t st);
+void launch_crf_tensor_sweep_bwd(const CrfTensorParams& dp, const CrfGradLists& lists, const int32_t* indices, const float* unaries,
+                                 const float* compat, const float* q_in, const float* q_new, const float* grad_new, const float* dm_in,
+                                 float* dm_out, float* grad_unaries, float* slots, float* msg, float* x, bool first, hipStream_t st);
 // The last gather and the start of the chain.  grad_start: grad_q itself (no sweep ran) or NULL: gathered from dm_in.  With
 // grad_q0 != NULL that is the gradient of q0; otherwise -q_start * it goes into grad_unaries (q_start = crf_expf(-unaries)).
 // first: no sweep ran, grad_unaries is stored rather than added to.
-void launch_crf_tensor_grad_close(const CrfTensorParams& dp, const uint2* rows, const float2* edge, const float4* temporal,
-                                  const CrfTensorTransposed& tr, const float* q_start, const float* grad_start, const float* dm_in,
-                                  float* grad_unaries, float* grad_q0, bool first, hipStream_t st);
+void launch_crf_tensor_grad_close(const CrfTensorParams& dp, const CrfGradLists& lists, const float* q_start, const float* grad_start,
+                                  const float* dm_in, float* grad_unaries, float* grad_q0, bool first, hipStream_t st);
 // grad_compat[c] = the sum of slots[b][c] over the blocks in ascending order (blocks == 0: zero).
 void launch_crf_tensor_grad_compat(const float* slots, size_t blocks, int C, float* grad_compat, hipStream_t st);
 // The gradient of the energies from one sweep, behind its launch_crf_tensor_sweep_bwd: dm is what that launch left in dm_out, q_in
 // the sweep's input iterate.  Adds to grad_edge [nnz] (live entries inside the clamped rows, each found through its position in the
 // transposed lists) and to grad_links [N][2][K] (cells with a neighbouring frame, only with dp.temporal); either may be NULL.  The
 // caller zeroes both before the first launch.
-void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
-                                   const float4* temporal, const CrfTensorTransposed& tr, const float* dm, const float* q_in,
-                                   float* grad_edge, float* grad_links, hipStream_t st);
+void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const CrfGradLists& lists, const int32_t* indices, const float* dm,
+                                   const float* q_in, float* grad_edge, float* grad_links, hipStream_t st);
 // The backward of launch_crf_tensor_energies: grad_params[7] from grad_edge [nnz] and grad_links [N][2][K] (either may be NULL: zero)
 // and the params in device memory; slots is the workspace above.  Nothing flows to yxrgb.
 void launch_crf_tensor_param_grad(const CrfTensorParams& dp, const float* params, const float* yxrgb, const int64_t* offsets,

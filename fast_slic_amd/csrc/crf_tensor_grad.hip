@@ -38,30 +38,14 @@
 // counts only when its source row is a node of the gathering frame, the entry number lies inside that row's clamped bounds in `rows`
 // (so it is below nnz and edge[] of it was written by k_crf_tensor_edges), and the entry is live.
 // Every grid is exact (one trip), as the forward's.
-#include "crf.h"
 #include "crf_tensor_grad.h"
+#include "crf_tensor_sweep.h"
 #include "device_common.h"
 
 // The recomputed message, exponential and sum must be the forward's bits: the same operations under the same contraction rule.
 #pragma clang fp contract(off)
 
 namespace fslic {
-
-struct CrfGradLists {
-    const uint2* rows;
-    const float2* edge;
-    const float4* temporal;
-    CrfTensorTransposed tr;
-};
-
-// The bounds of the transposed row of (frame, node) g, clamped into [0, nnz] and to non-decreasing.
-static __device__ __forceinline__ uint2 crf_grad_bounds(const CrfTensorParams& dp, const int64_t* __restrict__ offsets, size_t g) {
-    long long t0 = offsets[g], t1 = offsets[g + 1];
-    t0 = t0 < 0 ? 0 : (t0 > dp.nnz ? dp.nnz : t0);
-    t1 = t1 < 0 ? 0 : (t1 > dp.nnz ? dp.nnz : t1);
-    if (t1 < t0) t1 = t0;
-    return make_uint2((uint32_t)t0, (uint32_t)t1);
-}
 
 // G[w, cls, i] from the dm of the sweep that read it: the transposed entries in list order, then frame w + 1, then frame w - 1.
 static __device__ __forceinline__ float crf_grad_gather(const CrfTensorParams& dp, const CrfGradLists& L, const float* __restrict__ dm,
@@ -92,8 +76,8 @@ static __device__ __forceinline__ float crf_grad_gather(const CrfTensorParams& d
     return G;
 }
 
-// m[cls * stride] and x[cls * stride] are the message and the second plane's value of (the thread's node, cls): LDS, or the workspace's
-// planes above kCrfTensorLdsClasses classes.
+// The second plane holds the exponentials, then G' q', then da: LDS, or the workspace's x above kCrfTensorLdsClasses classes
+// (crf_tensor_sweep.h).
 template <bool LDS>
 __global__ __launch_bounds__(kCrfTensorNodes * kCrfTensorWaves) void k_crf_tensor_sweep_bwd(
         CrfTensorParams dp, CrfGradLists L, const int32_t* __restrict__ idx, const float* __restrict__ unary,
@@ -102,87 +86,57 @@ __global__ __launch_bounds__(kCrfTensorNodes * kCrfTensorWaves) void k_crf_tenso
         float* __restrict__ slots, float* msg, float* xpl, int first) {
     extern __shared__ float s_crf_grad[];
     const int C = dp.C, K = dp.K;
-    const int tiles = (K + kCrfTensorNodes - 1) / kCrfTensorNodes;
-    const int w = blockIdx.x / tiles;                                          // the frame
-    const int lane = threadIdx.x % kCrfTensorNodes, wave = threadIdx.x / kCrfTensorNodes, waves = blockDim.x / kCrfTensorNodes;
-    const int i = (blockIdx.x - w * tiles) * kCrfTensorNodes + lane;           // the node
-    const bool live = i < K;                                                   // (a lane past the frame's end only keeps the barriers)
-    const size_t CK = (size_t)C * K, base = (size_t)w * CK;
-    float* m = LDS ? s_crf_grad + lane : msg + base + i;
-    float* x = LDS ? s_crf_grad + (size_t)C * kCrfTensorNodes + lane : xpl + base + i;
-    const size_t stride = LDS ? (size_t)kCrfTensorNodes : (size_t)K;
-    const bool has_prev = dp.temporal && w > 0, has_next = dp.temporal && w < dp.N - 1;
+    const CrfSweepThread t = crf_sweep_thread<LDS>(dp, s_crf_grad, msg, xpl);
 
-    // G' of every class of the slice into the thread's own cells of dm_out; the message as k_crf_tensor_sweep takes it
-    if (live) {
-        const uint2 r = L.rows[(size_t)w * K + i];
-        const float4 t = L.temporal[(size_t)w * K + i];
-        const uint2 tb = grad_new ? make_uint2(0u, 0u) : crf_grad_bounds(dp, L.tr.offsets, (size_t)w * K + i);
-        for (int cls = wave; cls < C; cls += waves) {
-            const size_t cell = base + (size_t)cls * K + i;
-            dm_out[cell] = grad_new ? grad_new[cell] : crf_grad_gather(dp, L, dm_in, tb, w, i, cls);
-            const float* qc = q_in + base + (size_t)cls * K;
-            float message = 0.0f;
-            for (uint32_t k = r.x; k < r.y; ++k) {
-                const float2 es = L.edge[k];
-                if (es.y == kCrfDeadEntry) continue;
-                message = __builtin_fmaf(es.x * qc[idx[k]], es.y, message);
-            }
-            if (has_prev) message = __builtin_fmaf(t.x * qc[i - (ptrdiff_t)CK], t.y, message);
-            if (has_next) message = __builtin_fmaf(t.z * qc[i + CK], t.w, message);
-            m[cls * stride] = message;
+    // G' of every class of the slice into the thread's own cells of dm_out; then the forward's message, exponential and sum
+    if (t.live) {
+        const uint2 r = L.rows[(size_t)t.w * K + t.i];
+        const float4 tl = L.temporal[(size_t)t.w * K + t.i];
+        const uint2 tb = grad_new ? make_uint2(0u, 0u) : crf_clamped_bounds(L.tr.offsets, (size_t)t.w * K + t.i, dp.nnz);
+        for (int cls = t.wave; cls < C; cls += t.waves) {
+            const size_t cell = t.base + (size_t)cls * K + t.i;
+            dm_out[cell] = grad_new ? grad_new[cell] : crf_grad_gather(dp, L, dm_in, tb, t.w, t.i, cls);
+            t.m[cls * t.stride] = crf_sweep_message(t, K, r, tl, idx, L.edge, q_in, cls);
         }
     }
     __syncthreads();
-    // the compatibility sum and the exponential, as the forward
-    if (live) {
-        for (int cls = wave; cls < C; cls += waves) {
-            float gathered = 0.0f;
-            for (int o = 0; o < cls; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
-            for (int o = cls + 1; o < C; ++o) gathered = __builtin_fmaf(compat[o], m[o * stride], gathered);
-            x[cls * stride] = crf_expf(-(unary[base + (size_t)cls * K + i] + gathered));
-        }
-    }
+    if (t.live)
+        for (int cls = t.wave; cls < C; cls += t.waves) t.x[cls * t.stride] = crf_sweep_exp(t, C, K, compat, unary, cls);
     __syncthreads();
     // the forward's own clamp decision: where it clamped, the sum was a constant
-    bool clamped = false;
-    if (live) {
-        float sum = 0.0f;
-        for (int cls = 0; cls < C; ++cls) sum += x[cls * stride];
-        clamped = (double)sum < 1e-5;
-    }
+    const bool clamped = t.live && crf_sweep_clamps(crf_sweep_class_sum(t, C));
     __syncthreads();                                                           // every sum is taken before the plane is reused
-    if (live)
-        for (int cls = wave; cls < C; cls += waves) {
-            const size_t cell = base + (size_t)cls * K + i;
-            x[cls * stride] = dm_out[cell] * q_new[cell];
+    if (t.live)
+        for (int cls = t.wave; cls < C; cls += t.waves) {
+            const size_t cell = t.base + (size_t)cls * K + t.i;
+            t.x[cls * t.stride] = dm_out[cell] * q_new[cell];
         }
     __syncthreads();
     float d = 0.0f;
-    if (live && !clamped)
-        for (int cls = 0; cls < C; ++cls) d += x[cls * stride];
+    if (t.live && !clamped)
+        for (int cls = 0; cls < C; ++cls) d += t.x[cls * t.stride];
     __syncthreads();
-    if (live)
-        for (int cls = wave; cls < C; cls += waves) {
-            const size_t cell = base + (size_t)cls * K + i;
+    if (t.live)
+        for (int cls = t.wave; cls < C; cls += t.waves) {
+            const size_t cell = t.base + (size_t)cls * K + t.i;
             const float da = -q_new[cell] * (dm_out[cell] - d);
-            x[cls * stride] = da;
+            t.x[cls * t.stride] = da;
             du[cell] = first ? da : du[cell] + da;
         }
     __syncthreads();
     // S over the other classes in ascending order; dm; the block's part of dcompat (the loop is uniform over the wavefront)
     float* slot = slots ? slots + (size_t)blockIdx.x * C : nullptr;
-    for (int cls = wave; cls < C; cls += waves) {
+    for (int cls = t.wave; cls < C; cls += t.waves) {
         float S = 0.0f, part = 0.0f;
-        if (live) {
-            for (int o = 0; o < cls; ++o) S += x[o * stride];
-            for (int o = cls + 1; o < C; ++o) S += x[o * stride];
-            dm_out[base + (size_t)cls * K + i] = compat[cls] * S;
-            if (slot) part = m[cls * stride] * S;
+        if (t.live) {
+            for (int o = 0; o < cls; ++o) S += t.x[o * t.stride];
+            for (int o = cls + 1; o < C; ++o) S += t.x[o * t.stride];
+            dm_out[t.base + (size_t)cls * K + t.i] = compat[cls] * S;
+            if (slot) part = t.m[cls * t.stride] * S;
         }
         if (slot) {
             const float total = wave_reduce_add<float>(part);
-            if (lane == 0) slot[cls] = first ? total : slot[cls] + total;
+            if (t.lane == 0) slot[cls] = first ? total : slot[cls] + total;
         }
     }
 }
@@ -196,7 +150,8 @@ __global__ __launch_bounds__(256) void k_crf_tensor_grad_close(CrfTensorParams d
     const int K = dp.K, C = dp.C;
     const int plane = (int)(p / (size_t)K), i = (int)(p - (size_t)plane * K);
     const int w = plane / C, cls = plane - w * C;
-    const float G = grad_start ? grad_start[p] : crf_grad_gather(dp, L, dm_in, crf_grad_bounds(dp, L.tr.offsets, (size_t)w * K + i), w, i, cls);
+    const float G = grad_start ? grad_start[p]
+                               : crf_grad_gather(dp, L, dm_in, crf_clamped_bounds(L.tr.offsets, (size_t)w * K + i, dp.nnz), w, i, cls);
     if (dq0) {
         dq0[p] = G;
         if (first) du[p] = 0.0f;
@@ -272,7 +227,7 @@ __global__ __launch_bounds__(kCrfParamGradBlock) void k_crf_tensor_param_grad(
         const double yi = planes[i], xi = planes[K + i], ri = planes[2 * (size_t)K + i], gi = planes[3 * (size_t)K + i], bi = planes[4 * (size_t)K + i];
         if (ge) {
             const double sw = params[0], srgb = params[2], sxy = params[4], ssw = params[5], ssxy = params[6];
-            const uint2 r = crf_grad_bounds(dp, offsets, (size_t)g);           // the row's bounds as k_crf_tensor_edges clamps them
+            const uint2 r = crf_clamped_bounds(offsets, (size_t)g, dp.nnz);
             for (uint32_t k = r.x; k < r.y; ++k) {
                 const int32_t j = idx[k];
                 if ((uint32_t)j >= (uint32_t)K || j == i) continue;            // a dead entry, a self-loop: the energy is the constant 0
@@ -323,15 +278,13 @@ __global__ __launch_bounds__(64) void k_crf_tensor_param_grad_close(const double
     out[threadIdx.x] = (float)s;
 }
 
-void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
-                                   const float4* temporal, const CrfTensorTransposed& tr, const float* dm, const float* q_in,
-                                   float* grad_edge, float* grad_links, hipStream_t st) {
+void launch_crf_tensor_energy_grad(const CrfTensorParams& dp, const CrfGradLists& lists, const int32_t* indices, const float* dm,
+                                   const float* q_in, float* grad_edge, float* grad_links, hipStream_t st) {
     // one thread per neighbour entry (none without grad_edge), then one per (frame, node) for the links; below 2^32 because nnz and N * K are below 2^31
     const uint32_t entries = grad_edge ? (uint32_t)dp.nnz : 0u;
     const uint32_t n = entries + (grad_links && dp.temporal ? (uint32_t)dp.N * (uint32_t)dp.K : 0u);
     if (n == 0) return;
-    const CrfGradLists L = {rows, edge, temporal, tr};
-    launch(k_crf_tensor_energy_grad, dim3((n + 255) / 256), dim3(256), 0, st, dp, L, indices, dm, q_in, grad_edge, grad_links, entries);
+    launch(k_crf_tensor_energy_grad, dim3((n + 255) / 256), dim3(256), 0, st, dp, lists, indices, dm, q_in, grad_edge, grad_links, entries);
 }
 
 void launch_crf_tensor_param_grad(const CrfTensorParams& dp, const float* params, const float* yxrgb, const int64_t* offsets,
@@ -343,28 +296,18 @@ void launch_crf_tensor_param_grad(const CrfTensorParams& dp, const float* params
     launch(k_crf_tensor_param_grad_close, dim3(1), dim3(64), 0, st, (const double*)slots, blocks, grad_params);
 }
 
-void launch_crf_tensor_sweep_bwd(const CrfTensorParams& dp, const uint2* rows, const int32_t* indices, const float2* edge,
-                                 const float4* temporal, const CrfTensorTransposed& tr, const float* unaries, const float* compat,
-                                 const float* q_in, const float* q_new, const float* grad_new, const float* dm_in, float* dm_out,
-                                 float* grad_unaries, float* slots, float* msg, float* x, bool first, hipStream_t st) {
-    // the forward sweep's block shape (launch_crf_tensor_sweep)
-    const int per = (dp.C + kCrfTensorWaves - 1) / kCrfTensorWaves, waves = (dp.C + per - 1) / per;
-    const dim3 grid((unsigned)crf_tensor_grad_blocks(dp.N, dp.K)), block(kCrfTensorNodes * waves);
-    const CrfGradLists L = {rows, edge, temporal, tr};
-    if (dp.C <= kCrfTensorLdsClasses)
-        launch(k_crf_tensor_sweep_bwd<true>, grid, block, (unsigned)(2 * sizeof(float) * kCrfTensorNodes * dp.C), st,
-               dp, L, indices, unaries, compat, q_in, q_new, grad_new, dm_in, dm_out, grad_unaries, slots, msg, x, (int)first);
-    else
-        launch(k_crf_tensor_sweep_bwd<false>, grid, block, 0, st,
-               dp, L, indices, unaries, compat, q_in, q_new, grad_new, dm_in, dm_out, grad_unaries, slots, msg, x, (int)first);
+void launch_crf_tensor_sweep_bwd(const CrfTensorParams& dp, const CrfGradLists& lists, const int32_t* indices, const float* unaries,
+                                 const float* compat, const float* q_in, const float* q_new, const float* grad_new, const float* dm_in,
+                                 float* dm_out, float* grad_unaries, float* slots, float* msg, float* x, bool first, hipStream_t st) {
+    const CrfSweepShape sh = crf_tensor_sweep_shape(dp.N, dp.C, dp.K);
+    launch(sh.lds ? k_crf_tensor_sweep_bwd<true> : k_crf_tensor_sweep_bwd<false>, dim3(sh.grid), dim3(sh.block), sh.lds, st, dp, lists,
+           indices, unaries, compat, q_in, q_new, grad_new, dm_in, dm_out, grad_unaries, slots, msg, x, (int)first);
 }
 
-void launch_crf_tensor_grad_close(const CrfTensorParams& dp, const uint2* rows, const float2* edge, const float4* temporal,
-                                  const CrfTensorTransposed& tr, const float* q_start, const float* grad_start, const float* dm_in,
-                                  float* grad_unaries, float* grad_q0, bool first, hipStream_t st) {
+void launch_crf_tensor_grad_close(const CrfTensorParams& dp, const CrfGradLists& lists, const float* q_start, const float* grad_start,
+                                  const float* dm_in, float* grad_unaries, float* grad_q0, bool first, hipStream_t st) {
     const size_t n = (size_t)dp.N * dp.C * dp.K;
-    const CrfGradLists L = {rows, edge, temporal, tr};
-    launch(k_crf_tensor_grad_close, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dp, L, q_start, grad_start, dm_in, grad_unaries,
+    launch(k_crf_tensor_grad_close, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dp, lists, q_start, grad_start, dm_in, grad_unaries,
            grad_q0, (int)first);
 }
 

@@ -18,7 +18,7 @@ int check_sizes(int N, int C, int K, long long nnz) {
     return FSLIC_OK;
 }
 
-// What fslic_hip_crf_tensor_inference checks ahead of its pointers, for the entries of the differentiable path.
+// What every entry with a device checks ahead of its pointers.
 int check_call(int device, int N, int C, int K, long long nnz, int temporal, int max_iter) {
     if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
     const int rc = check_sizes(N, C, K, nnz);
@@ -42,17 +42,43 @@ struct EnergySource {
     const float* links;                 // [N][2][K] or NULL
 };
 
-CrfTensorParams tensor_params(int N, int C, int K, int temporal, long long nnz, const EnergySource& src) {
+// One call of the three entries with sweeps and of their _energies forms: what all of them are given.
+struct CrfCall {
+    int device;
+    void* stream;
+    int N, C, K, temporal, max_iter;
+    long long nnz;
+    EnergySource src;
+    const float* compat;
+    const int32_t* members;
+    const int64_t* offsets;
+    const int32_t* indices;
+    const float* unaries;
+    void* workspace;
+    size_t workspace_bytes;
+};
+
+CrfTensorParams tensor_params(int N, int C, int K, int temporal, long long nnz, const fslic_crf_params* params) {
     CrfTensorParams dp = {};
     dp.N = N; dp.C = C; dp.K = K; dp.temporal = temporal; dp.nnz = nnz;
-    if (src.params) dp.p = *src.params;
+    if (params) dp.p = *params;
     return dp;
 }
 
-void launch_edges(const CrfTensorParams& dp, const EnergySource& src, const int32_t* members, const int64_t* offsets,
-                  const int32_t* indices, uint2* rows, float2* edge, float4* tmp, hipStream_t st) {
-    if (src.params) launch_crf_tensor_edges(dp, src.yxrgb, members, offsets, indices, rows, edge, tmp, st);
-    else launch_crf_tensor_edges_given(dp, src.edge, src.links, members, offsets, indices, rows, edge, tmp, st);
+// The checks of such a call, in the order of every entry: the numbers, the pointers (`own`: the entry's own and its energy source's
+// are there), the workspace.  -> the layout of the workspace in *ws.
+int check(const CrfCall& c, bool own, CrfTensorCall kind, bool with_compat, CrfTensorWorkspace* ws) {
+    const int rc = check_call(c.device, c.N, c.C, c.K, c.nnz, c.temporal, c.max_iter);
+    if (rc) return rc;
+    if (!own || !c.compat || !c.members || !c.offsets || !c.unaries || !c.workspace || (!c.indices && c.nnz > 0))
+        return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    *ws = crf_tensor_workspace(c.N, c.C, c.K, c.nnz, kind, with_compat);
+    return check_workspace(c.workspace, c.workspace_bytes, ws->bytes);
+}
+
+void launch_edges(const CrfCall& c, const CrfTensorParams& dp, const CrfTensorBuffers& b, hipStream_t st) {
+    if (c.src.params) launch_crf_tensor_edges(dp, c.src.yxrgb, c.members, c.offsets, c.indices, b.rows, b.edge, b.temporal, st);
+    else launch_crf_tensor_edges_given(dp, c.src.edge, c.src.links, c.members, c.offsets, c.indices, b.rows, b.edge, b.temporal, st);
 }
 
 int launch_status() {
@@ -60,106 +86,90 @@ int launch_status() {
     return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
 }
 
-// The bodies of the entries below, behind their argument checks.
-int run_inference(int device, void* stream, int N, int C, int K, int temporal, int max_iter, const EnergySource& src,
-                  const float* compat, const int32_t* members, const int64_t* offsets, const int32_t* indices, long long nnz,
-                  const float* unaries, const float* q0, float* q_out, void* workspace, const CrfTensorWorkspace& ws) {
+// The bodies of the entries below.
+// The forward: the start, the edge pass and max_iter sweeps.  at(it) is where iterate `it` lives: sweep `it` reads at(it) and writes
+// at(it + 1).  `placed`: the starting q where it already is; NULL: the start launch writes it to at(0).
+template <class At>
+int run_forward(const CrfCall& c, const CrfTensorWorkspace& ws, const float* q0, const float* placed, At at) {
     int rc;
     DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* base = reinterpret_cast<char*>(workspace);
-    float* buf[2] = {q_out, reinterpret_cast<float*>(base + ws.q)};
-    // sweep `it` writes buf[(max_iter - 1 - it) & 1], so that the last one writes q_out; the starting q sits where the first sweep
-    // does not write: q0 itself when it is given (it is only read), buf[max_iter & 1] otherwise
-    const size_t cells = (size_t)N * C * K;
-    const float* q_in = q0;
-    if (!q0 || max_iter == 0) {
-        float* start = buf[max_iter & 1];
-        launch_crf_tensor_start(unaries, q0, start, cells, st);
-        q_in = start;
+    if ((rc = scope.enter(c.device))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    const float* q_in = placed;
+    if (!placed) {
+        launch_crf_tensor_start(c.unaries, q0, at(0), (size_t)c.N * c.C * c.K, st);
+        q_in = at(0);
     }
-    if (max_iter > 0) {
-        const CrfTensorParams dp = tensor_params(N, C, K, temporal, nnz, src);
-        uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
-        float2* edge = reinterpret_cast<float2*>(base + ws.edge);
-        float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
-        float* msg = reinterpret_cast<float*>(base + ws.msg);
-        launch_edges(dp, src, members, offsets, indices, rows, edge, tmp, st);
-        for (int it = 0; it < max_iter; it++) {
-            float* out = buf[(max_iter - 1 - it) & 1];
-            launch_crf_tensor_sweep(dp, rows, indices, edge, tmp, unaries, compat, q_in, out, msg, st);
-            q_in = out;
+    if (c.max_iter > 0) {
+        const CrfTensorParams dp = tensor_params(c.N, c.C, c.K, c.temporal, c.nnz, c.src.params);
+        const CrfTensorBuffers b = crf_tensor_buffers(c.workspace, ws);
+        launch_edges(c, dp, b, st);
+        for (int it = 0; it < c.max_iter; it++) {
+            launch_crf_tensor_sweep(dp, b.lists(), c.indices, c.unaries, c.compat, q_in, at(it + 1), b.msg, st);
+            q_in = at(it + 1);
         }
     }
     return launch_status();
 }
 
-int run_inference_saved(int device, void* stream, int N, int C, int K, int temporal, int max_iter, const EnergySource& src,
-                        const float* compat, const int32_t* members, const int64_t* offsets, const int32_t* indices, long long nnz,
-                        const float* unaries, const float* q0, float* q_all, void* workspace, const CrfTensorGradWorkspace& ws) {
-    int rc;
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* base = reinterpret_cast<char*>(workspace);
-    const size_t cells = (size_t)N * C * K;
-    // plane 0 is the starting q, plane it + 1 what sweep `it` writes: the ping-pong of fslic_hip_crf_tensor_inference unrolled
-    launch_crf_tensor_start(unaries, q0, q_all, cells, st);
-    if (max_iter > 0) {
-        const CrfTensorParams dp = tensor_params(N, C, K, temporal, nnz, src);
-        uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
-        float2* edge = reinterpret_cast<float2*>(base + ws.edge);
-        float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
-        float* msg = reinterpret_cast<float*>(base + ws.msg);
-        launch_edges(dp, src, members, offsets, indices, rows, edge, tmp, st);
-        for (int it = 0; it < max_iter; it++)
-            launch_crf_tensor_sweep(dp, rows, indices, edge, tmp, unaries, compat, q_all + (size_t)it * cells,
-                                    q_all + (size_t)(it + 1) * cells, msg, st);
-    }
-    return launch_status();
+int run_inference(const CrfCall& c, bool own, const float* q0, float* q_out) {
+    CrfTensorWorkspace ws;
+    const int rc = check(c, own && q_out, kCrfCallPlain, false, &ws);
+    if (rc) return rc;
+    // a ping-pong between q_out and the workspace's q that ends in q_out: iterate `it` lives in buf[(max_iter - it) & 1].  A given
+    // q0 is only read, so the first sweep reads it where it is
+    float* buf[2] = {q_out, crf_tensor_buffers(c.workspace, ws).q};
+    const int max_iter = c.max_iter;
+    return run_forward(c, ws, q0, max_iter > 0 ? q0 : nullptr, [&](int it) { return buf[(max_iter - it) & 1]; });
+}
+
+int run_inference_saved(const CrfCall& c, bool own, const float* q0, float* q_all) {
+    CrfTensorWorkspace ws;
+    const int rc = check(c, own && q_all, kCrfCallSaved, false, &ws);
+    if (rc) return rc;
+    // iterate `it` is plane `it` of q_all: the ping-pong of run_inference unrolled
+    const size_t cells = (size_t)c.N * c.C * c.K;
+    return run_forward(c, ws, q0, nullptr, [&](int it) { return q_all + (size_t)it * cells; });
 }
 
 // grad_edge [nnz] and grad_links [N][2][K] (either may be NULL) are zeroed on the stream and filled behind each sweep's adjoint.
-int run_backward(int device, void* stream, int N, int C, int K, int temporal, int max_iter, const EnergySource& src,
-                 const float* compat, const int32_t* members, const int64_t* offsets, const int32_t* indices, long long nnz,
-                 const CrfTensorTransposed& tr, const float* unaries, const float* q_all, const float* grad_q, float* grad_unaries,
-                 float* grad_q0, float* grad_compat, float* grad_edge, float* grad_links, void* workspace,
-                 const CrfTensorGradWorkspace& ws) {
-    int rc;
+int run_backward(const CrfCall& c, bool own, const CrfTensorTransposed& tr, const float* q_all, const float* grad_q, float* grad_unaries,
+                 float* grad_q0, float* grad_compat, float* grad_edge, float* grad_links) {
+    CrfTensorWorkspace ws;
+    int rc = check(c, own && tr.offsets && q_all && grad_q && grad_unaries && ((tr.entries && tr.rows) || c.nnz == 0), kCrfCallBackward,
+                   grad_compat != nullptr, &ws);
+    if (rc) return rc;
     DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char* base = reinterpret_cast<char*>(workspace);
-    const size_t cells = (size_t)N * C * K, blocks = crf_tensor_grad_blocks(N, K);
-    const CrfTensorParams dp = tensor_params(N, C, K, temporal, nnz, src);
-    uint2* rows = reinterpret_cast<uint2*>(base + ws.rows);
-    float2* edge = reinterpret_cast<float2*>(base + ws.edge);
-    float4* tmp = reinterpret_cast<float4*>(base + ws.temporal);
-    float* msg = reinterpret_cast<float*>(base + ws.msg);
-    float* dm[2] = {reinterpret_cast<float*>(base + ws.dm), reinterpret_cast<float*>(base + ws.dm) + cells};
-    float* x = reinterpret_cast<float*>(base + ws.x);
-    float* slots = grad_compat ? reinterpret_cast<float*>(base + ws.slots) : nullptr;
+    if ((rc = scope.enter(c.device))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    const int N = c.N, K = c.K, max_iter = c.max_iter;
+    const long long nnz = c.nnz;
+    const size_t cells = (size_t)N * c.C * K;
+    const CrfTensorParams dp = tensor_params(N, c.C, K, c.temporal, nnz, c.src.params);
+    const CrfTensorBuffers b = crf_tensor_buffers(c.workspace, ws);
+    const CrfGradLists lists = {b.lists(), tr};
+    float* dm[2] = {b.dm, b.dm + cells};
+    float* slots = grad_compat ? b.slots : nullptr;
     if (grad_edge && nnz > 0) HIPCHK(hipMemsetAsync(grad_edge, 0, (size_t)nnz * sizeof(float), st));
     if (grad_links) HIPCHK(hipMemsetAsync(grad_links, 0, (size_t)N * 2 * K * sizeof(float), st));
     // the energy gradients of a sweep need that sweep's dm alone; without entries and without links there is nothing to add
-    const bool energy_grad = (grad_edge && nnz > 0) || (grad_links && temporal && N > 1);
+    const bool energy_grad = (grad_edge && nnz > 0) || (grad_links && c.temporal && N > 1);
     if (max_iter > 0) {
         // the energies again rather than the forward's workspace: nothing but the iterates stays alive between the two calls
-        launch_edges(dp, src, members, offsets, indices, rows, edge, tmp, st);
+        launch_edges(c, dp, b, st);
         for (int it = max_iter - 1; it >= 0; it--) {
             const bool first = it == max_iter - 1;
-            launch_crf_tensor_sweep_bwd(dp, rows, indices, edge, tmp, tr, unaries, compat, q_all + (size_t)it * cells,
+            launch_crf_tensor_sweep_bwd(dp, lists, c.indices, c.unaries, c.compat, q_all + (size_t)it * cells,
                                         q_all + (size_t)(it + 1) * cells, first ? grad_q : nullptr, dm[(it + 1) & 1], dm[it & 1],
-                                        grad_unaries, slots, msg, x, first, st);
+                                        grad_unaries, slots, b.msg, b.x, first, st);
             if (energy_grad)
-                launch_crf_tensor_energy_grad(dp, rows, indices, edge, tmp, tr, dm[it & 1], q_all + (size_t)it * cells,
-                                              nnz > 0 ? grad_edge : nullptr, grad_links, st);
+                launch_crf_tensor_energy_grad(dp, lists, c.indices, dm[it & 1], q_all + (size_t)it * cells, nnz > 0 ? grad_edge : nullptr,
+                                              grad_links, st);
         }
     }
-    launch_crf_tensor_grad_close(dp, rows, edge, tmp, tr, q_all, max_iter > 0 ? nullptr : grad_q, dm[0], grad_unaries, grad_q0,
-                                 max_iter == 0, st);
-    if (grad_compat) launch_crf_tensor_grad_compat(slots, max_iter > 0 ? blocks : 0, C, grad_compat, st);
+    launch_crf_tensor_grad_close(dp, lists, q_all, max_iter > 0 ? nullptr : grad_q, dm[0], grad_unaries, grad_q0, max_iter == 0, st);
+    if (grad_compat)
+        launch_crf_tensor_grad_compat(slots, max_iter > 0 ? crf_tensor_sweep_shape(N, c.C, K).grid : 0, c.C, grad_compat, st);
     return launch_status();
 }
 
@@ -171,7 +181,7 @@ int fslic_hip_crf_tensor_workspace_size(int N, int C, int K, long long nnz, size
     if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     const int rc = check_sizes(N, C, K, nnz);
     if (rc) return rc;
-    *bytes = crf_tensor_workspace(N, C, K, nnz).bytes;
+    *bytes = crf_tensor_workspace(N, C, K, nnz, kCrfCallPlain, false).bytes;
     return FSLIC_OK;
 }
 
@@ -179,19 +189,9 @@ int fslic_hip_crf_tensor_inference(int device, void* stream, int N, int C, int K
                                    const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
                                    const int64_t* offsets, const int32_t* indices, long long nnz, const float* unaries, const float* q0,
                                    float* q_out, void* workspace, size_t workspace_bytes) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
-    int rc = check_sizes(N, C, K, nnz);
-    if (rc) return rc;
-    if (temporal != 0 && temporal != 1) return fail(FSLIC_E_INVALID, "temporal must be 0 or 1");
-    if (max_iter < 0) return fail(FSLIC_E_INVALID, "max_iter must be >= 0");
-    if (!params || !compat || !yxrgb || !members || !offsets || !unaries || !q_out || !workspace || (!indices && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(FSLIC_E_INVALID, "workspace must be 16-byte aligned");
-    const CrfTensorWorkspace ws = crf_tensor_workspace(N, C, K, nnz);
-    if (workspace_bytes < ws.bytes) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(ws.bytes) + " bytes needed");
-    const EnergySource src = {params, yxrgb, nullptr, nullptr};
-    return run_inference(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, unaries, q0, q_out,
-                         workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {params, yxrgb, nullptr, nullptr},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_inference(c, params && yxrgb, q0, q_out);
 }
 
 int fslic_hip_crf_tensor_grad_workspace_size(int N, int C, int K, long long nnz, int backward, int with_compat, size_t* bytes) {
@@ -200,7 +200,7 @@ int fslic_hip_crf_tensor_grad_workspace_size(int N, int C, int K, long long nnz,
     if (rc) return rc;
     if ((backward != 0 && backward != 1) || (with_compat != 0 && with_compat != 1))
         return fail(FSLIC_E_INVALID, "backward and with_compat must be 0 or 1");
-    *bytes = crf_tensor_grad_workspace(N, C, K, nnz, backward != 0, with_compat != 0).bytes;
+    *bytes = crf_tensor_workspace(N, C, K, nnz, backward ? kCrfCallBackward : kCrfCallSaved, with_compat != 0).bytes;
     return FSLIC_OK;
 }
 
@@ -208,15 +208,9 @@ int fslic_hip_crf_tensor_inference_saved(int device, void* stream, int N, int C,
                                          const fslic_crf_params* params, const float* compat, const float* yxrgb, const int32_t* members,
                                          const int64_t* offsets, const int32_t* indices, long long nnz, const float* unaries,
                                          const float* q0, float* q_all, void* workspace, size_t workspace_bytes) {
-    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
-    if (rc) return rc;
-    if (!params || !compat || !yxrgb || !members || !offsets || !unaries || !q_all || !workspace || (!indices && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, false, false);
-    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
-    const EnergySource src = {params, yxrgb, nullptr, nullptr};
-    return run_inference_saved(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, unaries, q0,
-                               q_all, workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {params, yxrgb, nullptr, nullptr},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_inference_saved(c, params && yxrgb, q0, q_all);
 }
 
 int fslic_hip_crf_tensor_backward(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
@@ -225,17 +219,10 @@ int fslic_hip_crf_tensor_backward(int device, void* stream, int N, int C, int K,
                                   const int32_t* t_entries, const int32_t* t_rows, const float* unaries, const float* q_all,
                                   const float* grad_q, float* grad_unaries, float* grad_q0, float* grad_compat, void* workspace,
                                   size_t workspace_bytes) {
-    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
-    if (rc) return rc;
-    if (!params || !compat || !yxrgb || !members || !offsets || !t_offsets || !unaries || !q_all || !grad_q || !grad_unaries ||
-        !workspace || ((!indices || !t_entries || !t_rows) && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, true, grad_compat != nullptr);
-    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
-    const EnergySource src = {params, yxrgb, nullptr, nullptr};
-    const CrfTensorTransposed tr = {t_offsets, t_entries, t_rows};
-    return run_backward(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, tr, unaries, q_all,
-                        grad_q, grad_unaries, grad_q0, grad_compat, nullptr, nullptr, workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {params, yxrgb, nullptr, nullptr},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_backward(c, params && yxrgb, {t_offsets, t_entries, t_rows}, q_all, grad_q, grad_unaries, grad_q0, grad_compat, nullptr,
+                        nullptr);
 }
 
 // ---- the energies as tensors: forward, backward to the params, and the three entries above with given energies ----
@@ -249,8 +236,7 @@ int fslic_hip_crf_tensor_energies(int device, void* stream, int N, int K, int te
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const EnergySource none = {};
-    const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, none);
+    const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, nullptr);
     if (nnz > 0) HIPCHK(hipMemsetAsync(edge, 0, (size_t)nnz * sizeof(float), st));      // the entries outside every clamped row
     launch_crf_tensor_energies(dp, params, yxrgb, members, offsets, indices, edge, links, st);
     return launch_status();
@@ -275,8 +261,7 @@ int fslic_hip_crf_tensor_energies_backward(int device, void* stream, int N, int 
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const EnergySource none = {};
-    const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, none);
+    const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, nullptr);
     launch_crf_tensor_param_grad(dp, params, yxrgb, offsets, indices, nnz > 0 ? grad_edge : nullptr, grad_links,
                                  reinterpret_cast<double*>(workspace), grad_params, st);
     return launch_status();
@@ -286,15 +271,9 @@ int fslic_hip_crf_tensor_inference_energies(int device, void* stream, int N, int
                                             const int32_t* members, const int64_t* offsets, const int32_t* indices, long long nnz,
                                             const float* edge, const float* links, const float* unaries, const float* q0, float* q_out,
                                             void* workspace, size_t workspace_bytes) {
-    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
-    if (rc) return rc;
-    if (!compat || !members || !offsets || !unaries || !q_out || !workspace || ((!indices || !edge) && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const CrfTensorWorkspace ws = crf_tensor_workspace(N, C, K, nnz);
-    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
-    const EnergySource src = {nullptr, nullptr, edge, links};
-    return run_inference(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, unaries, q0, q_out,
-                         workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {nullptr, nullptr, edge, links},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_inference(c, edge || nnz == 0, q0, q_out);
 }
 
 int fslic_hip_crf_tensor_inference_saved_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter,
@@ -302,15 +281,9 @@ int fslic_hip_crf_tensor_inference_saved_energies(int device, void* stream, int 
                                                   const int32_t* indices, long long nnz, const float* edge, const float* links,
                                                   const float* unaries, const float* q0, float* q_all, void* workspace,
                                                   size_t workspace_bytes) {
-    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
-    if (rc) return rc;
-    if (!compat || !members || !offsets || !unaries || !q_all || !workspace || ((!indices || !edge) && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, false, false);
-    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
-    const EnergySource src = {nullptr, nullptr, edge, links};
-    return run_inference_saved(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, unaries, q0,
-                               q_all, workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {nullptr, nullptr, edge, links},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_inference_saved(c, edge || nnz == 0, q0, q_all);
 }
 
 int fslic_hip_crf_tensor_backward_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter, const float* compat,
@@ -319,17 +292,10 @@ int fslic_hip_crf_tensor_backward_energies(int device, void* stream, int N, int 
                                            const int32_t* t_rows, const float* unaries, const float* q_all, const float* grad_q,
                                            float* grad_unaries, float* grad_q0, float* grad_compat, float* grad_edge, float* grad_links,
                                            void* workspace, size_t workspace_bytes) {
-    int rc = check_call(device, N, C, K, nnz, temporal, max_iter);
-    if (rc) return rc;
-    if (!compat || !members || !offsets || !t_offsets || !unaries || !q_all || !grad_q || !grad_unaries || !workspace ||
-        ((!indices || !edge || !t_entries || !t_rows) && nnz > 0))
-        return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const CrfTensorGradWorkspace ws = crf_tensor_grad_workspace(N, C, K, nnz, true, grad_compat != nullptr);
-    if ((rc = check_workspace(workspace, workspace_bytes, ws.bytes))) return rc;
-    const EnergySource src = {nullptr, nullptr, edge, links};
-    const CrfTensorTransposed tr = {t_offsets, t_entries, t_rows};
-    return run_backward(device, stream, N, C, K, temporal, max_iter, src, compat, members, offsets, indices, nnz, tr, unaries, q_all,
-                        grad_q, grad_unaries, grad_q0, grad_compat, grad_edge, grad_links, workspace, ws);
+    const CrfCall c = {device, stream, N, C, K, temporal, max_iter, nnz, {nullptr, nullptr, edge, links},
+                       compat, members, offsets, indices, unaries, workspace, workspace_bytes};
+    return run_backward(c, edge || nnz == 0, {t_offsets, t_entries, t_rows}, q_all, grad_q, grad_unaries, grad_q0, grad_compat, grad_edge,
+                        grad_links);
 }
 
 }  // extern "C"

@@ -135,6 +135,32 @@ def test_q_has_the_bits_of_the_dict_call(shape, key):
         assert torch.all(links[0, 0] == 0) and torch.all(links[-1, 1] == 0)
 
 
+@pytest.mark.parametrize("N,Cn,K", [(2, 21, 129), (2, G.LDS_CUT + 1, 70)])
+def test_forward_bits_and_repeated_calls_with_energies(N, Cn, K):
+    """test_forward_bits_and_repeated_calls of tests/test_gpu_crf_tensor_grad.py through energies=."""
+    case = G.Case(26, N, Cn, K)
+    with torch.no_grad():
+        edge, links = crf_edge_energies(case.graph, case.yx, case.mem, theta_gpu(COUPLED), True)
+
+    def grads(iters, with_q0):
+        e, l = edge.clone().requires_grad_(True), links.clone().requires_grad_(True)
+        un, comp, q0 = leaves(case, True, with_q0)
+        q = crf(case, iters, True, un, comp, q0, yxrgb=False, energies=(e, l))
+        backward(case, q)
+        return dict(q=q.detach(), unaries=un.grad, compat=comp.grad, q0=None if q0 is None else q0.grad, edge=e.grad, links=l.grad)
+
+    for iters in (0, 1, 2, 3):                                                      # no sweep, both parities of the ping-pong
+        for with_q0 in (False, True):
+            a, b = grads(iters, with_q0), grads(iters, with_q0)
+            with torch.no_grad():
+                plain = crf(case, iters, True, *leaves(case, True, with_q0), yxrgb=False, energies=(edge, links))
+            assert torch.equal(a["q"], plain), (iters, with_q0)
+            for name in ("unaries", "compat", "q0", "edge", "links"):
+                assert (a[name] is None and b[name] is None) or torch.equal(a[name], b[name]), (name, iters, with_q0)
+            if iters >= 1:
+                assert float(a["unaries"].abs().max()) > 0 and float(a["compat"].abs().max()) > 0
+
+
 def test_energies_are_simple_crfs_and_zero_where_nothing_is():
     N, Cn, K = 3, 3, 70
     case = G.Case(41, N, Cn, K)
