@@ -21,17 +21,15 @@ of every result.  This module imports torch; the package itself does not import 
 import ctypes as C
 import numbers
 
-import numpy as np
 import torch
 
-from . import _binding as B
-from .pool import MAX_COMPONENTS, _LABEL_TYPE, _NUMPY_LABELS, _check_device, _labels_on, _stream
+from . import _binding as B, _pairtable as T
+from ._pairtable import _MAX_CAPACITY, _pow2_at_least
+from .pool import MAX_COMPONENTS, _labels_on, _stream
 
 __all__ = ["label_overlap", "boundary_match", "OverlapTable"]
 
 MAX_TOLERANCE = 15
-_HEADER_FIXED = 16          # bytes of the workspace header before the per-frame pair counts (csrc/compare.h)
-_MIN_CAPACITY, _MAX_CAPACITY = 64, 1 << 31
 
 
 def _lib():
@@ -39,10 +37,6 @@ def _lib():
     if not hasattr(lib, "fslic_hip_overlap_accumulate"):
         raise RuntimeError("fast_slic_amd: the loaded library has no label map comparison entry points; rebuild it")
     return lib
-
-
-def _pow2_at_least(v):
-    return 1 << max(0, int(v) - 1).bit_length()
 
 
 def first_capacity(K, M):
@@ -123,21 +117,9 @@ class OverlapTable(object):
 
 
 # ---- argument checks: all of them run before any device work ----
-def _check_map(t, what):
-    if not isinstance(t, (np.ndarray, torch.Tensor)):
-        raise ValueError("%s must be a numpy array or a torch tensor" % what)
-    if t.ndim not in (2, 3):
-        raise ValueError("%s must be [H, W] or [N, H, W], got shape %s" % (what, tuple(t.shape)))
-    if 0 in t.shape:
-        raise ValueError("%s must not be empty, got shape %s" % (what, tuple(t.shape)))
-    ok = t.dtype.type in _NUMPY_LABELS if isinstance(t, np.ndarray) else t.dtype in _LABEL_TYPE
-    if not ok:
-        raise ValueError("%s must be int16 (Slic.iterate's map), int32 or int64, got %s" % (what, t.dtype))
-
-
 def _check_maps(labels, other):
-    _check_map(labels, "labels")
-    _check_map(other, "other")
+    T.check_label_map(labels, "labels")
+    T.check_label_map(other, "other")
     if tuple(other.shape) != tuple(labels.shape):
         raise ValueError("other must have shape %s to match the labels, got %s" % (tuple(labels.shape), tuple(other.shape)))
     H, W = (int(v) for v in labels.shape[-2:])
@@ -155,44 +137,12 @@ def _check_count(K, what):
     return K
 
 
-def _pick_device(labels, other, device):
-    """The GPU of the result.  Torch tensors must already be there (and on the same one); numpy arrays are uploaded."""
-    given = [(t, what) for t, what in ((labels, "labels"), (other, "other")) if isinstance(t, torch.Tensor)]
-    devs = {t.device for t, _ in given if t.device.type == "cuda"}
-    if device is not None:
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is not None:
-            devs.add(device)
-    if len(devs) > 1:
-        raise ValueError("labels, other and device must name one GPU, got %s" % sorted(str(d) for d in devs))
-    for t, what in given:                          # (a CPU tensor is the last thing refused)
-        _check_device(t, what)
-    if device is not None and device.type != "cuda":
-        raise ValueError("device must be a ROCm GPU, got %s (there is no CPU fallback)" % device)
-    if devs:
-        return devs.pop()
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _on(maps, dev, batched):
     out = []
     for m in maps:
         t, code = _labels_on(m, dev)
         out.append((t if batched else t.unsqueeze(0), code))
     return out
-
-
-def _accumulate(lib, lab, ltype, oth, otype, K, M, capacity):
-    """One pass at the given capacity -> (workspace, its bytes, the header on the host).  Synchronises the host."""
-    N, H, W = lab.shape
-    dev = lab.device
-    nbytes = C.c_size_t()
-    B._check(lib.fslic_hip_overlap_workspace_size(N, capacity, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    B._check(lib.fslic_hip_overlap_accumulate(dev.index, _stream(dev), N, H, W, K, M, lab.data_ptr(), ltype, oth.data_ptr(), otype,
-                                              capacity, ws.data_ptr(), nbytes.value))
-    header = ws[:_HEADER_FIXED + 4 * N].cpu().numpy().view(np.uint32)
-    return ws, nbytes.value, header
 
 
 def label_overlap(labels, other, num_components, num_other, *, device=None, _start_capacity=None):
@@ -210,40 +160,28 @@ def label_overlap(labels, other, num_components, num_other, *, device=None, _sta
     H, W = _check_maps(labels, other)
     K = _check_count(num_components, "num_components")
     M = _check_count(num_other, "num_other")
-    limit = capacity_limit(K, M, H, W)
-    capacity = first_capacity(K, M)
-    if _start_capacity is not None:
-        capacity = _start_capacity
-        if isinstance(capacity, bool) or not isinstance(capacity, int) or not _MIN_CAPACITY <= capacity <= _MAX_CAPACITY \
-                or capacity & (capacity - 1):
-            raise ValueError("_start_capacity must be a power of two in [%d, 2^31]" % _MIN_CAPACITY)
-        limit = max(limit, capacity)
-    dev = _pick_device(labels, other, device)
+    capacity, limit = T.start_capacity(first_capacity(K, M), capacity_limit(K, M, H, W), _start_capacity)
+    dev = T.pick_device(((labels, "labels"), (other, "other")), device)
 
     lib = _lib()
     batched = labels.ndim == 3
     (lab, ltype), (oth, otype) = _on((labels, other), dev, batched)
     N = lab.shape[0]
+
+    def accumulate(capacity):
+        nbytes = C.c_size_t()
+        B._check(lib.fslic_hip_overlap_workspace_size(N, capacity, C.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        B._check(lib.fslic_hip_overlap_accumulate(dev.index, _stream(dev), N, H, W, K, M, lab.data_ptr(), ltype, oth.data_ptr(), otype,
+                                                  capacity, ws.data_ptr(), nbytes.value))
+        return ws, nbytes.value
+
+    def compact(ws, nbytes, capacity, P, keys, count):
+        B._check(lib.fslic_hip_overlap_compact(dev.index, _stream(dev), N, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
+                                               count.data_ptr(), P))
+
     with torch.cuda.device(dev):
-        while True:
-            ws, nbytes, header = _accumulate(lib, lab, ltype, oth, otype, K, M, capacity)
-            if header[0] == 0:
-                break
-            del ws
-            if capacity >= limit:
-                raise RuntimeError("fast_slic_amd: the pair table overflowed at its largest size (%d slots per frame)" % capacity)
-            capacity *= 2
-        P = int(header[_HEADER_FIXED // 4:].sum(dtype=np.int64))
-        offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        offsets[1:] = ws[_HEADER_FIXED:_HEADER_FIXED + 4 * N].view(torch.int32).to(torch.int64).cumsum(0)
-        keys = torch.empty(P, dtype=torch.int64, device=dev)
-        count = torch.empty(P, dtype=torch.int32, device=dev)
-        if P:
-            B._check(lib.fslic_hip_overlap_compact(dev.index, _stream(dev), N, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
-                                                   count.data_ptr(), P))
-            keys, order = torch.sort(keys)                              # unique keys (frame << 32 | a << 16 | b): one possible order
-            count = count[order]
-        pairs = torch.stack([(keys >> 16) & 0xFFFF, keys & 0xFFFF])
+        pairs, count, _, offsets, capacity = T.run(accumulate, compact, N, capacity, limit, dev)
     return OverlapTable(pairs, count, offsets, K, M, capacity, batched)
 
 
@@ -254,7 +192,7 @@ def boundary_match(labels, other, tolerance=0, *, device=None):
     H, W = _check_maps(labels, other)
     if isinstance(tolerance, bool) or not isinstance(tolerance, numbers.Integral) or not 0 <= int(tolerance) <= MAX_TOLERANCE:
         raise ValueError("tolerance must be an integer in [0, %d], got %r" % (MAX_TOLERANCE, tolerance))
-    dev = _pick_device(labels, other, device)
+    dev = T.pick_device(((labels, "labels"), (other, "other")), device)
 
     lib = _lib()
     batched = labels.ndim == 3

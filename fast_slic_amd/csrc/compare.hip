@@ -5,7 +5,7 @@
 //                       ((a << 16 | b) + 1) with one ballot per distinct key, whose popcount is the key's count.  The tile's
 //                       distinct keys live one per lane; at the end of the tile every such lane issues ONE update of the frame's
 //                       open-addressing table.  Keys past the 64th of a tile (noise maps) go to the table as they are met.
-//   k_overlap_compact : the occupied slots of every frame's table, densely, in no particular order
+//                       The table and its compact pass: pairtable.h, pairtable.hip.
 //   k_boundary_match  : boundary pixels of `other` that have a boundary pixel of `labels` within Chebyshev distance `tolerance`,
 //                       and the boundary pixels of either map.  Per (frame, tile of 64 columns x 32 rows) one wavefront.  A row of
 //                       boundary bits is one 64-bit ballot: the tile's columns and, for the halo of `tolerance` columns on either
@@ -17,47 +17,15 @@
 #include "device_common.h"
 #include "pool.h"
 #include "compare.h"
-#include <algorithm>
 
 namespace fslic {
 
 constexpr int kOverlapRows = 16;                 // rows of an overlap tile
 constexpr int kMatchRows = 32;                   // rows of a boundary match tile
-constexpr uint32_t kOverlapMaxProbe = 255u;      // (linear probing at a load of at most 1/2, as the graph's table)
 static_assert(kMatchRows + 2 * kMatchMaxTolerance <= 64, "one lane per row of a tile and its halo");
 
-static __device__ __forceinline__ uint32_t overlap_hash(uint32_t v) {
-    v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
-    return v;
-}
-
-// One update of frame n's table: finds or claims the slot of `key`, then adds.  The table is declared full -- more than half of it
-// taken, or a probe run longer than kOverlapMaxProbe -- by setting the header's flag; the update is then lost, and so is the whole
-// pass (the caller starts over with a larger table).
-static __device__ __forceinline__ void overlap_table_add(RagHeader* __restrict__ hdr, uint32_t* __restrict__ tkey, uint32_t* __restrict__ tcnt,
-                                                         int n, uint32_t cap_mask, uint32_t key, uint32_t cnt) {
-    const size_t base = (size_t)n * ((size_t)cap_mask + 1);
-    uint32_t h = overlap_hash(key) & cap_mask;
-    for (uint32_t probe = 0; probe <= min(cap_mask, kOverlapMaxProbe); ++probe) {
-        uint32_t cur = __hip_atomic_load(&tkey[base + h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0u) {
-            cur = atomicCAS(&tkey[base + h], 0u, key);
-            if (cur == 0u) {
-                if (atomicAdd(rag_counts(hdr) + n, 1u) > (cap_mask >> 1)) atomicExch(&hdr->overflow, 1u);     // more than capacity / 2 pairs
-                cur = key;
-            }
-        }
-        if (cur == key) {
-            atomicAdd(&tcnt[base + h], cnt);
-            return;
-        }
-        h = (h + 1u) & cap_mask;
-    }
-    atomicExch(&hdr->overflow, 1u);
-}
-
 template <class LA, class LB>
-__global__ __launch_bounds__(256) void k_overlap_tiles(const LA* __restrict__ labels, const LB* __restrict__ other, RagHeader* __restrict__ hdr,
+__global__ __launch_bounds__(256) void k_overlap_tiles(const LA* __restrict__ labels, const LB* __restrict__ other, PairHeader* __restrict__ hdr,
                                                        uint32_t* __restrict__ tkey, uint32_t* __restrict__ tcnt,
                                                        int N, int H, int W, uint32_t K, uint32_t M, uint32_t cap_mask) {
     const int lane = LANE();
@@ -67,10 +35,7 @@ __global__ __launch_bounds__(256) void k_overlap_tiles(const LA* __restrict__ la
     const unsigned long long nwaves = (unsigned long long)gridDim.x * 4ull;
     const size_t HW = (size_t)H * (size_t)W;
     for (unsigned long long t = (unsigned long long)blockIdx.x * 4ull + wave; t < ntiles; t += nwaves) {
-        // The pass is lost: leave.  A workgroup-scope load, which the caches may serve: every tile reads this one word, and at agent
-        // scope those reads queue up behind each other at the memory side (measured: 22 ns a tile, whatever the tile held).  A stale
-        // 0 only delays the leaving.
-        if (rfl(__hip_atomic_load(&hdr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0u) return;
+        if (pair_pass_lost(hdr)) return;
         const int n = (int)(t / per);
         const unsigned long long tt = t - (unsigned long long)n * per;
         const unsigned long long ty = tt / ntx, tx = tt - ty * ntx;
@@ -119,54 +84,11 @@ __global__ __launch_bounds__(256) void k_overlap_tiles(const LA* __restrict__ la
                         ecnt += cnt;
                     }
                 } else if (lane == 0) {                                    // the lanes are taken: this row's share goes out at once
-                    overlap_table_add(hdr, tkey, tcnt, n, cap_mask, cur, cnt);
+                    pair_table_add<false>(hdr, tkey, tcnt, nullptr, n, cap_mask, cur, cnt);
                 }
             }
         }
-        if (lane < D) overlap_table_add(hdr, tkey, tcnt, n, cap_mask, ent, ecnt);
-    }
-}
-
-constexpr int kCompactRounds = 16;               // slots a lane of k_overlap_compact looks at: one cursor add per 1024 slots
-
-__global__ __launch_bounds__(256) void k_overlap_compact(RagHeader* __restrict__ hdr, const uint32_t* __restrict__ tkey, const uint32_t* __restrict__ tcnt,
-                                                         unsigned long long capacity, unsigned long long total,
-                                                         unsigned long long* __restrict__ keys, int32_t* __restrict__ count,
-                                                         unsigned long long max_pairs) {
-    const int lane = LANE();
-    const unsigned long long nwaves = (unsigned long long)gridDim.x * 4ull, chunk = 64ull * kCompactRounds;
-    const unsigned long long nchunks = (total + chunk - 1) / chunk;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (unsigned long long c = (unsigned long long)blockIdx.x * 4ull + (threadIdx.x >> 6); c < nchunks; c += nwaves) {
-        uint32_t key[kCompactRounds];
-        uint32_t before[kCompactRounds];                                   // occupied slots of the chunk in earlier rounds
-        uint32_t sum = 0;
-#pragma unroll
-        for (int r = 0; r < kCompactRounds; ++r) {
-            const unsigned long long i = c * chunk + (unsigned long long)r * 64ull + lane;
-            key[r] = i < total ? tkey[i] : 0u;
-        }
-#pragma unroll
-        for (int r = 0; r < kCompactRounds; ++r) {
-            const unsigned long long taken = ballot(key[r] != 0u);
-            before[r] = sum + (uint32_t)__popcll(taken & below);
-            sum += (uint32_t)__popcll(taken);
-        }
-        if (sum == 0u) continue;
-        // one add of the cursor per chunk: the adds of one word queue up behind each other
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(&hdr->cursor, (unsigned long long)sum);
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-#pragma unroll
-        for (int r = 0; r < kCompactRounds; ++r) {
-            const unsigned long long i = c * chunk + (unsigned long long)r * 64ull + lane;
-            const unsigned long long pos = base + before[r];
-            if (key[r] != 0u && pos < max_pairs) {
-                keys[pos] = ((i / capacity) << 32) | (unsigned long long)(key[r] - 1u);
-                count[pos] = (int32_t)tcnt[i];
-            }
-        }
+        if (lane < D) pair_table_add<false>(hdr, tkey, tcnt, nullptr, n, cap_mask, ent, ecnt);
     }
 }
 
@@ -273,65 +195,30 @@ __global__ __launch_bounds__(256) void k_boundary_match(const LA* __restrict__ l
 }
 
 // ---- launches ---------------------------------------------------------------------------------
-static inline int compare_grid(unsigned long long items, unsigned long long per_block) {
-    const unsigned long long want = (items + per_block - 1) / per_block;
-    return (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, 256ull * 32ull));
-}
 static inline unsigned long long compare_tiles(int N, int H, int W, int rows) {
     return (unsigned long long)N * (((unsigned long long)W + 63ull) / 64ull) * (unsigned long long)((H + rows - 1) / rows);
 }
-struct OverlapTables {
-    RagHeader* hdr;
-    uint32_t *key, *cnt;
-};
-static inline OverlapTables overlap_tables(void* ws, int N, uint32_t capacity) {
-    char* p = reinterpret_cast<char*>(ws);
-    OverlapTables t;
-    t.hdr = reinterpret_cast<RagHeader*>(p);
-    t.key = reinterpret_cast<uint32_t*>(p + rag_header_bytes(N));
-    t.cnt = t.key + (size_t)N * (size_t)capacity;
-    return t;
-}
 
-// calls f(const LA*, const LB*) with the two maps as their label types
-template <class F>
-static void with_label_types(const void* labels, int label_type, const void* other, int other_type, F f) {
-    auto second = [&](auto* la) {
-        if (other_type == kLabelU16) f(la, reinterpret_cast<const uint16_t*>(other));
-        else if (other_type == kLabelI32) f(la, reinterpret_cast<const int32_t*>(other));
-        else f(la, reinterpret_cast<const int64_t*>(other));
-    };
-    if (label_type == kLabelU16) second(reinterpret_cast<const uint16_t*>(labels));
-    else if (label_type == kLabelI32) second(reinterpret_cast<const int32_t*>(labels));
-    else second(reinterpret_cast<const int64_t*>(labels));
-}
-
+// (the two maps as their label types: with_label_type of pool.h, nested)
 void launch_overlap_accumulate(const void* labels, int label_type, const void* other, int other_type, void* workspace,
                                int N, int H, int W, int K, int M, uint32_t capacity, hipStream_t st) {
-    const OverlapTables t = overlap_tables(workspace, N, capacity);
-    const dim3 grid(compare_grid(compare_tiles(N, H, W, kOverlapRows), 4)), block(256);
-    with_label_types(labels, label_type, other, other_type, [&](auto* la, auto* lb) {
-        using LA = std::remove_cv_t<std::remove_pointer_t<decltype(la)>>;
-        using LB = std::remove_cv_t<std::remove_pointer_t<decltype(lb)>>;
-        launch(k_overlap_tiles<LA, LB>, grid, block, 0, st, la, lb, t.hdr, t.key, t.cnt, N, H, W, (uint32_t)K, (uint32_t)M, capacity - 1u);
+    const PairTables t = pair_tables(workspace, N, capacity);
+    const dim3 grid(tile_grid(compare_tiles(N, H, W, kOverlapRows), 4)), block(256);
+    with_label_type(labels, label_type, [&](auto* la) {
+        with_label_type(other, other_type, [&](auto* lb) {
+            launch(k_overlap_tiles<std::decay_t<decltype(*la)>, std::decay_t<decltype(*lb)>>, grid, block, 0, st, la, lb, t.hdr, t.key, t.cnt,
+                   N, H, W, (uint32_t)K, (uint32_t)M, capacity - 1u);
+        });
     });
-}
-
-void launch_overlap_compact(void* workspace, int N, uint32_t capacity, unsigned long long* keys, int32_t* count,
-                            unsigned long long max_pairs, hipStream_t st) {
-    const OverlapTables t = overlap_tables(workspace, N, capacity);
-    const unsigned long long total = (unsigned long long)N * (unsigned long long)capacity;
-    launch(k_overlap_compact, dim3(compare_grid(total, 4ull * 64ull * kCompactRounds)), dim3(256), 0, st, t.hdr, t.key, t.cnt, (unsigned long long)capacity, total,
-           keys, count, max_pairs);
 }
 
 void launch_boundary_match(const void* labels, int label_type, const void* other, int other_type, unsigned long long* out,
                            int N, int H, int W, int tolerance, hipStream_t st) {
-    const dim3 grid(compare_grid(compare_tiles(N, H, W, kMatchRows) + 3ull * (unsigned long long)N, 4)), block(256);
-    with_label_types(labels, label_type, other, other_type, [&](auto* la, auto* lb) {
-        using LA = std::remove_cv_t<std::remove_pointer_t<decltype(la)>>;
-        using LB = std::remove_cv_t<std::remove_pointer_t<decltype(lb)>>;
-        launch(k_boundary_match<LA, LB>, grid, block, 0, st, la, lb, out, N, H, W, tolerance);
+    const dim3 grid(tile_grid(compare_tiles(N, H, W, kMatchRows) + 3ull * (unsigned long long)N, 4)), block(256);
+    with_label_type(labels, label_type, [&](auto* la) {
+        with_label_type(other, other_type, [&](auto* lb) {
+            launch(k_boundary_match<std::decay_t<decltype(*la)>, std::decay_t<decltype(*lb)>>, grid, block, 0, st, la, lb, out, N, H, W, tolerance);
+        });
     });
 }
 

@@ -81,11 +81,6 @@ void launch_edges(const CrfCall& c, const CrfTensorParams& dp, const CrfTensorBu
     else launch_crf_tensor_edges_given(dp, c.src.edge, c.src.links, c.members, c.offsets, c.indices, b.rows, b.edge, b.temporal, st);
 }
 
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("crf tensor launch: ") + hipGetErrorString(e));
-}
-
 // The bodies of the entries below.
 // The forward: the start, the edge pass and max_iter sweeps.  at(it) is where iterate `it` lives: sweep `it` reads at(it) and writes
 // at(it + 1).  `placed`: the starting q where it already is; NULL: the start launch writes it to at(0).
@@ -109,7 +104,7 @@ int run_forward(const CrfCall& c, const CrfTensorWorkspace& ws, const float* q0,
             q_in = at(it + 1);
         }
     }
-    return launch_status();
+    return launched("crf tensor launch");
 }
 
 int run_inference(const CrfCall& c, bool own, const float* q0, float* q_out) {
@@ -170,7 +165,7 @@ int run_backward(const CrfCall& c, bool own, const CrfTensorTransposed& tr, cons
     launch_crf_tensor_grad_close(dp, lists, q_all, max_iter > 0 ? nullptr : grad_q, dm[0], grad_unaries, grad_q0, max_iter == 0, st);
     if (grad_compat)
         launch_crf_tensor_grad_compat(slots, max_iter > 0 ? crf_tensor_sweep_shape(N, c.C, K).grid : 0, c.C, grad_compat, st);
-    return launch_status();
+    return launched("crf tensor launch");
 }
 
 }  // namespace
@@ -239,7 +234,7 @@ int fslic_hip_crf_tensor_energies(int device, void* stream, int N, int K, int te
     const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, nullptr);
     if (nnz > 0) HIPCHK(hipMemsetAsync(edge, 0, (size_t)nnz * sizeof(float), st));      // the entries outside every clamped row
     launch_crf_tensor_energies(dp, params, yxrgb, members, offsets, indices, edge, links, st);
-    return launch_status();
+    return launched("crf tensor launch");
 }
 
 int fslic_hip_crf_tensor_energies_backward_workspace_size(int N, int K, size_t* bytes) {
@@ -264,7 +259,7 @@ int fslic_hip_crf_tensor_energies_backward(int device, void* stream, int N, int 
     const CrfTensorParams dp = tensor_params(N, 1, K, temporal, nnz, nullptr);
     launch_crf_tensor_param_grad(dp, params, yxrgb, offsets, indices, nnz > 0 ? grad_edge : nullptr, grad_links,
                                  reinterpret_cast<double*>(workspace), grad_params, st);
-    return launch_status();
+    return launched("crf tensor launch");
 }
 
 int fslic_hip_crf_tensor_inference_energies(int device, void* stream, int N, int C, int K, int temporal, int max_iter, const float* compat,

@@ -47,6 +47,12 @@ static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsig
     add_kernel_node(*r, reinterpret_cast<void*>(kernel), grid, block, shmem, a, std::index_sequence_for<KArgs...>{});
 }
 
+// Blocks of a grid-stride kernel over `items` of which a block takes `per_block` a round: enough for one round, at most 32 a CU.
+static inline int tile_grid(unsigned long long items, unsigned long long per_block) {
+    const unsigned long long want = (items + per_block - 1) / per_block;
+    return (int)(want < 1ull ? 1ull : want > 256ull * 32ull ? 256ull * 32ull : want);
+}
+
 // Row-wise clear (hipMemset2DAsync on the stream, a memset node in the graph).
 static inline hipError_t clear_rows(void* dst, size_t pitch, size_t width_bytes, size_t rows, hipStream_t st) {
     GraphRecorder* r = current_recorder();

@@ -22,6 +22,14 @@ static __device__ __forceinline__ uint32_t canon(uint16_t v, uint32_t K) { retur
 static __device__ __forceinline__ uint32_t canon(int32_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
 static __device__ __forceinline__ uint32_t canon(int64_t v, uint32_t K) { return (unsigned long long)v < (unsigned long long)K ? (uint32_t)v : K; }
 
+// (launches) calls f(const L* map) with the map as its label type L; compare.hip nests two of them for its two maps
+template <class F>
+static inline void with_label_type(const void* map, int label_type, F f) {
+    if (label_type == kLabelU16) f(reinterpret_cast<const uint16_t*>(map));
+    else if (label_type == kLabelI32) f(reinterpret_cast<const int32_t*>(map));
+    else f(reinterpret_cast<const int64_t*>(map));
+}
+
 inline size_t pool_acc_bytes(int N, int C, int K, int reduce) {
     const size_t cells = (size_t)N * (size_t)C * (size_t)K;
     return reduce == kPoolMax ? cells * 8 : cells * 8 * kPoolLimbs;

@@ -280,11 +280,6 @@ __global__ __launch_bounds__(256) void k_unpool(const float* __restrict__ values
 }
 
 // ---- launches ---------------------------------------------------------------------------------
-static inline int pool_grid(unsigned long long items, unsigned long long per_block) {
-    const unsigned long long want = (items + per_block - 1) / per_block;
-    return (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, 256ull * 32ull));
-}
-
 // Work item = (tile, chunk of channels).  A wavefront walks its item's channels one after the other, so with few tiles (8 x 1280x720:
 // 7 200) whole-C items leave the chip with one long round of waves and a tail; the channels are cut into chunks until there are about
 // kPoolItems items (each chunk re-reads and re-analyses its tile's labels: 2 B/px per chunk, L2-served between neighbouring items).
@@ -292,7 +287,7 @@ static inline int pool_grid(unsigned long long items, unsigned long long per_blo
 constexpr unsigned long long kPoolItems = 256ull * 28ull * 4ull;
 constexpr int kPoolMinChunk = 4;
 template <class L>
-static void pool_tiles_as(const float* feat, const void* labels, int reduce, void* ws, int N, int C, int H, int W, int K, hipStream_t st) {
+static void pool_tiles_as(const float* feat, const L* lab, int reduce, void* ws, int N, int C, int H, int W, int K, hipStream_t st) {
     const unsigned long long tiles = (unsigned long long)N * (unsigned long long)((W + 63) / 64) * (unsigned long long)((H + kPoolRows - 1) / kPoolRows);
     const unsigned long long most = (unsigned long long)(C + kPoolMinChunk - 1) / kPoolMinChunk;     // chunks of at least kPoolMinChunk channels
     const int want = (int)std::min<unsigned long long>(most, std::max<unsigned long long>(1ull, (kPoolItems + tiles - 1) / tiles));
@@ -300,17 +295,14 @@ static void pool_tiles_as(const float* feat, const void* labels, int reduce, voi
     const unsigned long long items = tiles * (unsigned long long)nchunk;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws);
     uint32_t* counts = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + pool_acc_bytes(N, C, K, reduce));
-    const L* lab = reinterpret_cast<const L*>(labels);
     if (reduce == kPoolMax)
-        launch(k_pool_tiles<L, true>, dim3(pool_grid(items, 4)), dim3(256), 0, st, feat, lab, acc, counts, N, C, H, W, (uint32_t)K, nchunk, cchunk);
+        launch(k_pool_tiles<L, true>, dim3(tile_grid(items, 4)), dim3(256), 0, st, feat, lab, acc, counts, N, C, H, W, (uint32_t)K, nchunk, cchunk);
     else
-        launch(k_pool_tiles<L, false>, dim3(pool_grid(items, 4)), dim3(256), 0, st, feat, lab, acc, counts, N, C, H, W, (uint32_t)K, nchunk, cchunk);
+        launch(k_pool_tiles<L, false>, dim3(tile_grid(items, 4)), dim3(256), 0, st, feat, lab, acc, counts, N, C, H, W, (uint32_t)K, nchunk, cchunk);
 }
 void launch_pool_tiles(const float* feat, const void* labels, int label_type, int reduce, void* workspace,
                        int N, int C, int H, int W, int K, hipStream_t st) {
-    if (label_type == kLabelU16) pool_tiles_as<uint16_t>(feat, labels, reduce, workspace, N, C, H, W, K, st);
-    else if (label_type == kLabelI32) pool_tiles_as<int32_t>(feat, labels, reduce, workspace, N, C, H, W, K, st);
-    else pool_tiles_as<int64_t>(feat, labels, reduce, workspace, N, C, H, W, K, st);
+    with_label_type(labels, label_type, [&](auto* lab) { pool_tiles_as(feat, lab, reduce, workspace, N, C, H, W, K, st); });
 }
 
 void launch_pool_finalize(const void* workspace, int reduce, float* values, int32_t* counts, int32_t* argmax,
@@ -318,31 +310,25 @@ void launch_pool_finalize(const void* workspace, int reduce, float* values, int3
     const unsigned long long total = (unsigned long long)N * (unsigned long long)C * (unsigned long long)K;
     const unsigned long long* acc = reinterpret_cast<const unsigned long long*>(workspace);
     const uint32_t* cnt = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(workspace) + pool_acc_bytes(N, C, K, reduce));
-    launch(k_pool_finalize, dim3(pool_grid(total, 256)), dim3(256), 0, st, acc, cnt, reduce, values, counts, argmax, C, (uint32_t)K, total);
+    launch(k_pool_finalize, dim3(tile_grid(total, 256)), dim3(256), 0, st, acc, cnt, reduce, values, counts, argmax, C, (uint32_t)K, total);
 }
 
-template <class L, bool kArg>
-static void unpool_as(const float* values, const void* labels, const int32_t* argmax, float fill, float* out,
+template <bool kArg, class L>
+static void unpool_as(const float* values, const L* lab, const int32_t* argmax, float fill, float* out,
                       int N, int C, int H, int W, int K, hipStream_t st) {
     const unsigned long long HW = (unsigned long long)H * (unsigned long long)W, bpf = (HW + 1023ull) / 1024ull;
     const dim3 grid((unsigned)(bpf * (unsigned long long)N));
-    const L* lab = reinterpret_cast<const L*>(labels);
     if (HW % 4ull == 0ull && (reinterpret_cast<uintptr_t>(out) & 15u) == 0u)
         launch(k_unpool<L, kArg, true>, grid, dim3(256), 0, st, values, lab, argmax, fill, out, C, HW, (uint32_t)K, bpf);
     else
         launch(k_unpool<L, kArg, false>, grid, dim3(256), 0, st, values, lab, argmax, fill, out, C, HW, (uint32_t)K, bpf);
 }
-template <class L>
-static void unpool_label(const float* values, const void* labels, const int32_t* argmax, float fill, float* out,
-                         int N, int C, int H, int W, int K, hipStream_t st) {
-    if (argmax) unpool_as<L, true>(values, labels, argmax, fill, out, N, C, H, W, K, st);
-    else unpool_as<L, false>(values, labels, argmax, fill, out, N, C, H, W, K, st);
-}
 void launch_unpool(const float* values, const void* labels, int label_type, const int32_t* argmax, float fill, float* out,
                    int N, int C, int H, int W, int K, hipStream_t st) {
-    if (label_type == kLabelU16) unpool_label<uint16_t>(values, labels, argmax, fill, out, N, C, H, W, K, st);
-    else if (label_type == kLabelI32) unpool_label<int32_t>(values, labels, argmax, fill, out, N, C, H, W, K, st);
-    else unpool_label<int64_t>(values, labels, argmax, fill, out, N, C, H, W, K, st);
+    with_label_type(labels, label_type, [&](auto* lab) {
+        if (argmax) unpool_as<true>(values, lab, argmax, fill, out, N, C, H, W, K, st);
+        else unpool_as<false>(values, lab, argmax, fill, out, N, C, H, W, K, st);
+    });
 }
 
 }  // namespace fslic

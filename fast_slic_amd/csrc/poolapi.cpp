@@ -16,10 +16,6 @@ int check_common(int device, int N, int C, int K, int reduce) {
     if ((long long)N * C * K >= (1ll << 40)) return fail(FSLIC_E_INVALID, "N * C * K must be below 2^40");
     return FSLIC_OK;
 }
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("pool launch: ") + hipGetErrorString(e));
-}
 
 }  // namespace
 
@@ -45,7 +41,7 @@ int fslic_hip_pool(int device, void* stream, int N, int C, int H, int W, int K, 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(hipMemsetAsync(workspace, 0, need, st));
     launch_pool_tiles(features, labels, label_type, reduce, workspace, N, C, H, W, K, st);
-    return launched();
+    return launched("pool launch");
 }
 
 int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int reduce, const void* workspace, size_t workspace_bytes,
@@ -58,7 +54,7 @@ int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int r
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     launch_pool_finalize(workspace, reduce, values, counts, argmax, N, C, K, reinterpret_cast<hipStream_t>(stream));
-    return launched();
+    return launched("pool launch");
 }
 
 int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
@@ -69,7 +65,7 @@ int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     launch_unpool(values, labels, label_type, argmax, fill, out, N, C, H, W, K, reinterpret_cast<hipStream_t>(stream));
-    return launched();
+    return launched("pool launch");
 }
 
 }  // extern "C"

@@ -7,53 +7,17 @@
 //                   the contrast.  The tile's distinct keys live one per lane (lane d: key d, its count, its C sums); at the end of the
 //                   tile every such lane issues ONE update of the frame's open-addressing table.  Keys past the 64th of a tile (noise
 //                   maps) are sent to the table as they are met, one update per (row, key).
-//   k_rag_compact : the occupied slots of every frame's table, densely, in no particular order
+// The table and its compact pass: pairtable.h, pairtable.hip.
 // All integer work: counts are 32-bit integer adds, contrast sums 64-bit integer adds, so neither the order in which tiles arrive nor
 // the capacity of the table can change a bit of the result.  Labels are checked against K before they form a key.
 #include "device_common.h"
 #include "pool.h"
 #include "rag.h"
-#include <algorithm>
 
 namespace fslic {
 
 constexpr int kRagRows = 16;                 // rows of a tile
 constexpr int kRagPitch = 66;                // 64 columns and one halo column on either side
-constexpr uint32_t kRagMaxProbe = 255u;      // (linear probing at a load of at most 1/2: runs of a few dozen slots are already rare)
-
-static __device__ __forceinline__ uint32_t rag_hash(uint32_t v) {
-    v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
-    return v;
-}
-
-// One update of frame n's table: finds or claims the slot of `key`, then adds.  The table is declared full -- more than half of it
-// taken, or a probe run longer than kRagMaxProbe -- by setting the header's flag; the update is then lost, and so is the whole pass
-// (the caller starts over with a larger table).
-static __device__ __forceinline__ void rag_table_add(RagHeader* __restrict__ hdr, uint32_t* __restrict__ tkey, uint32_t* __restrict__ tcnt,
-                                                     unsigned long long* __restrict__ tsum, int n, uint32_t cap_mask, int C,
-                                                     uint32_t key, uint32_t cnt, const uint32_t (&s)[kRagMaxChannels]) {
-    const size_t base = (size_t)n * ((size_t)cap_mask + 1);
-    uint32_t h = rag_hash(key) & cap_mask;
-    for (uint32_t probe = 0; probe <= min(cap_mask, kRagMaxProbe); ++probe) {
-        uint32_t cur = __hip_atomic_load(&tkey[base + h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0u) {
-            cur = atomicCAS(&tkey[base + h], 0u, key);
-            if (cur == 0u) {
-                if (atomicAdd(rag_counts(hdr) + n, 1u) > (cap_mask >> 1)) atomicExch(&hdr->overflow, 1u);     // more than capacity / 2 pairs
-                cur = key;
-            }
-        }
-        if (cur == key) {
-            atomicAdd(&tcnt[base + h], cnt);
-#pragma unroll
-            for (int c = 0; c < kRagMaxChannels; ++c)                    // (a run-time index would send s[] to scratch memory)
-                if (c < C) atomicAdd(&tsum[(base + h) * (size_t)C + c], (unsigned long long)s[c]);
-            return;
-        }
-        h = (h + 1u) & cap_mask;
-    }
-    atomicExch(&hdr->overflow, 1u);
-}
 
 // the C bytes of one pixel in one word (channel c in bits 8c .. 8c + 7)
 static __device__ __forceinline__ uint32_t load_pixel(const uint8_t* __restrict__ p, int C, bool word) {
@@ -72,7 +36,7 @@ static __device__ __forceinline__ uint32_t absdiff2(uint32_t a, uint32_t b, int 
 }
 
 template <class L, bool kImg, bool k8>
-__global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels, const uint8_t* __restrict__ image, RagHeader* __restrict__ hdr,
+__global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels, const uint8_t* __restrict__ image, PairHeader* __restrict__ hdr,
                                                    uint32_t* __restrict__ tkey, uint32_t* __restrict__ tcnt, unsigned long long* __restrict__ tsum,
                                                    int N, int C, int H, int W, uint32_t K, uint32_t cap_mask, bool word) {
     __shared__ uint32_t s_lab[4][kRagRows + 1][kRagPitch];                 // K: no label (outside [0, K), past the image)
@@ -87,7 +51,7 @@ __global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels,
     const unsigned long long nwaves = (unsigned long long)gridDim.x * 4ull;
     const size_t HW = (size_t)H * (size_t)W;
     for (unsigned long long t = (unsigned long long)blockIdx.x * 4ull + wave; t < ntiles; t += nwaves) {
-        if (rfl(__hip_atomic_load(&hdr->overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u) return;   // the pass is lost: leave
+        if (pair_pass_lost(hdr)) return;
         const int n = (int)(t / per);
         const unsigned long long tt = t - (unsigned long long)n * per;
         const int ty = (int)(tt / ntx), tx = (int)(tt - (unsigned long long)ty * ntx);
@@ -132,7 +96,7 @@ __global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels,
         }
         wave_lds_sync();
         // lane d: the tile's d-th distinct key, its pixel pairs and its channel sums
-        uint32_t ent = 0, ecnt = 0, esum[kRagMaxChannels] = {0, 0, 0, 0};
+        uint32_t ent = 0, ecnt = 0, esum[kPairMaxChannels] = {0, 0, 0, 0};
         int D = 0;
         for (int r = 0; r < nrows; ++r) {
             const uint32_t a = sl[r][lane + 1];
@@ -185,7 +149,7 @@ __global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels,
                     }
                     pend &= ~((m ? 1u : 0u) << s);
                 }
-                uint32_t add[kRagMaxChannels] = {0, 0, 0, 0};
+                uint32_t add[kPairMaxChannels] = {0, 0, 0, 0};
                 if (kImg) {
                     const uint32_t r01 = wave_reduce_add<uint32_t>(v01);
                     add[0] = r01 & 0xFFFFu;
@@ -204,72 +168,24 @@ __global__ __launch_bounds__(256) void k_rag_tiles(const L* __restrict__ labels,
                         ent = cur;
                         ecnt += cnt;
 #pragma unroll
-                        for (int c = 0; c < kRagMaxChannels; ++c) esum[c] += add[c];
+                        for (int c = 0; c < kPairMaxChannels; ++c) esum[c] += add[c];
                     }
                 } else if (lane == 0) {                                    // the lanes are taken: this row's share goes out at once
-                    rag_table_add(hdr, tkey, tcnt, tsum, n, cap_mask, C, cur, cnt, add);
+                    pair_table_add<true>(hdr, tkey, tcnt, tsum, n, cap_mask, cur, cnt, C, add);
                 }
             }
         }
-        if (lane < D) rag_table_add(hdr, tkey, tcnt, tsum, n, cap_mask, C, ent, ecnt, esum);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_rag_compact(RagHeader* __restrict__ hdr, const uint32_t* __restrict__ tkey, const uint32_t* __restrict__ tcnt,
-                                                     const unsigned long long* __restrict__ tsum, int C, unsigned long long capacity,
-                                                     unsigned long long total, unsigned long long* __restrict__ keys,
-                                                     int32_t* __restrict__ boundary, unsigned long long* __restrict__ contrast,
-                                                     unsigned long long max_edges) {
-    const int lane = LANE();
-    const unsigned long long stride = (unsigned long long)gridDim.x * 256ull;
-    const unsigned long long rounds = (total + stride - 1) / stride;        // every lane of a wavefront makes the same number of rounds
-    unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x;
-    for (unsigned long long it = 0; it < rounds; ++it, i += stride) {
-        const uint32_t key = i < total ? tkey[i] : 0u;
-        const unsigned long long taken = ballot(key != 0u);
-        if (!taken) continue;
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(&hdr->cursor, (unsigned long long)__popcll(taken));
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-        const unsigned long long pos = base + (unsigned long long)__popcll(taken & ((1ull << lane) - 1ull));
-        if (key != 0u && pos < max_edges) {
-            keys[pos] = ((i / capacity) << 32) | (unsigned long long)key;
-            boundary[pos] = (int32_t)tcnt[i];
-            if (contrast)
-                for (int c = 0; c < C; ++c) contrast[pos * (unsigned long long)C + c] = tsum[i * (unsigned long long)C + c];
-        }
+        if (lane < D) pair_table_add<true>(hdr, tkey, tcnt, tsum, n, cap_mask, ent, ecnt, C, esum);
     }
 }
 
 // ---- launches ---------------------------------------------------------------------------------
-static inline int rag_grid(unsigned long long items, unsigned long long per_block) {
-    const unsigned long long want = (items + per_block - 1) / per_block;
-    return (int)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, 256ull * 32ull));
-}
-struct RagTables {
-    RagHeader* hdr;
-    uint32_t *key, *cnt;
-    unsigned long long* sum;
-};
-static inline RagTables rag_tables(void* ws, int N, uint32_t capacity) {
-    char* p = reinterpret_cast<char*>(ws);
-    const size_t slots = (size_t)N * (size_t)capacity;
-    RagTables t;
-    t.hdr = reinterpret_cast<RagHeader*>(p);
-    t.key = reinterpret_cast<uint32_t*>(p + rag_header_bytes(N));
-    t.cnt = t.key + slots;
-    t.sum = reinterpret_cast<unsigned long long*>(t.cnt + slots);
-    return t;
-}
-
 template <class L>
-static void rag_tiles_as(const void* labels, const uint8_t* image, void* ws, int N, int C, int H, int W, int K, int connectivity,
+static void rag_tiles_as(const L* lab, const uint8_t* image, void* ws, int N, int C, int H, int W, int K, int connectivity,
                          uint32_t capacity, hipStream_t st) {
     const unsigned long long tiles = (unsigned long long)N * (unsigned long long)((W + 63) / 64) * (unsigned long long)((H + kRagRows - 1) / kRagRows);
-    const RagTables t = rag_tables(ws, N, capacity);
-    const L* lab = reinterpret_cast<const L*>(labels);
-    const dim3 grid(rag_grid(tiles, 4)), block(256);
+    const PairTables t = pair_tables(ws, N, capacity);
+    const dim3 grid(tile_grid(tiles, 4)), block(256);
     const bool word = C == 4 && (reinterpret_cast<uintptr_t>(image) & 3u) == 0u;      // a pixel is one aligned 32-bit word
     const uint32_t mask = capacity - 1u;
 #define FSLIC_RAG_LAUNCH(IMG, EIGHT) \
@@ -285,17 +201,7 @@ static void rag_tiles_as(const void* labels, const uint8_t* image, void* ws, int
 }
 void launch_rag_accumulate(const void* labels, int label_type, const uint8_t* image, void* workspace,
                            int N, int C, int H, int W, int K, int connectivity, uint32_t capacity, hipStream_t st) {
-    if (label_type == kLabelU16) rag_tiles_as<uint16_t>(labels, image, workspace, N, C, H, W, K, connectivity, capacity, st);
-    else if (label_type == kLabelI32) rag_tiles_as<int32_t>(labels, image, workspace, N, C, H, W, K, connectivity, capacity, st);
-    else rag_tiles_as<int64_t>(labels, image, workspace, N, C, H, W, K, connectivity, capacity, st);
-}
-
-void launch_rag_compact(void* workspace, int N, int C, uint32_t capacity, unsigned long long* keys, int32_t* boundary,
-                        unsigned long long* contrast, unsigned long long max_edges, hipStream_t st) {
-    const RagTables t = rag_tables(workspace, N, capacity);
-    const unsigned long long total = (unsigned long long)N * (unsigned long long)capacity;
-    launch(k_rag_compact, dim3(rag_grid(total, 256)), dim3(256), 0, st, t.hdr, t.key, t.cnt, t.sum, C, (unsigned long long)capacity, total,
-           keys, boundary, contrast, max_edges);
+    with_label_type(labels, label_type, [&](auto* lab) { rag_tiles_as(lab, image, workspace, N, C, H, W, K, connectivity, capacity, st); });
 }
 
 }  // namespace fslic

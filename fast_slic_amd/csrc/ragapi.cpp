@@ -9,19 +9,11 @@ using namespace fslic;
 namespace {
 
 int check_tables(int device, int N, int K, int C, long long capacity) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
-    if (N < 1) return fail(FSLIC_E_INVALID, "N must be positive");
+    const int rc = check_pair_table(device, N, capacity);
+    if (rc) return rc;
     if (K < 1 || K > 65534) return fail(FSLIC_E_INVALID, "K must be in [1, 65534]");
-    if (C < 0 || C > kRagMaxChannels) return fail(FSLIC_E_INVALID, "C must be in [0, 4] (0: no image)");
-    if (capacity < (long long)kRagMinCapacity || capacity > (long long)kRagMaxCapacity || (capacity & (capacity - 1)) != 0)
-        return fail(FSLIC_E_INVALID, "capacity must be a power of two in [64, 2^31]");
-    if ((long long)N * capacity >= (1ll << 40)) return fail(FSLIC_E_INVALID, "N * capacity must be below 2^40");
+    if (C < 0 || C > kPairMaxChannels) return fail(FSLIC_E_INVALID, "C must be in [0, 4] (0: no image)");
     return FSLIC_OK;
-}
-
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FSLIC_OK : fail(FSLIC_E_HIP, std::string("rag launch: ") + hipGetErrorString(e));
 }
 
 }  // namespace
@@ -32,7 +24,7 @@ int fslic_hip_rag_workspace_size(int N, int K, int C, long long capacity, size_t
     if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     const int rc = check_tables(0, N, K, C, capacity);
     if (rc) return rc;
-    *bytes = rag_workspace_bytes(N, C, (uint32_t)capacity);
+    *bytes = pair_workspace_bytes(N, C, (uint32_t)capacity);
     return FSLIC_OK;
 }
 
@@ -44,14 +36,14 @@ int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int 
     if (connectivity != 4 && connectivity != 8) return fail(FSLIC_E_INVALID, "connectivity must be 4 or 8");
     if (!labels || !workspace) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if ((image != nullptr) != (C > 0)) return fail(FSLIC_E_INVALID, "an image needs C in [1, 4], no image needs C == 0");
-    const size_t need = rag_workspace_bytes(N, C, (uint32_t)capacity);
+    const size_t need = pair_workspace_bytes(N, C, (uint32_t)capacity);
     if (workspace_bytes < need) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIPCHK(hipMemsetAsync(workspace, 0, need, st));
     launch_rag_accumulate(labels, label_type, image, workspace, N, C, H, W, K, connectivity, (uint32_t)capacity, st);
-    return launched();
+    return launched("rag launch");
 }
 
 int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capacity, void* workspace, size_t workspace_bytes,
@@ -61,14 +53,14 @@ int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capa
     if (!workspace || !keys || !boundary) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (contrast && C == 0) return fail(FSLIC_E_INVALID, "contrast needs C in [1, 4]");
     if (max_edges < 0) return fail(FSLIC_E_INVALID, "max_edges must be >= 0");
-    if (workspace_bytes < rag_workspace_bytes(N, C, (uint32_t)capacity)) return fail(FSLIC_E_INVALID, "workspace too small");
+    if (workspace_bytes < pair_workspace_bytes(N, C, (uint32_t)capacity)) return fail(FSLIC_E_INVALID, "workspace too small");
     DeviceScope scope;
     if ((rc = scope.enter(device))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(workspace) + offsetof(RagHeader, cursor), 0, sizeof(unsigned long long), st));
-    launch_rag_compact(workspace, N, C, (uint32_t)capacity, reinterpret_cast<unsigned long long*>(keys), boundary,
-                       reinterpret_cast<unsigned long long*>(contrast), (unsigned long long)max_edges, st);
-    return launched();
+    HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(workspace) + offsetof(PairHeader, cursor), 0, sizeof(unsigned long long), st));
+    launch_pair_compact(workspace, N, C, (uint32_t)capacity, 0u, true, reinterpret_cast<unsigned long long*>(keys), boundary,
+                        reinterpret_cast<unsigned long long*>(contrast), (unsigned long long)max_edges, st);
+    return launched("rag launch");
 }
 
 }  // extern "C"

@@ -18,14 +18,13 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _binding as B
-from .pool import _check_device, _check_labels, _check_num_components, _labels_on, _stream
+from . import _binding as B, _pairtable as T
+from ._pairtable import _MAX_CAPACITY, _pow2_at_least
+from .pool import _check_num_components, _labels_on, _stream
 
 __all__ = ["superpixel_graph", "SuperpixelGraph"]
 
 MAX_CHANNELS = 4
-_HEADER_FIXED = 16          # bytes of the workspace header before the per-frame pair counts (csrc/rag.h)
-_MIN_CAPACITY, _MAX_CAPACITY = 64, 1 << 31
 
 
 def _lib():
@@ -33,10 +32,6 @@ def _lib():
     if not hasattr(lib, "fslic_hip_rag_accumulate"):
         raise RuntimeError("fast_slic_amd: the loaded library has no region adjacency graph entry points; rebuild it")
     return lib
-
-
-def _pow2_at_least(v):
-    return 1 << max(0, int(v) - 1).bit_length()
 
 
 def first_capacity(K):
@@ -109,39 +104,6 @@ def _check_image(image, shape):
         raise ValueError("image must have 1 to %d channels, got C = %d" % (MAX_CHANNELS, image.shape[-1]))
 
 
-def _pick_device(labels, image, device):
-    """The GPU of the result.  Torch tensors must already be there (and on the same one); numpy arrays are uploaded."""
-    given = [(t, what) for t, what in ((labels, "labels"), (image, "image")) if isinstance(t, torch.Tensor)]
-    for t, what in given:
-        _check_device(t, what)
-    devs = {t.device for t, _ in given}
-    if device is not None:
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise ValueError("device must be a ROCm GPU, got %s (there is no CPU fallback)" % device)
-        if device.index is not None:
-            devs.add(device)
-    if len(devs) > 1:
-        raise ValueError("labels, image and device must name one GPU, got %s" % sorted(str(d) for d in devs))
-    if devs:
-        return devs.pop()
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _accumulate(lib, lab, ltype, img, K, connectivity, capacity):
-    """One pass at the given capacity -> (workspace, its bytes, the header on the host).  Synchronises the host."""
-    N, H, W = lab.shape
-    Cc = img.shape[-1] if img is not None else 0
-    dev = lab.device
-    nbytes = C.c_size_t()
-    B._check(lib.fslic_hip_rag_workspace_size(N, K, Cc, capacity, C.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    B._check(lib.fslic_hip_rag_accumulate(dev.index, _stream(dev), N, H, W, K, connectivity, lab.data_ptr(), ltype,
-                                          img.data_ptr() if img is not None else None, Cc, capacity, ws.data_ptr(), nbytes.value))
-    header = ws[:_HEADER_FIXED + 4 * N].cpu().numpy().view(np.uint32)
-    return ws, nbytes.value, header
-
-
 def superpixel_graph(labels, num_components, connectivity=4, image=None, *, device=None, _start_capacity=None):
     """The region adjacency graph of `labels` ([H, W] or [N, H, W]; int16, int32 or int64; numpy or torch) as a SuperpixelGraph.
 
@@ -154,13 +116,7 @@ def superpixel_graph(labels, num_components, connectivity=4, image=None, *, devi
     grow: the first table has a power of two >= 8 K slots per frame (at least 1024), which holds any planar map; a map with more
     distinct pairs (a noise map) doubles it and starts over, up to a table that holds every possible pair.  The result does not
     depend on the table's size.  `_start_capacity` (testing) sets the first table's slots per frame."""
-    if not isinstance(labels, (np.ndarray, torch.Tensor)):
-        raise ValueError("labels must be a numpy array or a torch tensor")
-    if labels.ndim not in (2, 3):
-        raise ValueError("labels must be [H, W] or [N, H, W], got shape %s" % (tuple(labels.shape),))
-    if 0 in labels.shape:
-        raise ValueError("labels must not be empty, got shape %s" % (tuple(labels.shape),))
-    _check_labels(labels, labels.shape)
+    T.check_label_map(labels, "labels")
     H, W = (int(v) for v in labels.shape[-2:])
     if H * W >= 1 << 29:
         raise ValueError("H * W must be below 2^29")
@@ -170,15 +126,8 @@ def superpixel_graph(labels, num_components, connectivity=4, image=None, *, devi
     connectivity = int(connectivity)
     if image is not None:
         _check_image(image, labels.shape)
-    limit = capacity_limit(K, H, W, connectivity)
-    capacity = first_capacity(K)
-    if _start_capacity is not None:
-        capacity = _start_capacity
-        if isinstance(capacity, bool) or not isinstance(capacity, int) or not _MIN_CAPACITY <= capacity <= _MAX_CAPACITY \
-                or capacity & (capacity - 1):
-            raise ValueError("_start_capacity must be a power of two in [%d, 2^31]" % _MIN_CAPACITY)
-        limit = max(limit, capacity)
-    dev = _pick_device(labels, image, device)
+    capacity, limit = T.start_capacity(first_capacity(K), capacity_limit(K, H, W, connectivity), _start_capacity)
+    dev = T.pick_device(((labels, "labels"), (image, "image")), device)
 
     lib = _lib()
     batched = labels.ndim == 3
@@ -190,29 +139,22 @@ def superpixel_graph(labels, num_components, connectivity=4, image=None, *, devi
         img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(device=dev).contiguous()
         if not batched:
             img = img.unsqueeze(0)
-    N = lab.shape[0]
-    Cc = img.shape[-1] if img is not None else 0
+    N, Cc = lab.shape[0], img.shape[-1] if img is not None else 0
+
+    def accumulate(capacity):
+        nbytes = C.c_size_t()
+        B._check(lib.fslic_hip_rag_workspace_size(N, K, Cc, capacity, C.byref(nbytes)))
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        B._check(lib.fslic_hip_rag_accumulate(dev.index, _stream(dev), N, H, W, K, connectivity, lab.data_ptr(), ltype,
+                                              img.data_ptr() if img is not None else None, Cc, capacity, ws.data_ptr(), nbytes.value))
+        return ws, nbytes.value
+
+    def compact(ws, nbytes, capacity, E, keys, boundary, contrast=None):
+        B._check(lib.fslic_hip_rag_compact(dev.index, _stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
+                                           boundary.data_ptr(), contrast.data_ptr() if contrast is not None else None, E))
+
     with torch.cuda.device(dev):
-        while True:
-            ws, nbytes, header = _accumulate(lib, lab, ltype, img, K, connectivity, capacity)
-            if header[0] == 0:
-                break
-            del ws
-            if capacity >= limit:
-                raise RuntimeError("fast_slic_amd: the pair table overflowed at its largest size (%d slots per frame)" % capacity)
-            capacity *= 2
-        E = int(header[_HEADER_FIXED // 4:].sum(dtype=np.int64))
-        offsets = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        offsets[1:] = ws[_HEADER_FIXED:_HEADER_FIXED + 4 * N].view(torch.int32).to(torch.int64).cumsum(0)
-        keys = torch.empty(E, dtype=torch.int64, device=dev)
-        boundary = torch.empty(E, dtype=torch.int32, device=dev)
-        contrast = torch.empty((E, Cc), dtype=torch.int64, device=dev) if img is not None else None
-        if E:
-            B._check(lib.fslic_hip_rag_compact(dev.index, _stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
-                                               boundary.data_ptr(), contrast.data_ptr() if contrast is not None else None, E))
-            keys, order = torch.sort(keys)                              # unique keys (frame << 32 | a << 16 | b): one possible order
-            boundary = boundary[order]
-            if contrast is not None:
-                contrast = contrast[order]
-        edge_index = torch.stack([(keys >> 16) & 0xFFFF, keys & 0xFFFF])
+        edge_index, boundary, extra, offsets, capacity = T.run(accumulate, compact, N, capacity, limit, dev,
+                                                               [((Cc,), torch.int64)] if img is not None else [])
+    contrast = extra[0] if extra else None
     return SuperpixelGraph(edge_index, boundary, contrast, offsets, K, capacity)

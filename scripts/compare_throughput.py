@@ -68,7 +68,7 @@ def trace(out, reps):
             rows += [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in csv.DictReader(f)]
     rows.sort(key=lambda r: r[1])
     result = {}
-    for name in ("k_overlap_tiles", "k_overlap_compact", "k_boundary_match", "k_rag_tiles", "k_rag_compact"):
+    for name in ("k_overlap_tiles", "k_pair_compact<false>", "k_boundary_match", "k_rag_tiles", "k_pair_compact<true>"):
         d = [(e - s) / 1e3 for n, s, e in rows if name in n]
         parts = {name: d}
         if name == "k_boundary_match":

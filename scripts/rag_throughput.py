@@ -6,7 +6,7 @@ Engine.get_connectivity on the same maps with the labels left in HBM (wall clock
     python scripts/rag_throughput.py [--reps 20] [--json out.json]
 
 Label maps are Slic's on synthetic frames (one per frame of the batch).  Kernel names for a separate
-`rocprofv3 --kernel-trace --stats` run: k_rag_tiles, k_rag_compact, k_adjacent_pairs."""
+`rocprofv3 --kernel-trace --stats` run: k_rag_tiles, k_pair_compact<true>, k_adjacent_pairs."""
 import argparse
 import ctypes as C
 import json

@@ -191,6 +191,23 @@ def test_small_start_capacity_grows_to_the_same_result():
     assert 64 < g.capacity <= 2048
 
 
+# ---- tables that end inside a chunk of the compact pass (1024 slots) ----
+@pytest.mark.parametrize("H,W,K,connectivity,Cc,capacity", [
+    (17, 65, 8, 8, 3, 64),         # 3 x 64 slots: one partial chunk that holds the three frames
+    (33, 130, 20, 4, 4, 512),      # 3 x 512 slots: one chunk and a half, frame 1 straddles the chunks; C = 4: pixels read as words
+])
+def test_table_ends_inside_a_chunk(H, W, K, connectivity, Cc, capacity):
+    rng = np.random.default_rng(H * 1000 + W)
+    lab = rng.integers(0, K, (3, H, W)).astype(np.int16)
+    image = rng.integers(0, 256, (3, H, W, Cc), dtype=np.uint8)
+    ref = R.graph(lab, K, connectivity, image)
+    pairs = K * (K - 1) // 2
+    assert ref["offsets"].tolist() == [0, pairs, 2 * pairs, 3 * pairs] and 2 * pairs <= capacity      # every pair, in a table that holds them
+    g = superpixel_graph(lab, K, connectivity=connectivity, image=image, _start_capacity=capacity)
+    assert g.capacity == capacity
+    assert_graph(g, ref, "%d slots a frame" % capacity)
+
+
 # ---- batch ----
 def test_batch_of_three_maps():
     cases = [slic_case(240, 320, 150, seed=s) for s in range(3)]
