@@ -30,6 +30,49 @@ CASES = [
 CASE_NAMES = [c["name"] for c in CASES]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 
+# The edges of crf.hip (tests/golden/crf_edge_cases.npz): more classes than the LDS form holds (256) and exactly that many, one class,
+# window sizes on the block edges of the sweep (64 nodes) and of the edge kernel (256), the clamp of the class sum, neighbour rows of
+# thousands of entries, and a window that grows, shrinks and slides between inferences.
+# With the default params and make_inputs' random centres and colours every pairwise energy underflows against the unaries, so q
+# would not depend on the q before it.  WIDE makes the messages count: a stale q or another summation order changes the result.
+WIDE = [1.5, 2.0, 150.0, 120.0, 600.0, 0.5, 400.0]
+# further graphs: "hub" ("random", but nodes 0 and K-1 list HUB_ENTRIES neighbours each, duplicates and self-loops among them)
+HUB_ENTRIES = 3000
+# "offsets": every node's unaries (uniform in [0, 4)) are raised by one of these, so that the class sum spans everything from O(1) to
+# 0: below 1e-5 (clamped: the row no longer sums to 1), expf results that are denormal, rows of zeros.
+CLAMP_OFFSETS = [0.0, 9.0, 12.5, 40.0, 95.0, 104.0, 110.0]
+# "script": operations after the T initial frames are pushed and initialize()d (see replay); q of every live frame is recorded after
+# each "infer".  This one: grow with q on the device (2 -> 3), a read, two pops in a row (-> 1), three pushes (-> 4), a reset of one
+# frame, then a pop inside the capacity of 4 that shifts every frame.
+WINDOW_SCRIPT = [("infer", 2), ("push", 2), ("infer", 2), ("read", 1), ("pop",), ("pop",), ("infer", 1), ("push", 3), ("push", 4),
+                 ("push", 5), ("infer", 2), ("reset", 1), ("infer", 1), ("pop",), ("infer", 2)]
+
+
+def _block_edge(name, K, T):
+    return dict(name=name, C=2, K=K, T=T, iters=[2], graph="random", umode=["unary"], init="initialize", params=WIDE)
+
+
+EDGE_CASES = [
+    dict(name="c257_k65_t2_long", C=257, K=65, T=2, iters=[3], graph="long", umode=["unary", "mask"], init="initialize",
+         params=[0.375, 1.25, 150.0, 120.0, 600.0, 0.125, 400.0], compat=[0.25 + 0.125 * (c % 11) for c in range(257)]),
+    dict(name="c256_k33_t1", C=256, K=33, T=1, iters=[2], graph="random", umode=["unary"], init="initialize", params=WIDE),
+    dict(name="c255_k33_t1", C=255, K=33, T=1, iters=[2], graph="random", umode=["mask"], init="initialize", params=WIDE),
+    dict(name="c300_k33_t3_slide", C=300, K=33, T=3, iters=[2, 2], graph="random", umode=["mask", "unbiased", "unary"],
+         init="initialize", slide=True, params=WIDE),
+    dict(name="c1_k70_t2", C=1, K=70, T=2, iters=[3], graph="random", umode=["unary", "proba", "unbiased"], init="initialize",
+         params=WIDE),
+    dict(name="clamp_c3_k130_t3", C=3, K=130, T=3, iters=[4], graph="random", umode=["unary"], init="initialize",
+         offsets=CLAMP_OFFSETS),
+    _block_edge("n63", 63, 1), _block_edge("n64", 64, 1), _block_edge("n65", 65, 1),
+    _block_edge("n255", 85, 3), _block_edge("n256", 128, 2), _block_edge("n257", 257, 1),
+    dict(name="hub_c5_k200_t2", C=5, K=200, T=2, iters=[3], graph="hub", umode=["unary", "mask"], init="initialize",
+         params=[0.004, 0.05, 150.0, 120.0, 600.0, 0.002, 400.0]),
+    dict(name="window_c3_k40", C=3, K=40, T=2, iters=[2], graph="random", umode=["unary", "mask", "proba"], init="initialize",
+         params=WIDE, script=WINDOW_SCRIPT),
+]
+EDGE_CASE_NAMES = [c["name"] for c in EDGE_CASES]
+EDGE_CASE_BY_NAME = {c["name"]: c for c in EDGE_CASES}
+
 
 def _csr(lists):
     off = np.zeros(len(lists) + 1, np.int64)
@@ -43,6 +86,9 @@ def make_inputs(case, rng, graph_npz=None, chain=None):
     from fast_slic_amd._binding import CLUSTER_DTYPE
     C, K, T = case["C"], case["K"], case["T"]
     nframes = T + (1 if case.get("slide") else 0)
+    for op in case.get("script") or []:
+        if op[0] == "push":
+            nframes = max(nframes, op[1] + 1)
     g = case["graph"]
     chain_frames = chain() if g == "chain" else None
     base = None
@@ -76,8 +122,14 @@ def make_inputs(case, rng, graph_npz=None, chain=None):
                 lists = [[] for _ in range(K)]
             elif g == "small":
                 lists = [[0, 1, 1], [1, 2, 0, 2], []] if K == 3 else [[i] for i in range(K)]
-            elif g == "random":
+            elif g in ("random", "hub"):
                 lists = [list(rng.choice(K, int(rng.integers(0, 13)), replace=False)) for _ in range(K)]
+                if g == "hub":
+                    for i in (0, K - 1):
+                        l = list(rng.integers(0, K, HUB_ENTRIES))
+                        l[1] = l[0]                   # a duplicate
+                        l[-1] = i                     # a self-loop
+                        lists[i] = l
             else:   # long
                 lists = []
                 for i in range(K):
@@ -92,6 +144,8 @@ def make_inputs(case, rng, graph_npz=None, chain=None):
         conf = 0.0
         if umode == "unary":
             udata = rng.uniform(0.0, 4.0, (C, K)).astype(np.float32)
+            if case.get("offsets"):
+                udata = udata + rng.choice(np.array(case["offsets"], np.float32), K)[None, :]
         elif umode == "proba":
             p = rng.uniform(0.01, 1.0, (C, K)).astype(np.float32)
             udata = (p / p.sum(0, keepdims=True)).astype(np.float32)
@@ -110,9 +164,11 @@ def _fill(crf, f, fr):
     crf.set_unary(f, fr["umode"], fr["udata"], fr["conf"])
 
 
-def replay(crf, case, frames, host_only=False):
+def replay(crf, case, frames, host_only=False, only_step=None):
     """Run a case against `crf` (RefCRF of the maker or PkgCRF below); returns what the fixtures record.  host_only: stop before
-    the first inference with max_iter > 0 (what needs no GPU)."""
+    the first inference with max_iter > 0 (what needs no GPU; a case with a "script" stops before the script).  only_step: read q
+    after that inference alone (the other entries of rec["steps"] are None) and stop there, so that q stays where the earlier
+    inferences left it while the window moves; reading it, as recording every step does, brings it to the host."""
     C, K, T = case["C"], case["K"], case["T"]
     if case.get("params"):
         crf.set_params(case["params"])
@@ -139,8 +195,13 @@ def replay(crf, case, frames, host_only=False):
     rec["q0"] = [crf.inferred(f) for f in handles]
     if host_only and case["iters"][0] > 0:
         return rec
+    rec["steps"] = []
+    if case.get("script"):
+        _run_script(crf, case["script"], frames, handles, rec, only_step)
+        return rec
     crf.inference(case["iters"][0])
-    rec["steps"] = [[crf.inferred(f) for f in handles]]
+    if _record(crf, handles, rec, only_step):
+        return rec
     if case.get("slide"):
         crf.pop()
         handles.pop(0)
@@ -149,8 +210,41 @@ def replay(crf, case, frames, host_only=False):
         rec["unaries"].append(crf.unaries(f))
         handles.append(f)
         crf.inference(case["iters"][1])
-        rec["steps"].append([crf.inferred(f) for f in handles])
+        _record(crf, handles, rec, only_step)
     return rec
+
+
+def _record(crf, handles, rec, only_step):
+    """One step of rec["steps"]: q of every live frame, or None for a step that only_step leaves out.  -> only_step is reached."""
+    s = len(rec["steps"])
+    rec["steps"].append([crf.inferred(f) for f in handles] if only_step in (None, s) else None)
+    return only_step == s
+
+
+def _run_script(crf, script, frames, handles, rec, only_step=None):
+    """The operations of a case's "script" on the live frames `handles` (oldest first): ("infer", n), ("push", j) (frame j of the
+    inputs; the pushes name j = T, T + 1, ... in order, so rec["unaries"] stays indexed by input frame), ("pop",), ("reset", i)
+    (reset_inferred of the i-th live frame), ("read", i) (get_inferred of it, discarded).  Every "infer" records one step."""
+    for op in script:
+        if op[0] == "infer":
+            crf.inference(op[1])
+            if _record(crf, handles, rec, only_step):
+                return
+        elif op[0] == "push":
+            assert op[1] == len(rec["unaries"]), "pushes take the input frames in order"
+            f = crf.push()
+            _fill(crf, f, frames[op[1]])
+            rec["unaries"].append(crf.unaries(f))
+            handles.append(f)
+        elif op[0] == "pop":
+            crf.pop()
+            handles.pop(0)
+        elif op[0] == "reset":
+            crf.reset_inferred(handles[op[1]])
+        elif op[0] == "read":
+            crf.inferred(handles[op[1]])
+        else:
+            raise ValueError("unknown script operation %r" % (op,))
 
 
 def pack(case, frames, rec):

@@ -1,5 +1,6 @@
 """Golden vectors for SimpleCRF (src/simple-crf.{h,hpp,cpp}), generated from the UNMODIFIED reference:
-    REF=/path/to/fast-slic python tests/golden/make_golden_crf.py
+    REF=/path/to/fast-slic python tests/golden/make_golden_crf.py [crf_cases.npz] [crf_edge_cases.npz]
+Without a file name it writes crf_edge_cases.npz (crf_cases.EDGE_CASES) and leaves crf_cases.npz (crf_cases.CASES) alone.
 The reference's oracle/ recipe does not build simple-crf.cpp, so this script compiles it with setup.py's flags into a temporary
 directory outside the repository (plus a three-line shim exporting SimpleCRFFrame::calc_temporal_pairwise_energy, which the
 reference's C wrapper does not reach: it passes the frame itself), drives its extern "C" API through ctypes and records inputs and
@@ -7,7 +8,7 @@ outputs.  The replay of a case on this package is tests/crf_cases.py; the fixtur
 
 A case: new(C, K) -> params / compat -> T frames pushed (clusters, neighbour lists as CSR, unaries by set_unary / set_mask /
 set_proba / set_unbiased) -> initialize() or reset_inferred() of some frames -> inference(iters[0]) -> [pop_frame, push_frame of a
-frame whose q stays 0, inference(iters[1])].  The chain case records the reference on the clusters and neighbour lists of
+frame whose q stays 0, inference(iters[1])], or the operations of the case's "script".  The chain case records the reference on the clusters and neighbour lists of
 Slic(K).iterate on four frames (oracle/_ref's Slic, bit-identical to this package's), for tests/test_gpu_crf.py."""
 import ctypes as C
 import json
@@ -152,26 +153,31 @@ def chain_inputs():
     return frames
 
 
-def main():
+# output file -> its cases
+SETS = {"crf_cases.npz": CC.CASES, "crf_edge_cases.npz": CC.EDGE_CASES}
+
+
+def main(files):
     tmp = tempfile.mkdtemp(prefix="fslic_crf_ref_")
     try:
         lib = build_reference(tmp)
         graph = np.load(os.path.join(ROOT, "tests", "golden", "graph_cases.npz"))
-        blob = {}
-        for case in CC.CASES:
-            rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
-            inputs = CC.make_inputs(case, rng, graph, chain_inputs if case.get("graph") == "chain" else None)
-            crf = RefCRF(lib, case["C"], case["K"])
-            rec = CC.replay(crf, case, inputs)
-            crf.close()
-            for k, v in CC.pack(case, inputs, rec).items():
-                blob[case["name"] + "/" + k] = v
-        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "crf_cases.npz")
-        np.savez_compressed(path, **blob)
-        print("wrote", path, os.path.getsize(path), "bytes,", len(blob), "arrays")
+        for fname in files:
+            blob = {}
+            for case in SETS[fname]:
+                rng = np.random.default_rng(zlib.crc32(case["name"].encode()))
+                inputs = CC.make_inputs(case, rng, graph, chain_inputs if case.get("graph") == "chain" else None)
+                crf = RefCRF(lib, case["C"], case["K"])
+                rec = CC.replay(crf, case, inputs)
+                crf.close()
+                for k, v in CC.pack(case, inputs, rec).items():
+                    blob[case["name"] + "/" + k] = v
+            path = os.path.join(os.path.dirname(os.path.abspath(__file__)), fname)
+            np.savez_compressed(path, **blob)
+            print("wrote", path, os.path.getsize(path), "bytes,", len(blob), "arrays")
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:] or ["crf_edge_cases.npz"])

@@ -1,5 +1,6 @@
 """SimpleCRF (fast_slic_amd.crf), the part that needs no GPU: the reference's test/test_crf.py surface, bookkeeping, errors, the host
-setters / energies / reset_inferred bit-equal to the fixtures (tests/golden/crf_cases.npz, make_golden_crf.py), crf_expf against the
+setters / energies / reset_inferred bit-equal to the fixtures (tests/golden/crf_cases.npz and crf_edge_cases.npz, make_golden_crf.py),
+what the edge fixtures claim to contain, crf_expf against the
 host libm's expf, and -- where the reference sources are present -- the live reference on random cases."""
 import gc
 import os
@@ -16,6 +17,7 @@ from fast_slic_amd import _binding as B
 from fast_slic_amd.crf import SimpleCRF, SimpleCRFFrame
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crf_cases.npz"))
+EDGE_GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crf_edge_cases.npz"))
 
 
 # ---- the reference's test/test_crf.py, restated --------------------------------------------------------------------------------------
@@ -247,24 +249,70 @@ def test_frames_on_threads():
 
 
 # ---- fixtures ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", CC.CASE_NAMES)
+@pytest.mark.parametrize("name", CC.CASE_NAMES + CC.EDGE_CASE_NAMES)
 def test_host_side_matches_the_fixtures(name):
-    """Unaries (host logf), spatial / temporal energies and reset_inferred (crf_expf) bit-equal to the reference's; max_iter 0 too."""
-    case, frames = CC.unpack_frames(GOLD, name)
+    """Unaries (host logf), spatial / temporal energies and reset_inferred (crf_expf) bit-equal to the reference's; max_iter 0 too.
+    The edge cases (crf_edge_cases.npz) as well; one with a script up to its first inference."""
+    gold = GOLD if name in CC.CASE_BY_NAME else EDGE_GOLD
+    case, frames = CC.unpack_frames(gold, name)
     crf = CC.PkgCRF(case["C"], case["K"])
     rec = CC.replay(crf, case, frames, host_only=True)
     for j, u in enumerate(rec["unaries"]):
         key = "%s/f%d/unaries" % (name, j)
-        exp = GOLD[key] if key in GOLD.files else frames[j]["udata"]
+        exp = gold[key] if key in gold.files else frames[j]["udata"]
         assert u.tobytes() == exp.tobytes(), "frame %d unaries" % j
-    assert rec["spatial"].tobytes() == GOLD[name + "/spatial"].tobytes()
+    assert rec["spatial"].tobytes() == gold[name + "/spatial"].tobytes()
     if case["T"] > 1:
-        assert rec["temporal"].tobytes() == GOLD[name + "/temporal"].tobytes()
+        assert rec["temporal"].tobytes() == gold[name + "/temporal"].tobytes()
     for j, q in enumerate(rec["q0"]):
-        assert q.tobytes() == GOLD["%s/q0/%d" % (name, j)].tobytes(), "frame %d after initialize / reset_inferred" % j
+        assert q.tobytes() == gold["%s/q0/%d" % (name, j)].tobytes(), "frame %d after initialize / reset_inferred" % j
     if "steps" in rec:                                # max_iter 0: no GPU, nothing changes
         for j, q in enumerate(rec["steps"][0]):
-            assert q.tobytes() == GOLD["%s/step0/%d" % (name, j)].tobytes()
+            assert q.tobytes() == gold["%s/step0/%d" % (name, j)].tobytes()
+
+
+def test_edge_cases_contain_what_they_claim():
+    """The recorded q of the reference, not this package's: the clamp case really has clamped rows (their sum stays below 1), rows
+    the clamp leaves alone, denormal entries and nothing that is not finite; the hub case has its two long rows, with duplicates and
+    self-loops; the window case records one step per "infer" of its script with the window sizes the script goes through."""
+    name = "clamp_c3_k130_t3"
+    case = CC.EDGE_CASE_BY_NAME[name]
+    q = np.stack([EDGE_GOLD["%s/step0/%d" % (name, j)] for j in range(case["T"])])          # [T][C][K]
+    assert np.isfinite(q).all()
+    sums = q.astype(np.float64).sum(axis=1).reshape(-1)
+    assert sums.size == case["T"] * case["K"]
+    assert np.count_nonzero(sums < 0.999) >= 0.2 * sums.size
+    assert np.count_nonzero(np.abs(sums - 1.0) <= 1e-5) >= 0.2 * sums.size
+    assert np.count_nonzero((q != 0) & (np.abs(q) < np.finfo(np.float32).tiny)) >= 1
+    assert np.count_nonzero(q.max(axis=1) == 0) >= 1                                         # rows of zeros
+
+    name = "hub_c5_k200_t2"
+    K = CC.EDGE_CASE_BY_NAME[name]["K"]
+    for j in range(2):
+        off, idx = EDGE_GOLD["%s/f%d/off" % (name, j)], EDGE_GOLD["%s/f%d/idx" % (name, j)]
+        for i in (0, K - 1):
+            row = idx[off[i]:off[i + 1]]
+            assert row.size == CC.HUB_ENTRIES and np.unique(row).size < row.size and (row == i).any()
+        assert np.diff(off)[1:K - 1].max() <= 12
+
+    name = "window_c3_k40"
+    sizes = []
+    s = 0
+    while "%s/step%d/0" % (name, s) in EDGE_GOLD.files:
+        sizes.append(sum(1 for k in EDGE_GOLD.files if k.startswith("%s/step%d/" % (name, s))))
+        s += 1
+    assert sizes == [2, 3, 1, 4, 4, 3]
+    assert sizes == window_sizes(CC.EDGE_CASE_BY_NAME[name])
+
+
+def window_sizes(case):
+    """The number of live frames at each "infer" of a case's script."""
+    T, out = case["T"], []
+    for op in case["script"]:
+        T += {"push": 1, "pop": -1}.get(op[0], 0)
+        if op[0] == "infer":
+            out.append(T)
+    return out
 
 
 # ---- crf_expf ------------------------------------------------------------------------------------------------------------------

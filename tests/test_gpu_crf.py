@@ -34,8 +34,8 @@ def test_inference_matches_the_reference(name):
         check_q(qs, expected(name, s), "%s step %d" % (name, s))
 
 
-def build(name):
-    case, frames = CC.unpack_frames(GOLD, name)
+def build(name, gold=GOLD):
+    case, frames = CC.unpack_frames(gold, name)
     crf = CC.PkgCRF(case["C"], case["K"])
     if case.get("params"):
         crf.set_params(case["params"])
