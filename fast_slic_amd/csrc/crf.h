@@ -1,6 +1,7 @@
 // crf.h -- SimpleCRF (src/simple-crf.{h,hpp,cpp}): mean-field inference of a Potts CRF over the superpixel graph, spatial edges
 // inside a frame and temporal edges between consecutive frames.  Internal to the library; the public boundary is the fslic_hip_crf_*
-// part of include/fslic_hip.h (wrappers in capi.cpp), the kernels and the device side of inference() are in crf.hip.
+// part of include/fslic_hip.h (wrappers in capi.cpp), the device side of inference() is in crf.hip.  Its kernels are the tensor
+// CRF's edge pass and sweep (crf_tensor.h, crf_tensor.hip): one copy of the mean-field arithmetic serves both surfaces.
 //
 // Frame data lives on the host (clusters, neighbour lists, unaries, and q until the first inference): every getter and setter is a
 // host operation and a CRF can be built and filled without a GPU.  inference() uploads what changed since the last call (per-frame
@@ -112,17 +113,21 @@ __host__ __device__ inline float crf_member_factor(uint32_t m_from, uint32_t m_t
     return sqrtf((float)m_from / (float)n);
 }
 
-// ---- device side (crf.hip) -------------------------------------------------------------------------------------------------------
-struct CrfDevParams {
-    int T, C, K;
-    fslic_crf_params p;
-};
-void launch_crf_edges(const CrfDevParams& dp, const fslic_cluster* cl, const uint32_t* rowptr, const uint32_t* idx, float2* edge,
-                      float4* temporal, hipStream_t st);
-void launch_crf_iteration(const CrfDevParams& dp, const uint32_t* rowptr, const uint32_t* idx, const float2* edge, const float4* temporal,
-                          const float* unary, const float* compat, const float* q_in, float* q_out, float* scratch, hipStream_t st);
-void launch_crf_expf(const float* in, float* out, size_t n, hipStream_t st);
-bool crf_messages_in_lds(int C);
+// ---- the clusters as the tensor kernels read them (crf_tensor.h) ------------------------------------------------------------------
+// A window of T frames is 6 * T * K words: the planes yxrgb [T][5][K] float32, then members [T][K] int32 holding the 32 bits of
+// num_members.  This writes frame `w` of it from the frame's K clusters; host only, no device involved.
+inline void crf_stage_clusters(const fslic_cluster* cl, size_t w, size_t T, size_t K, float* window) {
+    float* planes = window + w * 5 * K;
+    float* members = window + T * 5 * K + w * K;
+    for (size_t i = 0; i < K; i++) {
+        planes[i] = cl[i].y;
+        planes[K + i] = cl[i].x;
+        planes[2 * K + i] = cl[i].r;
+        planes[3 * K + i] = cl[i].g;
+        planes[4 * K + i] = cl[i].b;
+        memcpy(members + i, &cl[i].num_members, 4);
+    }
+}
 
 }  // namespace fslic
 
@@ -153,17 +158,15 @@ struct fslic_crf {                          // SimpleCRF (src/simple-crf.hpp:70-
     // device state: the window of the last inference, bound to one engine
     fslic_engine* eng = nullptr;
     int capT = 0;                           // frames the buffers are sized for
-    size_t cap_edges = 0;
+    long long nnz = 0;                      // neighbour entries of the window as uploaded
     fslic::Device<float> d_q[2];                // [capT][C][K] each, d_q[cur] holds the current q
     int cur = 0;
     fslic::Device<float> d_unary;
     fslic::Device<float> d_compat;
-    fslic::Device<float> d_scratch;             // messages when they do not fit in LDS (crf_messages_in_lds)
-    fslic::Device<fslic_cluster> d_cl;
-    fslic::Device<uint32_t> d_rowptr;           // [capT * K + 1]
-    fslic::Device<uint32_t> d_idx;              // [cap_edges]
-    fslic::Device<float2> d_edge;               // per edge (energy, factor)
-    fslic::Device<float4> d_temporal;           // per node (energy, factor) towards t-1 and t+1
+    fslic::Device<float> d_cl;                  // [6 * capT * K]: the uploaded frames' yxrgb planes, then their member counts (crf_stage_clusters)
+    fslic::Device<int64_t> d_offsets;           // [capT * K + 1]: the neighbour lists of the window as one CSR over (frame, node)
+    fslic::Device<int32_t> d_idx;               // [nnz]
+    fslic::Device<char> d_work;                 // rows, temporal, edge and msg: crf_tensor_workspace(T, C, K, nnz, kCrfCallSaved, false)
     bool graph_uploaded = false;
 };
 

@@ -1,128 +1,32 @@
-// crf.hip -- SimpleCRF inference (src/simple-crf.cpp:62-153) on gfx950, and the device side of its host state (crf.h).
-//   k_crf_edges      once per inference(), every frame: per neighbour entry the spatial energy and the member factor, per node the
-//                    temporal energies and factors towards t-1 and t+1.  None of them depends on the class or the iteration.
-//   k_crf_iteration  one Jacobi sweep of SimpleCRF::infer_once over every frame: reads q of the previous sweep, writes the other buffer
-//                    (the reference's new_probas).  One thread per (frame, node) does all its classes: messages (kept in LDS), the
-//                    compatibility transform, the exponential, the clamp at 1e-5 and the normalisation, each sum in the reference's order.
+// crf.hip -- the device side of SimpleCRF's host state (crf.h): inference() (src/simple-crf.cpp:62-153) on gfx950.
+// The kernels are the tensor CRF's (crf_tensor.h, crf_tensor.hip), so the mean-field arithmetic exists once:
+//   launch_crf_tensor_edges  once per inference(), every frame, temporal links on: row bounds, per neighbour entry the spatial energy and
+//                            the member factor, per node the temporal energies and factors towards t-1 and t+1.
+//   launch_crf_tensor_sweep  one Jacobi sweep of SimpleCRF::infer_once over every frame: reads q of the previous sweep, writes the other
+//                            buffer (the reference's new_probas).  A block is 64 nodes of one frame times up to 16 wavefronts, one per
+//                            class slice; messages stay in LDS up to kCrfTensorLdsClasses (128) classes and go to a [T][C][K] plane of
+//                            the CRF's workspace above that.
+// What this file adds is the window: the frames go up in the form those kernels read (clusters as yxrgb planes and member counts, the
+// neighbour lists as one int64 / int32 CSR over (frame, node)), q stays on the device between calls.
 // max_iter sweeps go back to back on one slot's stream; one synchronisation at the end.
 #include "crf.h"
+#include "crf_tensor.h"
 
 #include <algorithm>
 
-// Every rounding of this file is the reference build's: a product is fused into a sum exactly where that build fuses it (__builtin_fmaf,
-// see crf.h) and nowhere else (see realdist.hip for what hipcc's default would do), division and sqrtf are the correctly rounded ones
-// (HIP's default), the exponential is crf_expf.
+// Every rounding of the CRF's device code (this file, crf_tensor.hip, crf_tensor_sweep.h) is the reference build's: a product is fused
+// into a sum exactly where that build fuses it (__builtin_fmaf, see crf.h) and nowhere else (see realdist.hip for what hipcc's default
+// would do), division and sqrtf are the correctly rounded ones (HIP's default), the exponential is crf_expf.
 #pragma clang fp contract(off)
 
 namespace fslic {
-
-constexpr int kCrfBlock = 64;                          // nodes per block: one wavefront
-constexpr int kCrfLdsClasses = 256;                    // messages of up to this many classes stay in LDS (64 KB per block)
-
-__global__ __launch_bounds__(256) void k_crf_edges(CrfDevParams dp, const fslic_cluster* __restrict__ cl, const uint32_t* __restrict__ rowptr,
-                                                   const uint32_t* __restrict__ idx, float2* __restrict__ edge, float4* __restrict__ temporal) {
-    const int n = dp.T * dp.K;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    const int w = g / dp.K, i = g - w * dp.K;
-    const fslic_cluster ci = cl[g];
-    const fslic_cluster* frame = cl + (size_t)w * dp.K;
-    for (uint32_t k = rowptr[g], k1 = rowptr[g + 1]; k < k1; ++k) {
-        const uint32_t j = idx[k];
-        const fslic_cluster cj = frame[j];
-        // calc_spatial_pairwise_energy(neighbor, i) (simple-crf.cpp:86): 0 for a self-loop
-        const float e = (int)j == i ? 0.0f : crf_spatial_energy(dp.p, cj, ci);
-        edge[k] = make_float2(e, crf_member_factor(cj.num_members, ci.num_members));
-    }
-    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (w > 0) {                                       // simple-crf.cpp:90-93
-        const fslic_cluster cp = cl[g - dp.K];
-        t.x = crf_temporal_energy(dp.p, ci, cp);
-        t.y = crf_member_factor(cp.num_members, ci.num_members);
-    }
-    if (w < dp.T - 1) {                                // :95-99
-        const fslic_cluster cn = cl[g + dp.K];
-        t.z = crf_temporal_energy(dp.p, ci, cn);
-        t.w = crf_member_factor(cn.num_members, ci.num_members);
-    }
-    temporal[g] = t;
-}
-
-// Messages of the thread's node: m[cls * mstride] (LDS, or the global scratch for more than kCrfLdsClasses classes).
-template <bool LDS>
-__global__ __launch_bounds__(kCrfBlock) void k_crf_iteration(CrfDevParams dp, const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ idx,
-                                                             const float2* __restrict__ edge, const float4* __restrict__ temporal,
-                                                             const float* __restrict__ unary, const float* __restrict__ compat,
-                                                             const float* __restrict__ q_in, float* __restrict__ q_out, float* __restrict__ scratch) {
-    extern __shared__ float s_msg[];
-    const int n = dp.T * dp.K;
-    const int g = blockIdx.x * kCrfBlock + threadIdx.x;
-    if (g >= n) return;
-    const int C = dp.C, K = dp.K;
-    const int w = g / K, i = g - w * K;
-    const size_t CK = (size_t)C * K;
-    const size_t base = (size_t)w * CK;
-    float* m = LDS ? s_msg + threadIdx.x : scratch + g;
-    const size_t mstride = LDS ? (size_t)kCrfBlock : (size_t)n;
-    const uint32_t k0 = rowptr[g], k1 = rowptr[g + 1];
-    const float4 t = temporal[g];
-    const bool has_prev = w > 0, has_next = w < dp.T - 1;
-    // message passing (simple-crf.cpp:71-102): neighbours in list order, then t-1, then t+1; each term fma(e * q, factor, message)
-    for (int cls = 0; cls < C; ++cls) {
-        const float* qc = q_in + base + (size_t)cls * K;
-        float message = 0.0f;
-        for (uint32_t k = k0; k < k1; ++k) {
-            const float2 es = edge[k];
-            message = __builtin_fmaf(es.x * qc[idx[k]], es.y, message);
-        }
-        if (has_prev) message = __builtin_fmaf(t.x * qc[i - (ptrdiff_t)CK], t.y, message);
-        if (has_next) message = __builtin_fmaf(t.z * qc[i + CK], t.w, message);
-        m[cls * mstride] = message;
-    }
-    // compatibility transform (:104-114): the Potts sum over the other classes in ascending order (fused), then expf
-    float* out = q_out + base + i;
-    const float* un = unary + base + i;
-    float sum = 0.0f;
-    for (int cls = 0; cls < C; ++cls) {
-        float gathered = 0.0f;
-        for (int o = 0; o < C; ++o) {
-            if (o == cls) continue;
-            gathered = __builtin_fmaf(compat[o], m[o * mstride], gathered);
-        }
-        const float ex = crf_expf(-(un[(size_t)cls * K] + gathered));
-        out[(size_t)cls * K] = ex;
-    }
-    // normalisation (:116-133): the sum over classes in ascending order, clamped at 1e-5 (a double comparison, as written there)
-    for (int cls = 0; cls < C; ++cls) sum += out[(size_t)cls * K];
-    if ((double)sum < 1e-5) sum = (float)1e-5;
-    for (int cls = 0; cls < C; ++cls) out[(size_t)cls * K] = out[(size_t)cls * K] / sum;
-}
 
 __global__ __launch_bounds__(256) void k_crf_expf(const float* __restrict__ in, float* __restrict__ out, size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += stride) out[p] = crf_expf(in[p]);
 }
 
-bool crf_messages_in_lds(int C) { return C <= kCrfLdsClasses; }
-
-void launch_crf_edges(const CrfDevParams& dp, const fslic_cluster* cl, const uint32_t* rowptr, const uint32_t* idx, float2* edge,
-                      float4* temporal, hipStream_t st) {
-    const int n = dp.T * dp.K;
-    launch(k_crf_edges, dim3((n + 255) / 256), dim3(256), 0, st, dp, cl, rowptr, idx, edge, temporal);
-}
-
-void launch_crf_iteration(const CrfDevParams& dp, const uint32_t* rowptr, const uint32_t* idx, const float2* edge, const float4* temporal,
-                          const float* unary, const float* compat, const float* q_in, float* q_out, float* scratch, hipStream_t st) {
-    const int n = dp.T * dp.K;
-    const dim3 grid((n + kCrfBlock - 1) / kCrfBlock);
-    if (crf_messages_in_lds(dp.C))
-        launch(k_crf_iteration<true>, grid, dim3(kCrfBlock), (unsigned)(sizeof(float) * kCrfBlock * dp.C), st,
-               dp, rowptr, idx, edge, temporal, unary, compat, q_in, q_out, scratch);
-    else
-        launch(k_crf_iteration<false>, grid, dim3(kCrfBlock), 0, st, dp, rowptr, idx, edge, temporal, unary, compat, q_in, q_out, scratch);
-}
-
-void launch_crf_expf(const float* in, float* out, size_t n, hipStream_t st) {
+static void launch_crf_expf(const float* in, float* out, size_t n, hipStream_t st) {
     const size_t blocks = std::min<size_t>((n + 255) / 256, 8192);
     launch(k_crf_expf, dim3((unsigned)std::max<size_t>(blocks, 1)), dim3(256), 0, st, in, out, n);
 }
@@ -130,10 +34,10 @@ void launch_crf_expf(const float* in, float* out, size_t n, hipStream_t st) {
 // ---- host side of inference() ------------------------------------------------------------------------------------------------------
 void crf_release_device(fslic_crf* crf) {
     if (crf->eng) (void)hipSetDevice(crf->eng->device);
-    crf->d_q[0].release(); crf->d_q[1].release(); crf->d_unary.release(); crf->d_compat.release(); crf->d_scratch.release();
-    crf->d_cl.release(); crf->d_rowptr.release(); crf->d_idx.release(); crf->d_edge.release(); crf->d_temporal.release();
+    crf->d_q[0].release(); crf->d_q[1].release(); crf->d_unary.release(); crf->d_compat.release();
+    crf->d_cl.release(); crf->d_offsets.release(); crf->d_idx.release(); crf->d_work.release();
     crf->capT = 0;
-    crf->cap_edges = 0;
+    crf->nnz = 0;
     crf->cur = 0;
     crf->graph_uploaded = false;
     crf->eng = nullptr;
@@ -159,10 +63,16 @@ int crf_pull_q(fslic_crf* crf, fslic_crf_frame* f) {
     return FSLIC_OK;
 }
 
-static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, size_t max_iter, std::vector<uint32_t>& rowptr,
-                            std::vector<uint32_t>& idx) {
+// Host staging of the window's upload: alive until the stream is synchronised.
+struct CrfStaging {
+    std::vector<int64_t> offsets;
+    std::vector<uint32_t> idx;
+    std::unique_ptr<float[]> cl;            // crf_stage_clusters writes every word: no fill first
+};
+
+static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, size_t max_iter, CrfStaging& s) {
     const int T = (int)crf->frames.size();
-    const size_t C = crf->C, K = crf->K, CK = C * K;
+    const size_t C = crf->C, K = crf->K, CK = C * K, n = (size_t)T * K;
     // 1. frames that move to another window position (a pop shifts them, more frames reallocate) take their q along through the host
     const bool realloc = T > crf->capT;
     bool moved = realloc || !crf->graph_uploaded;
@@ -181,53 +91,51 @@ static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, siz
         f->dev_pos = w;
         f->dirty_graph = f->dirty_unary = f->dirty_q = true;
     }
-    // 2. buffers
+    // 2. the buffers whose size follows the number of frames (reserve frees and allocates anew when it has to grow)
     if (realloc) {
-        crf->d_q[0].release(); crf->d_q[1].release(); crf->d_unary.release(); crf->d_scratch.release(); crf->d_cl.release();
-        crf->d_rowptr.release(); crf->d_temporal.release();
-        const size_t n = (size_t)T * K;
         int rc;
         if ((rc = crf->d_q[0].reserve((size_t)T * CK)) || (rc = crf->d_q[1].reserve((size_t)T * CK)) ||
-            (rc = crf->d_unary.reserve((size_t)T * CK)) || (rc = crf->d_cl.reserve(n)) || (rc = crf->d_rowptr.reserve(n + 1)) ||
-            (rc = crf->d_temporal.reserve(n)))
+            (rc = crf->d_unary.reserve((size_t)T * CK)) || (rc = crf->d_cl.reserve(6 * n)) || (rc = crf->d_offsets.reserve(n + 1)) ||
+            (rc = crf->d_compat.reserve(C)))
             return rc;
-        if (!crf_messages_in_lds((int)C) && (rc = crf->d_scratch.reserve((size_t)T * CK))) return rc;
-        if (!crf->d_compat && (rc = crf->d_compat.reserve(C))) return rc;
         crf->capT = T;
         crf->cur = 0;
     }
-    // 3. uploads: the neighbour lists of the window as one CSR over (frame, node), whenever a frame's graph or position changed
+    // 3. uploads.  Whenever a frame's graph or position changed, the whole window anew: its neighbour lists as one CSR over
+    //    (frame, node), its clusters as planes and member counts, each with one copy
     bool graph = moved;
     for (auto& f : crf->frames) graph = graph || f->dirty_graph;
+    float* yxrgb = crf->d_cl;
+    const int32_t* members = reinterpret_cast<const int32_t*>(yxrgb + 5 * n);
     if (graph) {
-        rowptr.assign((size_t)T * K + 1, 0u);
+        s.offsets.assign(n + 1, 0);
         size_t total = 0;
         for (int w = 0; w < T; w++)
             for (size_t i = 0; i < K; i++) {
                 total += crf->frames[w]->edges[i].size();
                 if (total >= (1ull << 31)) return fail(FSLIC_E_INVALID, "the frames hold 2^31 or more neighbour entries");
-                rowptr[(size_t)w * K + i + 1] = (uint32_t)total;
+                s.offsets[(size_t)w * K + i + 1] = (int64_t)total;
             }
-        idx.resize(total);
-        for (int w = 0; w < T; w++)
+        s.idx.resize(total);
+        s.cl.reset(new float[6 * n]);
+        for (int w = 0; w < T; w++) {
             for (size_t i = 0; i < K; i++) {
                 const auto& l = crf->frames[w]->edges[i];
-                std::copy(l.begin(), l.end(), idx.begin() + rowptr[(size_t)w * K + i]);
+                std::copy(l.begin(), l.end(), s.idx.begin() + s.offsets[(size_t)w * K + i]);
             }
-        if (total > crf->cap_edges || !crf->d_idx) {
-            crf->d_idx.release(); crf->d_edge.release();
-            int rc;
-            if ((rc = crf->d_idx.reserve(total)) || (rc = crf->d_edge.reserve(total))) return rc;
-            crf->cap_edges = total;
+            crf_stage_clusters(crf->frames[w]->clusters.data(), (size_t)w, (size_t)T, K, s.cl.get());
         }
-        HIPCHK(hipMemcpyAsync(crf->d_rowptr, rowptr.data(), rowptr.size() * 4, hipMemcpyHostToDevice, st));
-        if (total) HIPCHK(hipMemcpyAsync(crf->d_idx, idx.data(), total * 4, hipMemcpyHostToDevice, st));
+        int rc;
+        if ((rc = crf->d_idx.reserve(total))) return rc;
+        crf->nnz = (long long)total;
+        HIPCHK(hipMemcpyAsync(crf->d_offsets, s.offsets.data(), s.offsets.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        // the setters refuse an index >= num_nodes, so the same bytes read as int32 hold no dead entry
+        if (total) HIPCHK(hipMemcpyAsync(crf->d_idx, s.idx.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(yxrgb, s.cl.get(), 6 * n * sizeof(float), hipMemcpyHostToDevice, st));
         crf->graph_uploaded = true;
     }
     for (int w = 0; w < T; w++) {
         fslic_crf_frame* f = crf->frames[w].get();
-        if (f->dirty_graph || graph)
-            HIPCHK(hipMemcpyAsync(crf->d_cl + (size_t)w * K, f->clusters.data(), K * sizeof(fslic_cluster), hipMemcpyHostToDevice, st));
         if (f->dirty_unary)
             HIPCHK(hipMemcpyAsync(crf->d_unary + (size_t)w * CK, f->unaries.data(), CK * sizeof(float), hipMemcpyHostToDevice, st));
         if (f->dirty_q)
@@ -235,13 +143,17 @@ static int crf_inference_on(fslic_crf* crf, fslic_engine* e, hipStream_t st, siz
         f->dirty_graph = f->dirty_unary = f->dirty_q = false;
     }
     HIPCHK(hipMemcpyAsync(crf->d_compat, crf->compat.data(), C * sizeof(float), hipMemcpyHostToDevice, st));
-    // 4. the edge kernel, then max_iter sweeps ping-ponging between the two q buffers
-    CrfDevParams dp;
-    dp.T = T; dp.C = (int)C; dp.K = (int)K; dp.p = crf->params;
-    launch_crf_edges(dp, crf->d_cl, crf->d_rowptr, crf->d_idx, crf->d_edge, crf->d_temporal, st);
+    // 4. the edge pass into the workspace (rows, temporal, edge; msg above kCrfTensorLdsClasses classes), then max_iter sweeps
+    //    ping-ponging between the two q buffers
+    const CrfTensorWorkspace ws = crf_tensor_workspace(T, (int)C, (int)K, crf->nnz, kCrfCallSaved, false);
+    int rc = crf->d_work.reserve(ws.bytes);
+    if (rc) return rc;
+    const CrfTensorBuffers b = crf_tensor_buffers(crf->d_work.get(), ws);
+    CrfTensorParams dp;
+    dp.N = T; dp.C = (int)C; dp.K = (int)K; dp.temporal = 1; dp.nnz = crf->nnz; dp.p = crf->params;
+    launch_crf_tensor_edges(dp, yxrgb, members, crf->d_offsets, crf->d_idx, b.rows, b.edge, b.temporal, st);
     for (size_t it = 0; it < max_iter; it++) {
-        launch_crf_iteration(dp, crf->d_rowptr, crf->d_idx, crf->d_edge, crf->d_temporal, crf->d_unary, crf->d_compat,
-                             crf->d_q[crf->cur], crf->d_q[crf->cur ^ 1], crf->d_scratch, st);
+        launch_crf_tensor_sweep(dp, b.lists(), crf->d_idx, crf->d_unary, crf->d_compat, crf->d_q[crf->cur], crf->d_q[crf->cur ^ 1], b.msg, st);
         crf->cur ^= 1;
     }
     HIPCHK(hipGetLastError());
@@ -270,8 +182,8 @@ int crf_inference(fslic_crf* crf, fslic_engine* e, size_t max_iter) {
     if (rc) return rc;
     crf->eng = e;
     hipStream_t st = e->slots[lease.slot].st;
-    std::vector<uint32_t> rowptr, idx;                           // staging of the CSR upload: alive until the stream is synchronised
-    rc = crf_inference_on(crf, e, st, max_iter, rowptr, idx);
+    CrfStaging staging;
+    rc = crf_inference_on(crf, e, st, max_iter, staging);
     if (rc) {                                                    // nothing may still run against the staging; the device state is rebuilt
         const std::string msg = last_error();
         (void)hipStreamSynchronize(st);

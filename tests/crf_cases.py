@@ -30,9 +30,12 @@ CASES = [
 CASE_NAMES = [c["name"] for c in CASES]
 CASE_BY_NAME = {c["name"]: c for c in CASES}
 
-# The edges of crf.hip (tests/golden/crf_edge_cases.npz): more classes than the LDS form holds (256) and exactly that many, one class,
-# window sizes on the block edges of the sweep (64 nodes) and of the edge kernel (256), the clamp of the class sum, neighbour rows of
-# thousands of entries, and a window that grows, shrinks and slides between inferences.
+# The edges of the sweep behind SimpleCRF.inference and superpixel_crf (tests/golden/crf_edge_cases.npz).  Its own: 127, 128 and 129
+# classes around the cut at which the messages leave LDS (128: the largest LDS form, 16 wavefronts of 8 classes), 17 classes (two
+# classes per wavefront, the last wavefront with one) on a last tile of 6 live lanes, one class, window sizes on the block edges of
+# the sweep (64 nodes) and of the edge pass (256), the clamp of the class sum, neighbour rows of thousands of entries, and a window
+# that grows, shrinks and slides between inferences.  And those of the kernels SimpleCRF ran before it, which cut at 256 classes:
+# 255, 256, 257 and 300 classes.
 # With the default params and make_inputs' random centres and colours every pairwise energy underflows against the unaries, so q
 # would not depend on the q before it.  WIDE makes the messages count: a stale q or another summation order changes the result.
 WIDE = [1.5, 2.0, 150.0, 120.0, 600.0, 0.5, 400.0]
@@ -52,6 +55,19 @@ def _block_edge(name, K, T):
     return dict(name=name, C=2, K=K, T=T, iters=[2], graph="random", umode=["unary"], init="initialize", params=WIDE)
 
 
+# "ugrid": the unaries (uniform in [0, 4)) are rounded down to multiples of 1 / ugrid.  They and q0 = expf(-unaries) then take 256
+# values and compress to a third, which keeps the fixture file below 1 MiB.  A cell still differs from another one with probability
+# 255 / 256, so a sweep that mixes up classes, lanes or frames shows; the energies keep full mantissas, so every message, every Potts
+# sum and every q after the first sweep is rounded as with any other unaries.
+UNARY_GRID = 64
+
+
+def _class_edge(C, K, T):
+    """The smallest shape at which one form of the sweep can go wrong; the compat values differ, so the order of the Potts sum shows."""
+    return dict(name="c%d_k%d_t%d" % (C, K, T), C=C, K=K, T=T, iters=[2], graph="random", umode=["unary"], init="initialize",
+                params=WIDE, compat=[0.25 + 0.125 * (c % 11) for c in range(C)], ugrid=UNARY_GRID)
+
+
 EDGE_CASES = [
     dict(name="c257_k65_t2_long", C=257, K=65, T=2, iters=[3], graph="long", umode=["unary", "mask"], init="initialize",
          params=[0.375, 1.25, 150.0, 120.0, 600.0, 0.125, 400.0], compat=[0.25 + 0.125 * (c % 11) for c in range(257)]),
@@ -69,6 +85,10 @@ EDGE_CASES = [
          params=[0.004, 0.05, 150.0, 120.0, 600.0, 0.002, 400.0]),
     dict(name="window_c3_k40", C=3, K=40, T=2, iters=[2], graph="random", umode=["unary", "mask", "proba"], init="initialize",
          params=WIDE, script=WINDOW_SCRIPT),
+    _class_edge(127, 33, 1),                  # just below the cut
+    _class_edge(128, 33, 2),                  # the largest LDS form (64 KB), with temporal links
+    _class_edge(129, 33, 2),                  # the first plane form: messages in the workspace, exponentials in q_out
+    _class_edge(17, 70, 3),                   # two classes per wavefront, the last wavefront with one; a tile of 6 live lanes
 ]
 EDGE_CASE_NAMES = [c["name"] for c in EDGE_CASES]
 EDGE_CASE_BY_NAME = {c["name"]: c for c in EDGE_CASES}
@@ -144,6 +164,8 @@ def make_inputs(case, rng, graph_npz=None, chain=None):
         conf = 0.0
         if umode == "unary":
             udata = rng.uniform(0.0, 4.0, (C, K)).astype(np.float32)
+            if case.get("ugrid"):
+                udata = np.floor(udata * np.float32(case["ugrid"])) / np.float32(case["ugrid"])
             if case.get("offsets"):
                 udata = udata + rng.choice(np.array(case["offsets"], np.float32), K)[None, :]
         elif umode == "proba":

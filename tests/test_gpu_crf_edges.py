@@ -1,9 +1,10 @@
-"""SimpleCRF inference on the MI355X at the edges of crf.hip, bit-equal to the reference's (tests/golden/crf_edge_cases.npz,
-crf_cases.EDGE_CASES, make_golden_crf.py): the sweep with its messages in global scratch (more than 256 classes) and with the
-largest LDS form (256 classes, 64 KB of dynamic LDS), one class, windows on the block edges of both kernels, the clamp of the class
-sum, neighbour rows of thousands of entries, a window that grows, shrinks and slides while q lives on the device, setters on the
-scratch path, a CRF that changes its engine, and two scratch-path CRFs on two threads.  No tolerance anywhere: crf.h promises the
-reference's bits."""
+"""SimpleCRF inference on the MI355X at the edges of its kernels, the tensor CRF's edge pass and sweep (crf.hip, crf_tensor.hip),
+bit-equal to the reference's (tests/golden/crf_edge_cases.npz, crf_cases.EDGE_CASES, make_golden_crf.py): the sweep with its
+messages in a plane of the CRF's workspace (more than 128 classes: 129, and the 255 to 300 classes around the cut of the kernels
+SimpleCRF ran before) and with the largest LDS form (128 classes, 64 KB of dynamic LDS), 127 and 17 classes, one class, windows on
+the block edges of both kernels, the clamp of the class sum, neighbour rows of thousands of entries, a window that grows, shrinks
+and slides while q lives on the device, setters on the plane path, a CRF that changes its engine, and two plane-path CRFs on two
+threads.  No tolerance anywhere: crf.h promises the reference's bits."""
 import os
 import threading
 
@@ -49,9 +50,10 @@ def test_edge_cases_match_the_reference(name):
 
 
 def test_scratch_and_lds_forms_agree_with_a_fresh_twin():
-    """test_setters_between_calls on the scratch path: after two iterations one frame gets new unaries and one neighbour list grows
-    (the edge buffers are allocated anew, the window's buffers and the message scratch stay), then two more iterations equal those
-    of a deep copy taken before them, which uploads everything into buffers of its own."""
+    """test_setters_between_calls with the messages in the workspace's plane (257 classes): after two iterations one frame gets new
+    unaries and one neighbour list grows (the index buffer and the workspace, which holds the per-entry energies and that plane, are
+    allocated anew; the window's buffers stay), then two more iterations equal those of a deep copy taken before them, which uploads
+    everything into buffers of its own."""
     rng = np.random.default_rng(11)
     case, crf, handles = build("c257_k65_t2_long", EDGE_GOLD)
     crf.inference(2)
@@ -65,7 +67,7 @@ def test_scratch_and_lds_forms_agree_with_a_fresh_twin():
     twin.inference(2)
     got = [f.get_inferred() for f in handles]
     exp = [twin.get_frame(f.time).get_inferred() for f in handles]
-    check_q(got, exp, "after setters, messages in scratch")
+    check_q(got, exp, "after setters, messages in the workspace")
     assert not any(np.array_equal(g, b) for g, b in zip(got, before))
 
 
@@ -88,7 +90,8 @@ def test_rebinding_to_a_second_engine_carries_q():
 
 
 def test_two_scratch_path_crfs_on_two_threads():
-    """The message scratch belongs to the CRF, not to the engine's slot: two CRFs with more than 256 classes infer side by side."""
+    """The workspace with the message plane belongs to the CRF, not to the engine's slot: two CRFs with more than 128 classes infer
+    side by side."""
     names = ["c257_k65_t2_long", "c300_k33_t3_slide"]
     out, errors = {}, []
 

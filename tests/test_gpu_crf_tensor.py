@@ -1,6 +1,7 @@
 """SimpleCRF inference on torch tensors on the MI355X (fast_slic_amd/crf_torch.py, csrc/crf_tensor.hip), bit for bit: against the
-reference's recorded results (tests/golden/crf_cases.npz), against the package's SimpleCRF (itself pinned to the reference) at the
-seams of the sweep's layout (64 nodes a block, one wavefront per class slice, the LDS cut at 128 classes), with neighbour entries out
+reference's recorded results (tests/golden/crf_cases.npz, and the edges of the sweep in crf_edge_cases.npz), against the package's
+SimpleCRF (pinned to the same fixtures; it runs the same edge pass and sweep, so these compare the two uploads) at the seams of the
+sweep's layout (64 nodes a block, one wavefront per class slice, the LDS cut at 128 classes), with neighbour entries out
 of range, batch independence, streams, no host synchronisation, SuperpixelGraph.to_batch_csr, and the all-GPU chain
 Slic -> pool -> graph -> CRF -> unpool.  Every comparison is np.array_equal on the float bits; there are no tolerances."""
 import os
@@ -18,7 +19,11 @@ from fast_slic_amd.rag import superpixel_graph
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crf_cases.npz"))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLD = np.load(os.path.join(GOLDEN, "crf_cases.npz"))
+EDGE_GOLD = np.load(os.path.join(GOLDEN, "crf_edge_cases.npz"))
+# the edge cases that are one window and one inference: what a single superpixel_crf call can replay
+EDGE_NAMES = [c["name"] for c in CC.EDGE_CASES if not c.get("script") and not c.get("slide")]
 LDS_CUT = 128                     # kCrfTensorLdsClasses (csrc/crf_tensor.h)
 
 
@@ -52,19 +57,20 @@ def on_gpu(a):
 
 # ---- the reference's fixtures ----
 def fixture(name):
-    case, frames = CC.unpack_frames(GOLD, name)
+    gold = GOLD if name in CC.CASE_BY_NAME else EDGE_GOLD
+    case, frames = CC.unpack_frames(gold, name)
     T = case["T"]
     frames = frames[:T]
-    unaries = [GOLD["%s/f%d/unaries" % (name, j)] if frames[j]["umode"] != "unary" else frames[j]["udata"] for j in range(T)]
+    unaries = [gold["%s/f%d/unaries" % (name, j)] if frames[j]["umode"] != "unary" else frames[j]["udata"] for j in range(T)]
     rows = [[list(map(int, f["idx"][f["off"][i]:f["off"][i + 1]])) for i in range(case["K"])] for f in frames]
     yx, mem = cluster_tensors([f["clusters"] for f in frames])
     params = dict(zip(CC.PARAM_NAMES, case["params"])) if case.get("params") else None
-    q0 = np.stack([GOLD["%s/q0/%d" % (name, j)] for j in range(T)])
-    step = np.stack([GOLD["%s/step0/%d" % (name, j)] for j in range(T)])
+    q0 = np.stack([gold["%s/q0/%d" % (name, j)] for j in range(T)])
+    step = np.stack([gold["%s/step0/%d" % (name, j)] for j in range(T)])
     return case, on_gpu(np.stack(unaries).astype(np.float32)), csr_tensors(rows), yx, mem, params, case.get("compat"), q0, step
 
 
-@pytest.mark.parametrize("name", CC.CASE_NAMES)
+@pytest.mark.parametrize("name", CC.CASE_NAMES + EDGE_NAMES)
 def test_matches_the_reference_fixture(name):
     case, un, graph, yx, mem, params, compat, q0, step = fixture(name)
     q = superpixel_crf(un, graph, yx, mem, max_iter=case["iters"][0], params=params, compat=compat, temporal=True, q0=on_gpu(q0))
