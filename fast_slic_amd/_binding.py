@@ -45,7 +45,7 @@ EXPORTS = [
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
     "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
-    "fslic_hip_debug_lsc_state",
+    "fslic_hip_debug_lsc_state", "fslic_hip_debug_forms_seen", "fslic_hip_debug_forms_all",
     # SimpleCRF (fast_slic_amd/crf.py)
     "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
     "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
@@ -71,6 +71,47 @@ EXPORTS = [
 
 _lib = None
 _lib_lock = threading.Lock()
+
+# ---- the record of kernel forms (include/fslic_hip.h: fslic_hip_debug_forms_seen / _all; csrc/forms.h) ----
+FORM_FAMILIES = {1: "blk", 2: "bin", 3: "pre", 4: "k32", 5: "generic", 6: "generic_rec", 7: "preempt_update"}
+FORM_TABLES = {0: "notab", 1: "rowvec", 2: "rowvec16", 3: "2d", 4: "tabs16", 5: "lut"}
+
+
+def form_name(code):
+    """A form code as words, e.g. 'blk r16 fused s2 rowvec nolab', 'k32 r8 full srt lut lab', 'preempt_update lists'."""
+    code = int(code)
+    family = FORM_FAMILIES.get(code & 15, "family%d" % (code & 15))
+    if family == "preempt_update":
+        return family + (" allpairs" if (code >> 18) & 1 else " lists")
+    stride = (code >> 11) & 7
+    words = [family]
+    if (code >> 4) & 63:
+        words.append("r%d" % ((code >> 4) & 63))
+    words += ["fused" if (code >> 10) & 1 else "full", "s%d" % stride if stride else "srt",
+              FORM_TABLES.get((code >> 14) & 7, "table%d" % ((code >> 14) & 7)), "nolab" if (code >> 17) & 1 else "lab"]
+    return " ".join(words)
+
+
+def _form_codes(fn, *extra):
+    buf = (C.c_uint32 * 256)()
+    n = int(fn(buf, 256, *extra))
+    if n < 0 or n > 256:
+        raise RuntimeError("the form record cannot be read (%d)" % n)
+    return [int(buf[i]) for i in range(n)]
+
+
+def forms_seen(clear=False):
+    """Names of the kernel forms this process has enqueued since the record was last cleared (a set)."""
+    return {form_name(c) for c in _form_codes(load_library().fslic_hip_debug_forms_seen, 1 if clear else 0)}
+
+
+def forms_all():
+    """Names of every form the dispatch can produce, in the order of the library's static tables (a list)."""
+    return [form_name(c) for c in _form_codes(load_library().fslic_hip_debug_forms_all)]
+
+
+def form_codes_all():
+    return _form_codes(load_library().fslic_hip_debug_forms_all)
 
 
 def build_library(force=False):
@@ -145,6 +186,9 @@ def load_library():
         lib.fslic_hip_last_prelabels.argtypes = [vp, i32, vp]
         if hasattr(lib, "fslic_hip_debug_lsc_state"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
             lib.fslic_hip_debug_lsc_state.argtypes = [vp, i32, i32, i32, vp, vp]
+        if hasattr(lib, "fslic_hip_debug_forms_seen"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks the form record)
+            lib.fslic_hip_debug_forms_seen.argtypes = [vp, i32, i32]
+            lib.fslic_hip_debug_forms_all.argtypes = [vp, i32]
         lib.fslic_hip_last_timing_report.argtypes = [vp]
         lib.fslic_hip_last_timing_report.restype = C.c_char_p
         if hasattr(lib, "fslic_hip_last_recorder_report"):

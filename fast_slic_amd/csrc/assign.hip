@@ -2,6 +2,7 @@
 // Hand-written gfx950 (CDNA4, wave64) kernels of the SLIC hot path; see kernels.h for the launch interface and
 // DESIGN.md for the design.  All arithmetic on this path is integer, so results are bit-identical to the reference.
 #include "device_common.h"
+#include "forms.h"
 #include <type_traits>
 
 namespace fslic {
@@ -1337,6 +1338,9 @@ static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv
     if (!FUSE && R <= 16 && f.tab_vmode && f.tabv16_words > 0) { f.tab = f.tabv16; f.tab_words = f.tabv16_words; f.tab_dyoff = f.tabv16_dyoff; }
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;       // whole KB: what the LDS-DMA pieces fill
+    // (the form record, forms.h: the table is named after the buffer selected above)
+    const uint32_t table = f.tab_vmode ? (f.tab == f_.tabv16 && !FUSE ? kFormTabRowvec16 : kFormTabRowvec) : (FUSE && R == 16 ? kFormTab2d16 : kFormTab2d);
+    note_form(form_code(kFormBlk, R, FUSE, STRIDE, table, NOLAB));
     if constexpr (R == 32) {
         static_assert(!FUSE, "32 rows per wavefront: full pass only");
         launch((k_assign_blk2_w6<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
@@ -1357,6 +1361,7 @@ static void launch_assign_bin_t(const FrameDev& f_, int nframes, int rem, int Hv
     const FrameDev f = with_subsampled_table(f_);
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
+    note_form(form_code(kFormBin, R, true, STRIDE, R == 16 ? kFormTabRowvec : R == 4 ? kFormTab2d : f.tab_vmode ? kFormTabRowvec : kFormTab2d));
     if constexpr (R == 16) {
         launch((k_assign_bin_w6<R, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     } else if constexpr (R == 4) {
@@ -1372,6 +1377,7 @@ static void launch_assign_pre_t(const FrameDev& f_, int nframes, int rem, int Hv
     const FrameDev f = with_subsampled_table(f_);
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8), nframes);
     const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
+    note_form(form_code(kFormPre, 8, true, STRIDE, f.tab_vmode ? kFormTabRowvec : kFormTab2d));
     if (f.tab_vmode) launch((k_assign_pre<8, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
     else launch((k_assign_pre<8, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
 }
@@ -1423,17 +1429,15 @@ static int assign_rows_per_wave(const FrameDev& f, int nframes, int Hv, bool fus
     return (!fuse_update && blocks8 > 3072) ? 16 : 8;
 }
 
-template <int R>
-static void launch_assign_r(const FrameDev& f, int nframes, int rem, int stride, int Hv, int buf, int sbuf, bool fuse_update, hipStream_t st) {
+// the 32-bit kernel; 16 rows per wavefront exist for the full pass only (assign_rows_per_wave), so FUSED with R = 16 does not compile
+template <int R, bool FUSED>
+static void launch_assign_r(const FrameDev& f, int nframes, int rem, int stride, int Hv, int buf, int sbuf, hipStream_t st) {
+    static_assert(R == 8 || !FUSED, "k_assign with 16 rows per wavefront: the full pass only");
     dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
     const size_t lds = (size_t)f.lut_words * sizeof(uint32_t);
-    if (f.lut_words > 0) {
-        if (fuse_update) launch((k_assign<R, true, true>), grid, dim3(256), lds, st, f, rem, stride, Hv, buf, sbuf);
-        else launch((k_assign<R, false, true>), grid, dim3(256), lds, st, f, rem, stride, Hv, buf, sbuf);
-    } else {
-        if (fuse_update) launch((k_assign<R, true, false>), grid, dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
-        else launch((k_assign<R, false, false>), grid, dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
-    }
+    note_form(form_code(kFormK32, R, FUSED, 0, f.lut_words > 0 ? kFormTabLut : kFormTabNone));
+    if (f.lut_words > 0) launch((k_assign<R, FUSED, true>), grid, dim3(256), lds, st, f, rem, stride, Hv, buf, sbuf);
+    else launch((k_assign<R, FUSED, false>), grid, dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
 }
 
 // the fused pass of the block kernel, R rows per wavefront, storing or label-free
@@ -1488,8 +1492,9 @@ PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int
             return pg;
         }
     }
-    if (assign_rows_per_wave(f, nframes, Hv, fuse_update) >= 16) launch_assign_r<16>(f, nframes, rem, stride, Hv, buf, sbuf, fuse_update, st);
-    else launch_assign_r<8>(f, nframes, rem, stride, Hv, buf, sbuf, fuse_update, st);
+    if (fuse_update) launch_assign_r<8, true>(f, nframes, rem, stride, Hv, buf, sbuf, st);
+    else if (assign_rows_per_wave(f, nframes, Hv, false) >= 16) launch_assign_r<16, false>(f, nframes, rem, stride, Hv, buf, sbuf, st);
+    else launch_assign_r<8, false>(f, nframes, rem, stride, Hv, buf, sbuf, st);
     return pg;
 }
 
@@ -1559,9 +1564,42 @@ void launch_assign_generic(const FrameDev& f_, int nframes, int rem, int stride,
     if (Hv <= 0) return;
     const size_t n = (size_t)Hv * f.W;
     const int blocks = (int)((n + 255) / 256);
+    note_form(rec_dist ? form_code(kFormGenericRec, 0, true, 0, kFormTabNone) : form_code(kFormGeneric, 0, fuse_update, 0, kFormTabNone));
     if (rec_dist) launch(k_assign_generic_rec, dim3(blocks, 1), dim3(256), 0, st, f, rem, stride, Hv, rec_dist);
     else if (fuse_update) launch(k_assign_generic<true>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
     else launch(k_assign_generic<false>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
 }
+
+// Every code the launch functions above can note, one line per launch function and mode: an instantiation added there is added here
+// (tests/test_gpu_assign_forms.py compares the codes its cases recorded with this list, and tests/test_assign_forms_cpu.py its shape).
+// Not listed because they do not exist: k_assign<16, true, *> (16 rows are the full pass's, launch_assign_r refuses to compile it), the 32-row form on anything but the 32-row row-vector table (assign_rows_per_wave asks for tab_rows32).
+namespace {
+constexpr uint32_t B(int rows, bool fused, int stride, uint32_t table, bool nolab) { return form_code(kFormBlk, rows, fused, stride, table, nolab); }
+constexpr uint32_t N(int rows, int stride, uint32_t table) { return form_code(kFormBin, rows, true, stride, table); }
+constexpr uint32_t kRv = kFormTabRowvec, kRv16 = kFormTabRowvec16, k2d = kFormTab2d, k2d16 = kFormTab2d16;
+const uint32_t kAssignForms[] = {
+    // launch_assign_blk_t, full pass (stride 1): storing, then closing a label-free group
+    B(8, false, 1, kRv, false), B(8, false, 1, kRv16, false), B(8, false, 1, k2d, false),
+    B(16, false, 1, kRv, false), B(16, false, 1, kRv16, false), B(16, false, 1, k2d, false), B(32, false, 1, kRv, false),
+    B(8, false, 1, kRv, true), B(8, false, 1, kRv16, true), B(8, false, 1, k2d, true),
+    B(16, false, 1, kRv, true), B(16, false, 1, kRv16, true), B(16, false, 1, k2d, true), B(32, false, 1, kRv, true),
+    // launch_assign_blk_t, fused pass: storing (a frame redone, a slot under the sticky fallback), then label-free
+    B(8, true, 1, kRv, false), B(8, true, 2, kRv, false), B(8, true, 3, kRv, false), B(8, true, 1, k2d, false), B(8, true, 2, k2d, false), B(8, true, 3, k2d, false),
+    B(16, true, 1, kRv, false), B(16, true, 2, kRv, false), B(16, true, 3, kRv, false), B(16, true, 1, k2d16, false), B(16, true, 2, k2d16, false), B(16, true, 3, k2d16, false),
+    B(8, true, 1, kRv, true), B(8, true, 2, kRv, true), B(8, true, 3, kRv, true), B(8, true, 1, k2d, true), B(8, true, 2, k2d, true), B(8, true, 3, k2d, true),
+    B(16, true, 1, kRv, true), B(16, true, 2, kRv, true), B(16, true, 3, kRv, true), B(16, true, 1, k2d16, true), B(16, true, 2, k2d16, true), B(16, true, 3, k2d16, true),
+    // launch_assign_bin_t (the cluster pass fused in)
+    N(4, 3, k2d), N(8, 1, kRv), N(8, 2, kRv), N(8, 3, kRv), N(8, 1, k2d), N(8, 2, k2d), N(8, 3, k2d), N(16, 1, kRv), N(16, 2, kRv), N(16, 3, kRv),
+    // launch_assign_pre_t (preemptive mode)
+    form_code(kFormPre, 8, true, 1, kRv), form_code(kFormPre, 8, true, 2, kRv), form_code(kFormPre, 8, true, 3, kRv),
+    form_code(kFormPre, 8, true, 1, k2d), form_code(kFormPre, 8, true, 2, k2d), form_code(kFormPre, 8, true, 3, k2d),
+    // launch_assign_r (the 32-bit kernel; the stride is a run-time argument)
+    form_code(kFormK32, 8, true, 0, kFormTabLut), form_code(kFormK32, 8, true, 0, kFormTabNone), form_code(kFormK32, 8, false, 0, kFormTabLut),
+    form_code(kFormK32, 8, false, 0, kFormTabNone), form_code(kFormK32, 16, false, 0, kFormTabLut), form_code(kFormK32, 16, false, 0, kFormTabNone),
+    // launch_assign_generic
+    form_code(kFormGeneric, 0, true, 0, kFormTabNone), form_code(kFormGeneric, 0, false, 0, kFormTabNone), form_code(kFormGenericRec, 0, true, 0, kFormTabNone),
+};
+}  // namespace
+const uint32_t* assign_forms(int* n) { *n = (int)(sizeof(kAssignForms) / sizeof(kAssignForms[0])); return kAssignForms; }
 
 }  // namespace fslic

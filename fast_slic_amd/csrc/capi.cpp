@@ -3,6 +3,7 @@
 // Part of the host engine, see engine_internal.h.
 #include "engine_internal.h"
 #include "crf.h"
+#include "forms.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -322,6 +323,21 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot) {
 int fslic_hip_uncovered_redos(fslic_engine* e, int slot) {
     if (!e || slot < 0 || slot >= (int)e->slots.size()) return -1;
     return __atomic_load_n(&e->slots[slot].n_uncovered_redo, __ATOMIC_RELAXED);
+}
+
+// ---- the form record (forms.h; the record itself is in host_utils.cpp) ----
+int fslic_hip_debug_forms_seen(uint32_t* codes, int cap, int clear) {
+    if (cap < 0 || (cap > 0 && !codes)) return -1;
+    return fslic::forms_seen(codes, cap, clear != 0);
+}
+
+int fslic_hip_debug_forms_all(uint32_t* codes, int cap) {
+    if (cap < 0 || (cap > 0 && !codes)) return -1;
+    int na = 0, np = 0;
+    const uint32_t* a = fslic::assign_forms(&na);
+    const uint32_t* p = fslic::preempt_forms(&np);
+    for (int i = 0; i < na + np && i < cap; i++) codes[i] = i < na ? a[i] : p[i - na];
+    return na + np;
 }
 
 // ---- SimpleCRF (src/simple-crf.{h,hpp,cpp}): host state and bookkeeping here, inference in crf.hip --------------------------------

@@ -102,10 +102,14 @@ struct GroupJob {
 //   FSLIC_FUSEBIN      the cluster pass between two assign passes: 1 (default) fused into the assign kernel for launches that do
 //                      not fill the chip and a separate launch (k_bin_clusters<1>) otherwise; 0 always separate (round 2; also what
 //                      a frame with a stale pixel is redone with); 2 always fused (A/B measurements)
+//   FSLIC_BLOCKS_SCALE testing aid: an integer >= 1 (default 1) that multiplies assign_blocks8 (kernels.h), the launch size every
+//                      rows-per-wavefront and fusing rule is compared with, and nothing else: a small frame then takes the kernel
+//                      forms of a chip-filling launch (tests/test_gpu_assign_forms.py)
 struct Knobs {
     int group_size;
     bool use_graphs, poison, host_timing;
     int fuse_bin;
+    int blocks_scale;
 };
 const Knobs& knobs();
 

@@ -695,7 +695,9 @@ int group_finish(fslic_engine* e, Slot& s) {
         for (int attempt = 0; attempt < 2 && !s.generic && hm[kStFlags] != 0; attempt++) {
             const bool overflow = (hm[kStFlags] & kFlagListOverflow) != 0;
             const bool uncovered = (hm[kStFlags] & kFlagUncoveredPixel) != 0;
-            if (uncovered) {
+            // (an overflowing block assigns nothing, so later passes of that attempt work on centres that may well leave pixels uncovered:
+            // the flag then is a by-product, the redo is the generic one, and neither the counter nor the slot's fallback is concerned)
+            if (uncovered && !overflow) {
                 if (!s.store_labels) s.store_seen_credit = true;
                 s.store_labels = true; s.store_H = H; s.store_W = W; s.store_K = K; s.store_p = s.p;
                 __atomic_fetch_add(&s.n_uncovered_redo, 1, __ATOMIC_RELAXED);      // (read by fslic_hip_uncovered_redos without the engine lock)

@@ -2,10 +2,12 @@
 // graph), the stage entry points used by the parity tests (LAB conversion, connectivity on a caller's label map) and the
 // superpixel-graph utilities on a finished label map (src/fast-slic.cpp).  Part of the host engine, see engine_internal.h.
 #include "engine_internal.h"
+#include "forms.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 
 using namespace fslic;
 
@@ -334,3 +336,30 @@ int fslic_hip_copy_bandwidth(fslic_engine* e, size_t bytes, int reps, double* gb
 }
 
 }  // extern "C"
+
+// ---- the form record (forms.h): which kernel forms of the assign family and of k_preempt_update this process has enqueued ----------
+// A fixed table of distinct codes under one mutex: a launch takes the lock once, uncontended unless another slot's thread enqueues at the
+// same moment, and scans the few dozen codes seen so far.  Nothing on the device.
+namespace fslic {
+namespace {
+constexpr int kFormCap = 128;      // (the complete list holds 65 codes)
+std::mutex g_forms_mu;
+uint32_t g_forms[kFormCap];
+int g_nforms = 0;
+bool g_forms_overflow = false;
+}  // namespace
+void note_form(uint32_t code) {
+    std::lock_guard<std::mutex> lock(g_forms_mu);
+    for (int i = 0; i < g_nforms; i++)
+        if (g_forms[i] == code) return;
+    if (g_nforms < kFormCap) g_forms[g_nforms++] = code;
+    else g_forms_overflow = true;
+}
+int forms_seen(uint32_t* codes, int cap, bool clear) {
+    std::lock_guard<std::mutex> lock(g_forms_mu);
+    const int n = g_forms_overflow ? -2 : g_nforms;
+    for (int i = 0; codes && i < g_nforms && i < cap; i++) codes[i] = g_forms[i];
+    if (clear) { g_nforms = 0; g_forms_overflow = false; }
+    return n;
+}
+}  // namespace fslic

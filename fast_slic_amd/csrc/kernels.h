@@ -204,7 +204,13 @@ struct PassGeom {
 inline int visited_rows(int H, int rem, int stride) { return (H - rem + stride - 1) / stride; }
 // Eight-row assign blocks (kTileW columns x kWavesPerBlock wavefronts x 8 rows) of a launch over Hv visited rows of nframes frames: the
 // size every rows-per-wavefront and fusing threshold is compared against, whatever block height the launch then takes.
-inline int assign_blocks8(int W, int Hv, int nframes) { return nframes * ((W + kTileW - 1) / kTileW) * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8)); }
+// blocks_scale() (FSLIC_BLOCKS_SCALE, engine_internal.h; 1 unless a test sets it) multiplies the count and nothing else: no grid, table or
+// kernel argument derives from it, so a small frame takes the forms of a chip-filling launch.
+int blocks_scale();      // pipeline.cpp
+inline int assign_blocks8(int W, int Hv, int nframes) {
+    const long long b = (long long)nframes * ((W + kTileW - 1) / kTileW) * ((Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8)) * blocks_scale();
+    return b > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)b;
+}
 
 struct CcaDev {
     size_t frame_bytes;

@@ -39,11 +39,14 @@ Knobs read_knobs() {
     k.host_timing = getenv("FSLIC_HOST_TIMING") != nullptr;
     const char* fb = getenv("FSLIC_FUSEBIN");
     k.fuse_bin = fb ? std::min(std::max(atoi(fb), 0), 2) : 1;
+    const char* bs = getenv("FSLIC_BLOCKS_SCALE");
+    k.blocks_scale = bs ? std::min(std::max(atoi(bs), 1), 1 << 20) : 1;
     return k;
 }
 const Knobs g_knobs = read_knobs();      // once, when the library is loaded
 }  // namespace
 const Knobs& knobs() { return g_knobs; }
+int blocks_scale() { return g_knobs.blocks_scale; }
 
 // ---- slot ownership ------------------------------------------------------------------------------------------------
 namespace {

@@ -18,6 +18,7 @@
 // float-distance variants (src/context.h:100-125: BaseContext<float>::iterate is the same template, src/context.cpp:152-181) their
 // own assign kernels on the bins of the active clusters, with the member sums restricted to the active cells.
 #include "device_common.h"
+#include "forms.h"
 #include <atomic>
 
 namespace fslic {
@@ -190,13 +191,22 @@ void launch_preempt_update(const FrameDev& f_, int nframes, int buf, int sbuf, b
         constexpr int kMaxLds = (8192 + 2 * 4096 + 1) * 4 + 8192 * 2 + 16;
         static std::atomic<int> attr_state[64];
         if (!max_dynamic_lds_on_this_device(k_preempt_update<true>, kMaxLds, attr_state) && lds > 64 * 1024) {
+            note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true));
             launch(k_preempt_update<false>, dim3(nframes), dim3(1024), 0, st, f, rebin_all ? 1 : 0, l1_thres);
             return;
         }
+        note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, false));
         launch(k_preempt_update<true>, dim3(nframes), dim3(1024), lds, st, f, rebin_all ? 1 : 0, l1_thres);
     } else {
+        note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true));
         launch(k_preempt_update<false>, dim3(nframes), dim3(1024), 0, st, f, rebin_all ? 1 : 0, l1_thres);
     }
 }
+
+// the codes launch_preempt_update can note: the per-cell-list form (K <= 8192 and <= 4096 cells) and the all-pairs form (forms.h)
+static const uint32_t kPreemptForms[] = {
+    form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, false), form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true),
+};
+const uint32_t* preempt_forms(int* n) { *n = 2; return kPreemptForms; }
 
 }  // namespace fslic

@@ -263,6 +263,19 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot);
  * can.  Diagnostics aid. */
 int fslic_hip_uncovered_redos(fslic_engine* e, int slot);
 
+/* Debug entries, for tests only: the record of kernel FORMS.  The assign pass is a family of template instantiations picked by the
+ * spatial table, the stride, the launch size and the mode, and the preemptive update has two forms; every launch site notes a code for the
+ * instantiation it chose when it enqueues the launch or records it into a graph (a replay adds nothing).  The record is the process-wide
+ * set of distinct codes, thread-safe, host side only.  A code is
+ *   bits 0-3 family (1 blk, 2 bin, 3 pre, 4 k32, 5 generic, 6 generic_rec, 7 preempt_update) | bits 4-9 rows per wavefront |
+ *   bit 10 fused | bits 11-13 stride template (0: run-time argument) | bits 14-16 table (0 none, 1 row-vector, 2 the full pass's 16-row
+ *   row-vector table, 3 2-D, 4 2-D for 16 rows, 5 LUT) | bit 17 label-free | bit 18 all-pairs (preempt_update; 0: per-cell lists).
+ * forms_seen: up to `cap` recorded codes into `codes` (may be NULL with cap 0); returns how many are recorded, -2 when the record
+ * overflowed; `clear` != 0 empties the record afterwards.  forms_all: the complete list of codes the dispatch can produce (a static table
+ * next to the launch functions), up to `cap` into `codes`; returns its length.  -1: cap < 0, or codes NULL with cap > 0. */
+int fslic_hip_debug_forms_seen(uint32_t* codes, int cap, int clear);
+int fslic_hip_debug_forms_all(uint32_t* codes, int cap);
+
 /* Measurement aid (no counterpart in the reference): bytes read + written per second, in GB/s, of a plain streaming copy of
  * `bytes` on the engine's GPU (best of `reps` launches, HIP events) -- the measured HBM rate that bench.py prints next to the 8 TB/s of
  * the specification.  Allocates and frees 2 x `bytes` of device memory. */

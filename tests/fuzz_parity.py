@@ -47,6 +47,15 @@ def extreme_options(rng, kw):
     return kw
 
 
+def forms_met():
+    """The kernel forms of the assign family this run enqueued, decoded (the library's record, _binding.forms_seen): printed at the end
+    of a run beside the tally of paths, so that a sweep says which instantiations it met."""
+    from fast_slic_amd import _binding as B
+    if not hasattr(B.load_library(), "fslic_hip_debug_forms_seen"):      # (an A/B build given through FSLIC_LIB may lack the record)
+        return "not recorded by this library"
+    return sorted(B.forms_seen())
+
+
 def variants_main(seed, budget):
     """Mode `variants` (python tests/fuzz_parity.py SEED SECONDS variants): the same sweep for the paths the plain-C oracle does not restate --
     SlicRealDist / L2 / NoQ, the preemptive mode (Slic and the float family) and the Euclidean spatial table -- against the UNMODIFIED
@@ -125,7 +134,7 @@ def variants_main(seed, budget):
         if bad:
             print("\n".join(bad[:10]))
             sys.exit(1)
-    print("fuzz_parity variants seed %d: %d cases, %d frames, all bit-exact; %.0f s" % (seed, n_cases, n_frames, time.time() - t0))
+    print("fuzz_parity variants seed %d: %d cases, %d frames, all bit-exact; %.0f s; forms %s" % (seed, n_cases, n_frames, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -181,7 +190,7 @@ def cca_main(seed, budget):
             sys.exit(1)
         n_cases += 1
         kinds_seen[kind] = kinds_seen.get(kind, 0) + 1
-    print("fuzz_parity cca seed %d: %d maps, all bit-exact; %s; %.0f s" % (seed, n_cases, kinds_seen, time.time() - t0))
+    print("fuzz_parity cca seed %d: %d maps, all bit-exact; %s; %.0f s; forms %s" % (seed, n_cases, kinds_seen, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -256,7 +265,7 @@ def lsc_main(seed, budget):
         if bad:
             print("\n".join(bad))
             sys.exit(1)
-    print("fuzz_parity lsc seed %d: %d cases, deterministic, group == alone, worst best-overlap %.4f; %.0f s" % (seed, n_cases, worst, time.time() - t0))
+    print("fuzz_parity lsc seed %d: %d cases, deterministic, group == alone, worst best-overlap %.4f; %.0f s; forms %s" % (seed, n_cases, worst, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -337,7 +346,7 @@ def warm_main(seed, budget):
         if bad:
             print("\n".join(bad[:10]))
             sys.exit(1)
-    print("fuzz_parity warm seed %d: %d cases, all bit-exact; paths %s; %.0f s" % (seed, n_cases, paths, time.time() - t0))
+    print("fuzz_parity warm seed %d: %d cases, all bit-exact; paths %s; %.0f s; forms %s" % (seed, n_cases, paths, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -368,6 +377,8 @@ def pipeline_main(seed, budget):
     while time.time() - t0 < budget and (max_cases == 0 or n_sub < max_cases):
         burst = []                       # submissions between two drains
         for _ in range(int(rng.integers(1, 25))):
+            if max_cases and n_sub + len(burst) >= max_cases:      # (FUZZ_CASES ends the sequence inside a burst: a prefix of the same sequence)
+                break
             H, W, K, kw, n = pool[int(rng.integers(0, len(pool)))] if rng.random() < 0.8 else pool[0]
             frames = [np.ascontiguousarray(variant("ABCD"[int(rng.integers(0, 4))], H, W, seed=int(rng.integers(0, 1 << 30)))) for _ in range(n)]
             cls = np.stack([orc.initialize_clusters(f, K) for f in frames])
@@ -392,7 +403,7 @@ def pipeline_main(seed, budget):
             n_sub += 1
             n_frames += n
         print("  drained: %d submissions so far" % n_sub, flush=True)
-    print("fuzz_parity pipeline seed %d (%d slots, batching %d): %d submissions, %d frames, all bit-exact; %.0f s" % (seed, n_slots, batching, n_sub, n_frames, time.time() - t0))
+    print("fuzz_parity pipeline seed %d (%d slots, batching %d): %d submissions, %d frames, all bit-exact; %.0f s; forms %s" % (seed, n_slots, batching, n_sub, n_frames, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -462,7 +473,7 @@ def graph_main(seed, budget):
             print("  BAD")
             sys.exit(1)
         n_cases += 1
-    print("fuzz_parity graph seed %d: %d maps, all bit-exact; %.0f s" % (seed, n_cases, time.time() - t0))
+    print("fuzz_parity graph seed %d: %d maps, all bit-exact; %.0f s; forms %s" % (seed, n_cases, time.time() - t0, forms_met()))
     e.close()
 
 
@@ -521,7 +532,7 @@ def threads_main(seed, budget):
         print("BAD")
         print("\n".join(errors[:10]))
         sys.exit(1)
-    print("fuzz_parity threads seed %d: %d calls from 6 threads on 4 slots, all bit-exact; %.0f s" % (seed, sum(counts), time.time() - t0))
+    print("fuzz_parity threads seed %d: %d calls from 6 threads on 4 slots, all bit-exact; %.0f s; forms %s" % (seed, sum(counts), time.time() - t0, forms_met()))
     e.close()
 
 
@@ -616,7 +627,7 @@ def main():
         if bad:
             print("\n".join(bad[:10]))
             sys.exit(1)
-    print("fuzz_parity seed %d: %d cases, %d frames, all bit-exact; paths %s; %.0f s" % (seed, n_cases, n_frames, paths, time.time() - t0))
+    print("fuzz_parity seed %d: %d cases, %d frames, all bit-exact; paths %s; %.0f s; forms %s" % (seed, n_cases, n_frames, paths, time.time() - t0, forms_met()))
     e.close()
 
 

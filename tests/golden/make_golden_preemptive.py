@@ -3,7 +3,7 @@ float-distance variants SlicRealDist / SlicRealDistL2 / SlicRealDistNoQ with pre
 
     make -C oracle ref && python tests/golden/make_golden_preemptive.py      (build container only: needs /root/reference)
 
-Output (committed): tests/golden/preemptive_cases.npz.  The mode is deterministic integer arithmetic (thread-count and
+Output (committed): tests/golden/preemptive_cases.npz and tests/golden/preemptive_form_cases.npz.  The mode is deterministic integer arithmetic (thread-count and
 arch invariant, checked here), so the GPU tests compare bit for bit, including the is_updatable counters.
 """
 import json
@@ -30,6 +30,23 @@ CASES = [
     ("A_480x640_k200_iter20", "A", 480, 640, 200, 0.05, dict(max_iter=20)),
     ("B_480x640_k200", "B", 480, 640, 200, 0.1, {}),
     ("A_720x1280_k1600", "A", 720, 1280, 1600, 0.05, {}),
+]
+
+# Kept in a file of their own, tests/golden/preemptive_form_cases.npz (`python tests/golden/make_golden_preemptive.py forms` writes that
+# file alone): one small ragged frame per form of the preemptive passes, for tests/test_gpu_assign_forms.py.
+FORM_CASES = [
+    # k_assign_pre x stride template x
+    # table form -- the row-vector table from S ~ 45 on, the 2-D table below -- with last column tiles of 1, 2 and 63 pixels
+    ("form_rowvec_s1_A_150x193_k12", "A", 150, 193, 12, 0.05, dict(subsample_stride=1)),
+    ("form_rowvec_s2_B_200x130_k10", "B", 200, 130, 10, 0.05, dict(subsample_stride=2)),
+    ("form_rowvec_s3_A_97x260_k10", "A", 97, 260, 10, 0.02, dict(subsample_stride=3)),
+    ("form_2d_s1_A_65x130_k40", "A", 65, 130, 40, 0.05, dict(subsample_stride=1)),
+    ("form_2d_s2_B_130x63_k30", "B", 130, 63, 30, 0.1, dict(subsample_stride=2)),
+    ("form_2d_s3_D_121x193_k100", "D", 121, 193, 100, 0.05, dict(subsample_stride=3, max_iter=4)),
+    # k_preempt_update: per-cell lists up to K = 8192, all pairs from 8193 on -- the same frame on either side of the cut (S = 2: the
+    # assign passes are the generic kernel's)
+    ("form_update_A_161x207_k8192", "A", 161, 207, 8192, 0.05, dict(max_iter=4)),
+    ("form_update_A_161x207_k8193", "A", 161, 207, 8193, 0.05, dict(max_iter=4)),
 ]
 
 
@@ -106,11 +123,8 @@ def lsc_cases(out):
         print(name, "segments", len(np.unique(labels)), "is_updatable", np.unique(cl["is_updatable"], return_counts=True))
 
 
-def main():
-    out = {}
-    realdist_cases(out)
-    lsc_cases(out)
-    for name, var, H, W, K, thres, kw in CASES:
+def slic_cases(out, cases):
+    for name, var, H, W, K, thres, kw in cases:
         img = variant(var, H, W)
         cl0 = ref.initialize_clusters(img, K)
         ref.set_preemptive(True, thres)
@@ -128,6 +142,18 @@ def main():
         out[name + "/prelabels"] = pre
         out[name + "/kwargs"] = np.array(json.dumps(kw))
         print(name, "segments", len(np.unique(labels)), "is_updatable", np.unique(cl["is_updatable"], return_counts=True))
+
+
+def main():
+    forms = {}
+    slic_cases(forms, FORM_CASES)
+    np.savez_compressed(os.path.join(HERE, "preemptive_form_cases.npz"), **forms)
+    if sys.argv[1:] == ["forms"]:
+        return
+    out = {}
+    realdist_cases(out)
+    lsc_cases(out)
+    slic_cases(out, CASES)
     np.savez_compressed(os.path.join(HERE, "preemptive_cases.npz"), **out)
 
 

@@ -102,4 +102,4 @@ def test_the_library_reads_no_untested_switch():
     for fn in glob.glob(os.path.join(root, "fast_slic_amd", "csrc", "*")):
         if os.path.isfile(fn):
             found |= set(re.findall(r'getenv\("(\w+)"\)', open(fn).read()))
-    assert found == {"FSLIC_FUSEBIN", "FSLIC_GROUP", "FSLIC_GRAPH", "FSLIC_POISON", "FSLIC_HOST_TIMING"}, found
+    assert found == {"FSLIC_FUSEBIN", "FSLIC_GROUP", "FSLIC_GRAPH", "FSLIC_POISON", "FSLIC_HOST_TIMING", "FSLIC_BLOCKS_SCALE"}, found

@@ -7,8 +7,9 @@ passes for that work.  Everything must be the oracle's, bit for bit, on either p
 
 Small one-frame shapes take the fused cluster pass and never reach this code, so every case here is a multi-frame group sized by
 the launch rules of assign.hip (assign_blocks8 > 640 to leave the fused cluster pass, > 2048 for 16 rows per wavefront with the
-2-D table, > 3072 with the row-vector table, which tables.cpp builds from S ~ 45 on); `blocks8` below restates the rule and every
-case asserts the path it was chosen for.  The pre-connectivity plane the library hands out is that of the group's first frame.
+2-D table, > 3072 with the row-vector table, which tables.cpp builds from S ~ 45 on).  Every case asserts the form it was chosen
+for as the LIBRARY recorded it (B.forms_seen, DESIGN.md "The form record"): a rule moved in C++ fails the case instead of silently
+exercising another instantiation.  The pre-connectivity plane the library hands out is that of the group's first frame.
 """
 import functools
 import os
@@ -25,22 +26,14 @@ from util import describe_mismatch, cluster_fields_equal
 pytestmark = pytest.mark.gpu
 
 
-def blocks8(H, W, n, stride):
-    """kernels.h, assign_blocks8 of a group's first subsampled pass."""
-    hv = (H + stride - 1) // stride
-    return n * ((W + 63) // 64) * ((hv + 31) // 32)
-
-
-def vtable(H, W, K, stride):
-    """tables.cpp: the row-vector table replaces the 2-D one when the latter would exceed 12288 bytes."""
-    S = orc.S_of(H, W, K)
-    return (S + 2) * (2 * (S + max(7 * min(stride, 3), 15)) + 1) * 2 > 12288
-
-
-def expected_form(H, W, K, n, stride):
-    b, vt = blocks8(H, W, n, stride), vtable(H, W, K, stride)
-    assert b > 640, "the group would take the fused cluster pass"
-    return ("rowvec" if vt else "2d", 16 if b > (3072 if vt else 2048) else 8)
+def fused_forms(forms):
+    """(table, rows per wavefront, label-free) of the fused passes of the block kernel among recorded form names."""
+    out = set()
+    for f in forms:
+        w = f.split()
+        if w[0] == "blk" and w[2] == "fused":
+            out.add(("2d" if w[4] in ("2d", "tabs16") else w[4], int(w[1][1:]), w[5] == "nolab"))
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,8 +82,10 @@ def uncovered_in_some_pass(img, cl0, stride, max_iter):
     return False
 
 
-@pytest.fixture(scope="module")
+@pytest.fixture
 def eng():
+    """A fresh engine per case: its first sighting of a work is enqueued directly, which is when the form record is written (a replay
+    of a recorded graph notes nothing), so a case asserts the same whether it runs alone, again or in suite order."""
     from fast_slic_amd import Engine
     e = Engine(0, 2)
     yield e
@@ -148,12 +143,18 @@ CASES = [(name, st, mi) for name in SHAPES for st, mi in [(3, 10), (1, 1), (2, 4
 @pytest.mark.parametrize("name,stride,max_iter", CASES)
 def test_parity_on_covered_inputs(eng, name, stride, max_iter):
     n, H, W, K = SHAPES[name]
-    assert expected_form(H, W, K, n, stride) == FORMS[name]
     refs = two_images(H, W, K, n, stride, max_iter)
     assert not any((r[4] == 0xFFFF).any() or r[5] for r in refs), "grid-seeded centres were meant to cover every pixel"
     before = eng.uncovered_redos()
+    B.forms_seen(clear=True)
     assert_group("%s stride %d max_iter %d" % (name, stride, max_iter), run_group(eng, refs, stride, max_iter), refs)
+    forms = B.forms_seen()
     assert eng.uncovered_redos() == before
+    # the group's first sighting is enqueued directly: the record is this call's -- label-free fused passes of the case's form alone
+    # (the 16-row 2-D form reads its own table, `tabs16`), no cluster pass fused in, and a label-free full pass
+    assert fused_forms(forms) == {FORMS[name] + (True,)}, sorted(forms)
+    assert ("blk r16 fused s%d tabs16 nolab" % stride in forms) == (FORMS[name] == ("2d", 16)), sorted(forms)
+    assert not any(f.startswith("bin") for f in forms) and any(f.startswith("blk") and " full " in f and f.endswith("nolab") for f in forms), sorted(forms)
 
 
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -247,15 +248,19 @@ def test_arena_reuse_leaves_no_foreign_label_in_the_plane():
     stride, max_iter = 1, 3
     H1, W1, K1 = 200, 448, 90
     H2, W2, K2 = 192, 464, 60
-    assert blocks8(H1, W1, 16, stride) > 640 and blocks8(H2, W2, 16, stride) > 640
     first = two_images(H1, W1, K1, 16, stride, max_iter, scatter=70)
     assert all((r[4] == 0xFFFF).any() or r[5] > 0 for r in first)
     second = two_images(H2, W2, K2, 16, stride, max_iter)
     e = Engine(0, 1)
     try:
+        B.forms_seen(clear=True)
         assert_group("scattered 200x448", run_group(e, first, stride, max_iter), first)
+        # (the group left the fused cluster pass and tried the label-free passes first, then was redone with storing ones)
+        assert fused_forms(B.forms_seen()) == {("2d", 8, True), ("2d", 8, False)}, sorted(B.forms_seen())
         assert e.uncovered_redos() > 0
+        B.forms_seen(clear=True)
         got = run_group(e, second, stride, max_iter)
+        assert fused_forms(B.forms_seen()) == {("2d", 8, True)}, "the covered group was meant to take the label-free passes"
         pre = got[2]
         assert not ((pre >= K2) & (pre != 0xFFFF)).any(), "labels of the previous geometry in the plane"
         assert_group("covered 192x464", got, second)

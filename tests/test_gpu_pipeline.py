@@ -130,7 +130,12 @@ def test_config4_all_64_frames():
 
 
 def test_one_group_of_eight_4k_frames():
+    B.forms_seen(clear=True)
     _run_pipeline(2160, 3840, 1600, list(range(8)), 8, 2, 5)
+    # 8 x 3840x2160 is the one operating point whose full pass is large enough for 32 rows per wavefront (assign.hip,
+    # assign_rows_per_wave): read from the library's record, label-free or -- with the cluster pass fused in, FSLIC_FUSEBIN=2 -- storing
+    forms = B.forms_seen()
+    assert any(f.startswith("blk r32 full s1 rowvec") for f in forms), sorted(forms)
 
 
 # ---- the other operating points bench.py prints: same pipeline, same slots, same batching, every frame --
@@ -373,10 +378,12 @@ def test_parity_with_the_cluster_pass_always_fused():
     assert r.returncode == 0 and " passed" in tail, tail
 
 
-@pytest.mark.parametrize("switch", ["FSLIC_FUSEBIN=0", "FSLIC_GROUP=1", "FSLIC_GROUP=16", "FSLIC_GRAPH=0", "FSLIC_POISON=1", "FSLIC_HOST_TIMING=1"])
+@pytest.mark.parametrize("switch", ["FSLIC_FUSEBIN=0", "FSLIC_GROUP=1", "FSLIC_GROUP=16", "FSLIC_GRAPH=0", "FSLIC_POISON=1", "FSLIC_HOST_TIMING=1", "FSLIC_BLOCKS_SCALE=20"])
 def test_parity_under_every_switch_the_library_reads(switch):
     """Every environment switch of the shipping library (grep getenv fast_slic_amd/csrc: FSLIC_FUSEBIN, FSLIC_GROUP, FSLIC_GRAPH,
-    FSLIC_POISON, FSLIC_HOST_TIMING; read once when the library is loaded, hence a separate interpreter) against the oracle: the
+    FSLIC_POISON, FSLIC_HOST_TIMING, FSLIC_BLOCKS_SCALE; read once when the library is loaded, hence a separate interpreter) against the
+    oracle (FSLIC_BLOCKS_SCALE=20: a 1280x720 frame's 160 .. 460 eight-row blocks count as 3200 and more, so the BASELINE sizes leave the
+    fused cluster pass for the label-free 16-row forms and a 16-row full pass): the
     BASELINE sizes (C2, C3, C3b), the batch entry points FSLIC_GROUP cuts into groups (64 frames of C4, device-resident and host
     batches), a replayed pipeline, and the overflow / redo paths on a poisoned arena."""
     import os
@@ -398,7 +405,8 @@ def test_parity_under_every_switch_the_library_reads(switch):
 def test_sixteen_row_fused_pass_on_the_2d_table_at_every_stride(stride, n):
     """Launches of more than 2048 eight-row blocks with the 2-D spatial table (S <= 40) take the fused passes with 16 rows per wavefront
     (launch_assign, assign.hip; its own table `tabs16`): 8 / 12 / 16 frames of 1280x720 K=1600 in ONE group reach that at subsample_stride
-    1 / 2 / 3 (3680 / 2880 / 2560 blocks), the bench only at 3.  Every frame against the oracle, twice (the second group replays)."""
+    1 / 2 / 3 (3680 / 2880 / 2560 blocks), the bench only at 3.  Every frame against the oracle, twice (the second group replays); that the
+    16-row form on `tabs16` is what ran is read from the library's record."""
     import torch
     H, W, K = 720, 1280, 1600
     frames = [variant("A", H, W, seed=40 + i) for i in range(n)]
@@ -411,6 +419,7 @@ def test_sixteen_row_fused_pass_on_the_2d_table_at_every_stride(stride, n):
         torch.cuda.synchronize()
         a_rgb = e.pointer_array([t.data_ptr() for t in d_rgb])
         a_lab = e.pointer_array([t.data_ptr() for t in d_lab])
+        B.forms_seen(clear=True)
         for rep in range(3):
             cls = [orc.initialize_clusters(f, K) for f in frames]
             a_cls = e.pointer_array([c.ctypes.data for c in cls])
@@ -421,5 +430,7 @@ def test_sixteen_row_fused_pass_on_the_2d_table_at_every_stride(stride, n):
                 got = d_lab[i].cpu().numpy().view(np.uint16)
                 assert np.array_equal(got, exp[i][0]), describe_mismatch("stride %d rep %d frame %d" % (stride, rep, i), got, exp[i][0])
                 assert cls[i].tobytes() == exp[i][1].tobytes(), (stride, rep, i)
+        forms = B.forms_seen()
+        assert "blk r16 fused s%d tabs16 nolab" % stride in forms and not any(f.startswith("blk r8 fused") for f in forms), sorted(forms)
     finally:
         e.close()
