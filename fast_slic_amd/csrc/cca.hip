@@ -1267,11 +1267,15 @@ __global__ __launch_bounds__(256) void k_cca_relabel(CcaDev c, ExportDev ex, int
     }
     c.select(z);
     // One block = one 64x32 tile, thread = 4 consecutive pixels of one row, two rows per thread: 8-byte loads of the component numbers, a look-up in the tile's (contiguous, at most
-    // 4 KB) table of final labels, 8-byte stores.  Frames whose width is not a multiple of 4 take the scalar form.
+    // 4 KB) table of final labels, 8-byte stores.  Frames whose width is not a multiple of 4, and frames whose output map (the caller's
+    // buffer: any 2-byte-aligned address, include/fslic_hip.h) is not 8-byte aligned, take the scalar form: with W % 4 == 0 every row
+    // start keeps the residue of the map's base, so the base decides for all of the frame's stores.  (The component numbers `lid` are the
+    // engine's own plane, 8-byte aligned by the arena's carve.)  Uniform per block: one frame per blockIdx.y.
     constexpr int T = kCcaTile, TH = kCcaTileH;
     const int tiles_x = c.tiles_x, tiles_y = (c.H + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y;
-    const bool vec = (c.W & 3) == 0;
+    const int aligned8 = ((reinterpret_cast<uintptr_t>(c.out) & 7) == 0) ? 1 : 0;
+    const bool vec = (c.W & 3) == 0 && aligned8;
     // The tile's table of final labels goes into LDS first -- as much of it as the tile's pixels refer to (the largest component number
     // among them, found by a block-wide maximum: a few hundred entries), with coalesced 16-byte loads.  Read straight from memory every
     // pixel's look-up was a 64-address gather through the vector-memory path (eight per thread), which bounded the pass (65 us per

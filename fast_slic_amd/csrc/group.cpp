@@ -43,6 +43,9 @@ int fill_job(GroupJob& j, const fslic_params* p, int H, int W, int K, int n,
              const uint8_t* const* d_rgb, fslic_cluster* const* clusters, uint16_t* const* d_out) {
     if (n < 1 || n > (int)kMaxGroup || !d_rgb || !clusters || !d_out) return fail(FSLIC_E_INVALID, "bad group arguments");
     if (!p) return fail(FSLIC_E_INVALID, "params is NULL");
+    // a label map is uint16_t[H * W]: an odd address cannot hold one (include/fslic_hip.h; the frames themselves may lie anywhere)
+    for (int i = 0; i < n; i++)
+        if (reinterpret_cast<uintptr_t>(d_out[i]) & 1) return fail(FSLIC_E_INVALID, "d_labels[" + std::to_string(i) + "] is not 2-byte aligned");
     j.p = *p; j.H = H; j.W = W; j.K = K; j.n = n;
     for (int i = 0; i < n; i++) { j.d_rgb[i] = d_rgb[i]; j.clusters[i] = clusters[i]; j.d_out[i] = d_out[i]; }
     return FSLIC_OK;

@@ -107,7 +107,15 @@ int fslic_hip_iterate(fslic_engine* e, const fslic_params* p, int H, int W, int 
 /* Same computation with the frame already resident in HBM (NEW surface, absent in the reference;
  * SURVEY.md section 8f-4).  d_rgb / d_labels are DEVICE pointers on the engine's GPU; clusters stays a
  * host pointer (K*32 bytes).  `slot` selects the in-flight slot / stream (0 <= slot < n_slots).
- * The call returns after the slot's stream has been synchronised. */
+ * The call returns after the slot's stream has been synchronised.
+ * Alignment of the device buffers, here and in every entry point below that takes d_rgb / d_labels (the kernels read and write the
+ * caller's memory in place, e.g. frame i of one stacked tensor):
+ *   d_rgb    : any address.  A frame at a 4-byte-aligned address is read three dwords per four pixels; any other frame is read byte
+ *              by byte (same results, slower).  Frames of one group may differ.
+ *   d_labels : 2-byte aligned (it holds uint16_t); an odd address is refused with FSLIC_E_INVALID before any device work.  A map at an
+ *              8-byte-aligned address with W % 4 == 0 is written with 8-byte stores; any other map two bytes at a time (same
+ *              results, slower).  Maps of one group may differ.
+ * Exactly H*W*3 bytes are read from d_rgb and exactly H*W*2 bytes are written to d_labels: nothing before or behind them is touched. */
 int fslic_hip_iterate_device(fslic_engine* e, int slot, const fslic_params* p, int H, int W, int K,
                              const uint8_t* d_rgb, fslic_cluster* clusters, uint16_t* d_labels);
 
@@ -170,7 +178,8 @@ int fslic_hip_enforce_connectivity_nodes(fslic_engine* e, uint16_t* labels, int 
  * SlicModel.get_connectivity / get_knn_connectivity / get_mask_density / broadcast_density_to_mask,
  * cfast_slic.pyx:262-324).  `labels` (H*W uint16), `mask` (H*W uint8) and `result` (H*W uint8) may be host pointers or
  * device pointers (a label map left in HBM by fslic_hip_iterate_device needs no copy); the per-cluster arrays are host
- * arrays.  The reference returns a heap-allocated Connectivity (src/fast-slic-common.h:25-29); here the same content is
+ * arrays.  Device planes are read and written in place, one element at a time: `labels` 2-byte aligned, `mask` and `result` at any
+ * address, and no byte outside the H*W elements is touched.The reference returns a heap-allocated Connectivity (src/fast-slic-common.h:25-29); here the same content is
  * written into caller arrays: num_neighbors[K] and neighbors[K][stride] (unused entries 0). */
 
 /* fast_slic_get_connectivity(H, W, K, assignment), src/fast-slic.cpp:16-78: for every cluster its adjacent clusters
