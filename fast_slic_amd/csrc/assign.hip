@@ -3,6 +3,7 @@
 // DESIGN.md for the design.  All arithmetic on this path is integer, so results are bit-identical to the reference.
 #include "device_common.h"
 #include "forms.h"
+#include <algorithm>
 #include <type_traits>
 
 namespace fslic {
@@ -1324,179 +1325,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_wav
     assign_blk2_body<R, true, STRIDE, VT, false, true>(f, rem, Hv, bm);
 }
 
-// the launch's FrameDev with the table of the subsampled stride selected (the fused passes; the full pass reads `tab` as it is)
-static FrameDev with_subsampled_table(FrameDev f) {
-    f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad;
-    return f;
+// One row per form of the block kernel: its code (forms.h) and the kernel that runs it.  The wrapper is picked here, by rows and pass: _w6
+// for 32 rows, for the fused 16-row form and for the 16-row bin form, _w8 for the full 16-row form.  The row-vector tables take the VT
+// bodies; `tab` and `tabv16` differ in length only and share a kernel.
+struct BlkRow { uint32_t code; void (*kernel)(FrameDev, int, int, BlkMap); };
+constexpr bool row_vector(uint32_t table) { return table == kFormTabRowvec || table == kFormTabRowvec16; }
+template <int R, bool FUSE, int STRIDE, uint32_t TABLE, bool NOLAB>
+constexpr BlkRow blk_row() {
+    static_assert(R != 32 || (!FUSE && TABLE == kFormTabRowvec), "32 rows per wavefront: the full pass on the 32-row row-vector table only");
+    constexpr uint32_t code = form_code(kFormBlk, R, FUSE, STRIDE, TABLE, NOLAB);
+    if constexpr (R == 32 || (R == 16 && FUSE)) return {code, k_assign_blk2_w6<R, FUSE, STRIDE, row_vector(TABLE), NOLAB>};
+    else if constexpr (R == 16) return {code, k_assign_blk2_w8<R, FUSE, STRIDE, row_vector(TABLE), NOLAB>};
+    else return {code, k_assign_blk2<R, FUSE, STRIDE, row_vector(TABLE), NOLAB>};
 }
+template <int R, int STRIDE, uint32_t TABLE>
+constexpr BlkRow bin_row() {
+    constexpr uint32_t code = form_code(kFormBin, R, true, STRIDE, TABLE);
+    if constexpr (R == 16) return {code, k_assign_bin_w6<R, STRIDE, row_vector(TABLE)>};
+    else return {code, k_assign_bin<R, STRIDE, row_vector(TABLE)>};
+}
+template <int STRIDE, uint32_t TABLE>
+constexpr BlkRow pre_row() { return {form_code(kFormPre, 8, true, STRIDE, TABLE), k_assign_pre<8, STRIDE, row_vector(TABLE)>}; }
 
-template <int R, bool FUSE, int STRIDE, bool NOLAB = false>
-static void launch_assign_blk_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    FrameDev f = FUSE ? with_subsampled_table(f_) : f_;
-    if (FUSE && R == 16 && !f.tab_vmode) { f.tab = f.tabs16; f.tab_words = f.tabs16_words; f.tab_dyoff = f.tabs16_dyoff; f.tab_nrpad = f.tabs16_nrpad; }
-    // row-vector mode, full pass with at most 16 rows per wavefront: the shorter stride-1 table (48 entries = 768 bytes of LDS per block less)
-    if (!FUSE && R <= 16 && f.tab_vmode && f.tabv16_words > 0) { f.tab = f.tabv16; f.tab_words = f.tabv16_words; f.tab_dyoff = f.tabv16_dyoff; }
-    dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
-    const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;       // whole KB: what the LDS-DMA pieces fill
-    // (the form record, forms.h: the table is named after the buffer selected above)
-    const uint32_t table = f.tab_vmode ? (f.tab == f_.tabv16 && !FUSE ? kFormTabRowvec16 : kFormTabRowvec) : (FUSE && R == 16 ? kFormTab2d16 : kFormTab2d);
-    note_form(form_code(kFormBlk, R, FUSE, STRIDE, table, NOLAB));
-    if constexpr (R == 32) {
-        static_assert(!FUSE, "32 rows per wavefront: full pass only");
-        launch((k_assign_blk2_w6<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    } else if constexpr (R == 16 && !FUSE) {
-        if (f.tab_vmode) launch((k_assign_blk2_w8<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2_w8<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    } else if constexpr (R == 16 && FUSE) {
-        if (f.tab_vmode) launch((k_assign_blk2_w6<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2_w6<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    } else {
-        if (f.tab_vmode) launch((k_assign_blk2<R, FUSE, STRIDE, true, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_blk2<R, FUSE, STRIDE, false, NOLAB>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    }
-}
-
-template <int R, int STRIDE>
-static void launch_assign_bin_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    const FrameDev f = with_subsampled_table(f_);
-    dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
-    const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
-    note_form(form_code(kFormBin, R, true, STRIDE, R == 16 ? kFormTabRowvec : R == 4 ? kFormTab2d : f.tab_vmode ? kFormTabRowvec : kFormTab2d));
-    if constexpr (R == 16) {
-        launch((k_assign_bin_w6<R, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    } else if constexpr (R == 4) {
-        launch((k_assign_bin<R, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));      // (2-D table only)
-    } else {
-        if (f.tab_vmode) launch((k_assign_bin<R, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-        else launch((k_assign_bin<R, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    }
-}
-
-template <int STRIDE>
-static void launch_assign_pre_t(const FrameDev& f_, int nframes, int rem, int Hv, hipStream_t st) {
-    const FrameDev f = with_subsampled_table(f_);
-    dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * 8 - 1) / (kWavesPerBlock * 8), nframes);
-    const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;
-    note_form(form_code(kFormPre, 8, true, STRIDE, f.tab_vmode ? kFormTabRowvec : kFormTab2d));
-    if (f.tab_vmode) launch((k_assign_pre<8, STRIDE, true>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-    else launch((k_assign_pre<8, STRIDE, false>), blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
-}
-bool blk_kernel_applies(const FrameDev& f, int stride) {
-    return f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull;
-}
-
-// preemptive mode: the fused pass of the block kernel on the bins of the active clusters (see assign_blk2_body, PRE); false: the
-// geometry does not take the block kernel (the caller uses the generic kernel)
-bool launch_assign_pre(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, hipStream_t st) {
-    const FrameDev f = rotated(f_, buf, sbuf);
-    const int Hv = visited_rows(f.H, rem, stride);
-    if (!blk_kernel_applies(f, stride)) return false;
-    if (Hv <= 0) return true;
-    if (stride == 1) launch_assign_pre_t<1>(f, nframes, rem, Hv, st);
-    else if (stride == 2) launch_assign_pre_t<2>(f, nframes, rem, Hv, st);
-    else launch_assign_pre_t<3>(f, nframes, rem, Hv, st);
-    return true;
-}
-
-void launch_assign_fused_bin(const FrameDev& f_, int nframes, int rem, int stride, int it, hipStream_t st) {
-    const FrameDev f = rotated(f_, it & 1, it & 1, it % 3);
-    const int Hv = visited_rows(f.H, rem, stride);
-    if (Hv <= 0) return;
-    const int blocks8 = assign_blocks8(f.W, Hv, nframes);
-    const bool r16 = f.tab_vmode && blocks8 > 3072;      // as launch_assign
-    // Launches that leave most of the chip idle even with 8-row wavefronts (one or two 1280x720 frames: 160 blocks each on 256
-    // CUs): 4 rows per wavefront.  A wavefront alone on its SIMD issues a dependent instruction every 8 - 10 clocks, so a
-    // block's life there is its instruction chain; half the rows halve the argmin, label and sum phases of that chain.
-    const bool r4 = !f.tab_vmode && stride == 3 && blocks8 <= 384;      // (measured: one 1280x720 frame per group 179.5 -> 175.7 us, profiles/r04_assign_experiments.txt)
-    if (r4) {
-        launch_assign_bin_t<4, 3>(f, nframes, rem, Hv, st);
-    } else if (r16) {
-        if (stride == 1) launch_assign_bin_t<16, 1>(f, nframes, rem, Hv, st);
-        else if (stride == 2) launch_assign_bin_t<16, 2>(f, nframes, rem, Hv, st);
-        else launch_assign_bin_t<16, 3>(f, nframes, rem, Hv, st);
-    } else {
-        if (stride == 1) launch_assign_bin_t<8, 1>(f, nframes, rem, Hv, st);
-        else if (stride == 2) launch_assign_bin_t<8, 2>(f, nframes, rem, Hv, st);
-        else launch_assign_bin_t<8, 3>(f, nframes, rem, Hv, st);
-    }
-}
-
-static int assign_rows_per_wave(const FrameDev& f, int nframes, int Hv, bool fuse_update) {
-    const int blocks8 = assign_blocks8(f.W, Hv, nframes);
-    // 32 rows (row-vector table only): launches that keep the chip busy for three rounds of 16-row blocks and more -- the block
-    // prologue and the per-candidate fetch are then paid once per 8192 pixels instead of 4096
-    if (!fuse_update && f.tab_vmode && f.tab_rows32 && blocks8 > 4 * 6144) return 32;
-    return (!fuse_update && blocks8 > 3072) ? 16 : 8;
-}
-
-// the 32-bit kernel; 16 rows per wavefront exist for the full pass only (assign_rows_per_wave), so FUSED with R = 16 does not compile
-template <int R, bool FUSED>
-static void launch_assign_r(const FrameDev& f, int nframes, int rem, int stride, int Hv, int buf, int sbuf, hipStream_t st) {
-    static_assert(R == 8 || !FUSED, "k_assign with 16 rows per wavefront: the full pass only");
-    dim3 grid((f.W + kTileW - 1) / kTileW, (Hv + kWavesPerBlock * R - 1) / (kWavesPerBlock * R), nframes);
-    const size_t lds = (size_t)f.lut_words * sizeof(uint32_t);
-    note_form(form_code(kFormK32, R, FUSED, 0, f.lut_words > 0 ? kFormTabLut : kFormTabNone));
-    if (f.lut_words > 0) launch((k_assign<R, FUSED, true>), grid, dim3(256), lds, st, f, rem, stride, Hv, buf, sbuf);
-    else launch((k_assign<R, FUSED, false>), grid, dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
-}
-
-// the fused pass of the block kernel, R rows per wavefront, storing or label-free
-template <int R>
-static void launch_assign_fused_t(const FrameDev& f, int nframes, int rem, int stride, int Hv, bool label_free, hipStream_t st) {
-    if (label_free) {
-        if (stride == 1) launch_assign_blk_t<R, true, 1, true>(f, nframes, rem, Hv, st);
-        else if (stride == 2) launch_assign_blk_t<R, true, 2, true>(f, nframes, rem, Hv, st);
-        else launch_assign_blk_t<R, true, 3, true>(f, nframes, rem, Hv, st);
-    } else {
-        if (stride == 1) launch_assign_blk_t<R, true, 1>(f, nframes, rem, Hv, st);
-        else if (stride == 2) launch_assign_blk_t<R, true, 2>(f, nframes, rem, Hv, st);
-        else launch_assign_blk_t<R, true, 3>(f, nframes, rem, Hv, st);
-    }
-}
-
-PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf, bool label_free) {
-    const FrameDev f = rotated(f_, buf, sbuf, obuf);
-    const int Hv = visited_rows(f.H, rem, stride);
-    PassGeom pg;
-    pg.rem = rem; pg.stride = stride; pg.Hv = Hv; pg.BH = kWavesPerBlock * 8; pg.use_slots = 0;
-    if (Hv <= 0) return pg;
-    if (blk_kernel_applies(f, stride)) {       // block-level packed kernel
-        if (!fuse_update && stride == 1) {
-            const int rpw = assign_rows_per_wave(f, nframes, Hv, false);
-            if (label_free) {      // the full pass that closes a label-free group
-                if (rpw == 32) launch_assign_blk_t<32, false, 1, true>(f, nframes, rem, Hv, st);
-                else if (rpw == 16) launch_assign_blk_t<16, false, 1, true>(f, nframes, rem, Hv, st);
-                else launch_assign_blk_t<8, false, 1, true>(f, nframes, rem, Hv, st);
-                return pg;
-            }
-            if (rpw == 32) launch_assign_blk_t<32, false, 1>(f, nframes, rem, Hv, st);
-            else if (rpw == 16) launch_assign_blk_t<16, false, 1>(f, nframes, rem, Hv, st);
-            else launch_assign_blk_t<8, false, 1>(f, nframes, rem, Hv, st);
-            return pg;
-        }
-        if (fuse_update) {
-            pg.use_slots = 1;
-            // Launches of many blocks (3840x2160 frames in groups) with the row-vector table: 16 rows per wavefront, i.e. 64
-            // visited rows per block -- the block prologue (candidate list, table) is paid once per 4096 pixels instead of
-            // 2048.  Small launches keep 8 rows (more, shorter-lived blocks fill the chip better); so does the 2-D table,
-            // whose LDS footprint grows with the rows a wavefront spans.
-            const int fblocks8 = assign_blocks8(f.W, Hv, nframes);
-            // (2-D table: 16 rows from 2048 eight-row blocks on -- the launch then is one round of blocks instead of one and a bit)
-            const bool r16 = (f.tab_vmode && fblocks8 > 3072) || (!f.tab_vmode && f.tabs16_words > 0 && fblocks8 > 2048);
-            if (r16) {
-                pg.BH = kWavesPerBlock * 16;
-                launch_assign_fused_t<16>(f, nframes, rem, stride, Hv, label_free, st);
-                return pg;
-            }
-            launch_assign_fused_t<8>(f, nframes, rem, stride, Hv, label_free, st);
-            return pg;
-        }
-    }
-    if (fuse_update) launch_assign_r<8, true>(f, nframes, rem, stride, Hv, buf, sbuf, st);
-    else if (assign_rows_per_wave(f, nframes, Hv, false) >= 16) launch_assign_r<16, false>(f, nframes, rem, stride, Hv, buf, sbuf, st);
-    else launch_assign_r<8, false>(f, nframes, rem, stride, Hv, buf, sbuf, st);
-    return pg;
-}
+constexpr uint32_t kRv = kFormTabRowvec, kRv16 = kFormTabRowvec16, k2d = kFormTab2d, k2d16 = kFormTab2d16;
+constexpr BlkRow kBlkRows[] = {
+    // the full pass (stride 1): storing, then closing a label-free group
+    blk_row<8, false, 1, kRv, false>(), blk_row<8, false, 1, kRv16, false>(), blk_row<8, false, 1, k2d, false>(),
+    blk_row<16, false, 1, kRv, false>(), blk_row<16, false, 1, kRv16, false>(), blk_row<16, false, 1, k2d, false>(), blk_row<32, false, 1, kRv, false>(),
+    blk_row<8, false, 1, kRv, true>(), blk_row<8, false, 1, kRv16, true>(), blk_row<8, false, 1, k2d, true>(),
+    blk_row<16, false, 1, kRv, true>(), blk_row<16, false, 1, kRv16, true>(), blk_row<16, false, 1, k2d, true>(), blk_row<32, false, 1, kRv, true>(),
+    // the fused pass: storing (a frame redone, a slot under the sticky fallback), then label-free
+    blk_row<8, true, 1, kRv, false>(), blk_row<8, true, 2, kRv, false>(), blk_row<8, true, 3, kRv, false>(),
+    blk_row<8, true, 1, k2d, false>(), blk_row<8, true, 2, k2d, false>(), blk_row<8, true, 3, k2d, false>(),
+    blk_row<16, true, 1, kRv, false>(), blk_row<16, true, 2, kRv, false>(), blk_row<16, true, 3, kRv, false>(),
+    blk_row<16, true, 1, k2d16, false>(), blk_row<16, true, 2, k2d16, false>(), blk_row<16, true, 3, k2d16, false>(),
+    blk_row<8, true, 1, kRv, true>(), blk_row<8, true, 2, kRv, true>(), blk_row<8, true, 3, kRv, true>(),
+    blk_row<8, true, 1, k2d, true>(), blk_row<8, true, 2, k2d, true>(), blk_row<8, true, 3, k2d, true>(),
+    blk_row<16, true, 1, kRv, true>(), blk_row<16, true, 2, kRv, true>(), blk_row<16, true, 3, kRv, true>(),
+    blk_row<16, true, 1, k2d16, true>(), blk_row<16, true, 2, k2d16, true>(), blk_row<16, true, 3, k2d16, true>(),
+    // the cluster pass fused in
+    bin_row<4, 3, k2d>(), bin_row<8, 1, kRv>(), bin_row<8, 2, kRv>(), bin_row<8, 3, kRv>(), bin_row<8, 1, k2d>(), bin_row<8, 2, k2d>(), bin_row<8, 3, k2d>(),
+    bin_row<16, 1, kRv>(), bin_row<16, 2, kRv>(), bin_row<16, 3, kRv>(),
+    // preemptive mode
+    pre_row<1, kRv>(), pre_row<2, kRv>(), pre_row<3, kRv>(), pre_row<1, k2d>(), pre_row<2, k2d>(), pre_row<3, k2d>(),
+};
 
 // ---------------------------------------------------------------------------------------------
 // Generic gather: one thread per visited pixel, candidates read straight from the coarse cells,
@@ -1558,48 +1430,134 @@ __global__ __launch_bounds__(256) void k_assign_generic_rec(FrameDev f, int rem,
     assign_generic_body<true, true>(f, rem, stride, Hv, dist);
 }
 
+// The forms whose stride is a run-time argument (the 32-bit kernel, the generic kernel) and the recording form
+struct RunRow { uint32_t code; void (*kernel)(FrameDev, int, int, int, int, int); };
+struct RecRow { uint32_t code; void (*kernel)(FrameDev, int, int, int, uint16_t*); };
+template <int R, bool FUSE, bool LUT>
+constexpr RunRow k32_row() { return {form_code(kFormK32, R, FUSE, 0, LUT ? kFormTabLut : kFormTabNone), k_assign<R, FUSE, LUT>}; }
+template <bool FUSE>
+constexpr RunRow generic_row() { return {form_code(kFormGeneric, 0, FUSE, 0, kFormTabNone), k_assign_generic<FUSE>}; }
+constexpr RunRow kRunRows[] = {
+    k32_row<8, true, true>(), k32_row<8, true, false>(), k32_row<8, false, true>(), k32_row<8, false, false>(), k32_row<16, false, true>(), k32_row<16, false, false>(),
+    generic_row<true>(), generic_row<false>(),
+};
+constexpr RecRow kRecRows[] = {{form_code(kFormGenericRec, 0, true, 0, kFormTabNone), k_assign_generic_rec}};
+
+int assign_forms(uint32_t* codes, int cap) {
+    constexpr int nb = sizeof(kBlkRows) / sizeof(kBlkRows[0]), nr = sizeof(kRunRows) / sizeof(kRunRows[0]);
+    row_codes(kBlkRows, codes, cap);
+    row_codes(kRunRows, codes + std::min(nb, cap), std::max(cap - nb, 0));
+    return nb + nr + row_codes(kRecRows, codes + std::min(nb + nr, cap), std::max(cap - nb - nr, 0));
+}
+
+// Listed equals producible.  Over the whole domain of choose_form -- every flag, strides 0 .. 4, every launch size at each threshold and
+// one beyond it, every entry -- each code it returns has a row (so find_row in the launch functions below cannot come back empty), and
+// each row's code is returned for some input.  One set per (entry, stride): an evaluation stays far below the compiler's step limit.
+struct FormSet {
+    uint32_t codes[32] = {};
+    int n = 0;
+    bool all_listed = true;
+    constexpr bool has(uint32_t code) const {
+        for (int i = 0; i < n; i++)
+            if (codes[i] == code) return true;
+        return false;
+    }
+};
+constexpr FormSet producible(int entry, int stride) {
+    FormSet s;
+    for (unsigned bits = 0; bits < 128u; bits++)
+        for (int size : {kBlocksBinRows4, kBlocksFuseBin, kBlocksRows16Tab2d, kBlocksRows16, kBlocksRows32})
+            for (int beyond = 0; beyond < 2; beyond++) {
+                const uint32_t code = choose_form({entry, (bits & 1u) != 0, (bits & 2u) != 0, (bits & 4u) != 0, (bits & 8u) != 0, (bits & 16u) != 0,
+                                                   (bits & 32u) != 0, stride, (bits & 64u) != 0, size + beyond});
+                if (code == kFormNone || s.has(code)) continue;
+                s.all_listed = s.all_listed && (find_row(kBlkRows, code) || find_row(kRunRows, code) || find_row(kRecRows, code));
+                s.codes[s.n++] = code;
+            }
+    return s;
+}
+template <int I> constexpr FormSet kProducible = producible(I / 5, I % 5);
+using FormDomain = std::make_integer_sequence<int, kFormEntries * 5>;
+template <int... I> constexpr bool all_listed(std::integer_sequence<int, I...>) { return (kProducible<I>.all_listed && ...); }
+template <int... I> constexpr bool produced(uint32_t code, std::integer_sequence<int, I...>) { return (kProducible<I>.has(code) || ...); }
+template <class Row, size_t N> constexpr bool all_produced(const Row (&rows)[N]) {
+    for (const Row& r : rows)
+        if (!produced(r.code, FormDomain{})) return false;
+    return true;
+}
+static_assert(all_listed(FormDomain{}), "choose_form returns a code that has no row");
+static_assert(all_produced(kBlkRows) && all_produced(kRunRows) && all_produced(kRecRows), "a row that no input of choose_form reaches");
+
+bool blk_kernel_applies(const FrameDev& f, int stride) {
+    return f.tab_words > 0 && stride >= 1 && stride <= 3 && (unsigned long long)f.N * 4ull < 0x7FFFFFFFull;
+}
+static uint32_t choose(int entry, const FrameDev& f, int nframes, int Hv, int stride, bool label_free = false) {
+    return choose_form({entry, blk_kernel_applies(f, stride), f.tab_vmode != 0, f.tab_rows32 != 0, f.tabs16_words > 0, f.tabv16_words > 0,
+                        f.lut_words > 0, stride, label_free, assign_blocks8(f.W, Hv, nframes)});
+}
+// the grid of a tiled form: kTileW columns x the form's rows per block x frames
+static dim3 tile_grid_of(uint32_t code, const FrameDev& f, int nframes, int Hv) {
+    const int bh = kWavesPerBlock * form_rows(code);
+    return dim3((f.W + kTileW - 1) / kTileW, (Hv + bh - 1) / bh, nframes);
+}
+// the packed table the form reads into FrameDev::tab (`tab` itself serves the full pass as it is)
+static void select_table(FrameDev& f, uint32_t code) {
+    if (form_table(code) == kFormTabRowvec16) { f.tab = f.tabv16; f.tab_words = f.tabv16_words; f.tab_dyoff = f.tabv16_dyoff; }
+    else if (form_table(code) == kFormTab2d16) { f.tab = f.tabs16; f.tab_words = f.tabs16_words; f.tab_dyoff = f.tabs16_dyoff; f.tab_nrpad = f.tabs16_nrpad; }
+    else if (form_fused(code)) { f.tab = f.tabs; f.tab_words = f.tabs_words; f.tab_dyoff = f.tabs_dyoff; f.tab_nrpad = f.tabs_nrpad; }
+}
+static void launch_blk_form(uint32_t code, FrameDev f, int nframes, int rem, int Hv, hipStream_t st) {
+    note_form(code);
+    select_table(f, code);
+    const dim3 grid = tile_grid_of(code, f, nframes, Hv);
+    const size_t lds2 = ((size_t)f.tab_words * sizeof(uint32_t) + 1023) / 1024 * 1024;       // whole KB: what the LDS-DMA pieces fill
+    launch(find_row(kBlkRows, code)->kernel, blk_grid(grid), dim3(256), lds2, st, f, rem, Hv, blk_map(grid));
+}
+
+// preemptive mode: the fused pass of the block kernel on the bins of the active clusters (see assign_blk2_body, PRE); false: the
+// geometry does not take the block kernel (the caller uses the generic kernel)
+bool launch_assign_pre(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, hipStream_t st) {
+    const FrameDev f = rotated(f_, buf, sbuf);
+    const int Hv = visited_rows(f.H, rem, stride);
+    const uint32_t code = choose(kEntryPre, f, nframes, Hv, stride);
+    if (code == kFormNone) return false;
+    if (Hv > 0) launch_blk_form(code, f, nframes, rem, Hv, st);
+    return true;
+}
+
+void launch_assign_fused_bin(const FrameDev& f_, int nframes, int rem, int stride, int it, hipStream_t st) {
+    const FrameDev f = rotated(f_, it & 1, it & 1, it % 3);
+    const int Hv = visited_rows(f.H, rem, stride);
+    if (Hv > 0) launch_blk_form(choose(kEntryFusedBin, f, nframes, Hv, stride), f, nframes, rem, Hv, st);
+}
+
+PassGeom launch_assign(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, int obuf, bool label_free) {
+    const FrameDev f = rotated(f_, buf, sbuf, obuf);
+    const int Hv = visited_rows(f.H, rem, stride);
+    PassGeom pg;
+    pg.rem = rem; pg.stride = stride; pg.Hv = Hv; pg.BH = kWavesPerBlock * 8; pg.use_slots = 0;
+    if (Hv <= 0) return pg;
+    const uint32_t code = choose(fuse_update ? kEntryFused : kEntryFull, f, nframes, Hv, stride, label_free);
+    if (form_family(code) == kFormBlk) {       // block-level packed kernel; its fused pass leaves the sums per block (FrameDev::cpart)
+        if (form_fused(code)) { pg.use_slots = 1; pg.BH = kWavesPerBlock * form_rows(code); }
+        launch_blk_form(code, f, nframes, rem, Hv, st);
+    } else {                                   // the 32-bit kernel
+        note_form(code);
+        launch(find_row(kRunRows, code)->kernel, tile_grid_of(code, f, nframes, Hv), dim3(256), (size_t)f.lut_words * sizeof(uint32_t), st, f, rem, stride, Hv, buf, sbuf);
+    }
+    return pg;
+}
+
 void launch_assign_generic(const FrameDev& f_, int nframes, int rem, int stride, int buf, int sbuf, bool fuse_update, hipStream_t st, uint16_t* rec_dist) {
     const FrameDev f = rotated(f_, buf, sbuf);
     const int Hv = visited_rows(f.H, rem, stride);
     if (Hv <= 0) return;
     const size_t n = (size_t)Hv * f.W;
     const int blocks = (int)((n + 255) / 256);
-    note_form(rec_dist ? form_code(kFormGenericRec, 0, true, 0, kFormTabNone) : form_code(kFormGeneric, 0, fuse_update, 0, kFormTabNone));
-    if (rec_dist) launch(k_assign_generic_rec, dim3(blocks, 1), dim3(256), 0, st, f, rem, stride, Hv, rec_dist);
-    else if (fuse_update) launch(k_assign_generic<true>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
-    else launch(k_assign_generic<false>, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
+    const uint32_t code = choose(rec_dist ? kEntryGenericRec : fuse_update ? kEntryGenericFused : kEntryGenericFull, f, nframes, Hv, stride);
+    note_form(code);
+    if (rec_dist) launch(find_row(kRecRows, code)->kernel, dim3(blocks, 1), dim3(256), 0, st, f, rem, stride, Hv, rec_dist);
+    else launch(find_row(kRunRows, code)->kernel, dim3(blocks, nframes), dim3(256), 0, st, f, rem, stride, Hv, buf, sbuf);
 }
-
-// Every code the launch functions above can note, one line per launch function and mode: an instantiation added there is added here
-// (tests/test_gpu_assign_forms.py compares the codes its cases recorded with this list, and tests/test_assign_forms_cpu.py its shape).
-// Not listed because they do not exist: k_assign<16, true, *> (16 rows are the full pass's, launch_assign_r refuses to compile it), the 32-row form on anything but the 32-row row-vector table (assign_rows_per_wave asks for tab_rows32).
-namespace {
-constexpr uint32_t B(int rows, bool fused, int stride, uint32_t table, bool nolab) { return form_code(kFormBlk, rows, fused, stride, table, nolab); }
-constexpr uint32_t N(int rows, int stride, uint32_t table) { return form_code(kFormBin, rows, true, stride, table); }
-constexpr uint32_t kRv = kFormTabRowvec, kRv16 = kFormTabRowvec16, k2d = kFormTab2d, k2d16 = kFormTab2d16;
-const uint32_t kAssignForms[] = {
-    // launch_assign_blk_t, full pass (stride 1): storing, then closing a label-free group
-    B(8, false, 1, kRv, false), B(8, false, 1, kRv16, false), B(8, false, 1, k2d, false),
-    B(16, false, 1, kRv, false), B(16, false, 1, kRv16, false), B(16, false, 1, k2d, false), B(32, false, 1, kRv, false),
-    B(8, false, 1, kRv, true), B(8, false, 1, kRv16, true), B(8, false, 1, k2d, true),
-    B(16, false, 1, kRv, true), B(16, false, 1, kRv16, true), B(16, false, 1, k2d, true), B(32, false, 1, kRv, true),
-    // launch_assign_blk_t, fused pass: storing (a frame redone, a slot under the sticky fallback), then label-free
-    B(8, true, 1, kRv, false), B(8, true, 2, kRv, false), B(8, true, 3, kRv, false), B(8, true, 1, k2d, false), B(8, true, 2, k2d, false), B(8, true, 3, k2d, false),
-    B(16, true, 1, kRv, false), B(16, true, 2, kRv, false), B(16, true, 3, kRv, false), B(16, true, 1, k2d16, false), B(16, true, 2, k2d16, false), B(16, true, 3, k2d16, false),
-    B(8, true, 1, kRv, true), B(8, true, 2, kRv, true), B(8, true, 3, kRv, true), B(8, true, 1, k2d, true), B(8, true, 2, k2d, true), B(8, true, 3, k2d, true),
-    B(16, true, 1, kRv, true), B(16, true, 2, kRv, true), B(16, true, 3, kRv, true), B(16, true, 1, k2d16, true), B(16, true, 2, k2d16, true), B(16, true, 3, k2d16, true),
-    // launch_assign_bin_t (the cluster pass fused in)
-    N(4, 3, k2d), N(8, 1, kRv), N(8, 2, kRv), N(8, 3, kRv), N(8, 1, k2d), N(8, 2, k2d), N(8, 3, k2d), N(16, 1, kRv), N(16, 2, kRv), N(16, 3, kRv),
-    // launch_assign_pre_t (preemptive mode)
-    form_code(kFormPre, 8, true, 1, kRv), form_code(kFormPre, 8, true, 2, kRv), form_code(kFormPre, 8, true, 3, kRv),
-    form_code(kFormPre, 8, true, 1, k2d), form_code(kFormPre, 8, true, 2, k2d), form_code(kFormPre, 8, true, 3, k2d),
-    // launch_assign_r (the 32-bit kernel; the stride is a run-time argument)
-    form_code(kFormK32, 8, true, 0, kFormTabLut), form_code(kFormK32, 8, true, 0, kFormTabNone), form_code(kFormK32, 8, false, 0, kFormTabLut),
-    form_code(kFormK32, 8, false, 0, kFormTabNone), form_code(kFormK32, 16, false, 0, kFormTabLut), form_code(kFormK32, 16, false, 0, kFormTabNone),
-    // launch_assign_generic
-    form_code(kFormGeneric, 0, true, 0, kFormTabNone), form_code(kFormGeneric, 0, false, 0, kFormTabNone), form_code(kFormGenericRec, 0, true, 0, kFormTabNone),
-};
-}  // namespace
-const uint32_t* assign_forms(int* n) { *n = (int)(sizeof(kAssignForms) / sizeof(kAssignForms[0])); return kAssignForms; }
 
 }  // namespace fslic

@@ -333,11 +333,8 @@ int fslic_hip_debug_forms_seen(uint32_t* codes, int cap, int clear) {
 
 int fslic_hip_debug_forms_all(uint32_t* codes, int cap) {
     if (cap < 0 || (cap > 0 && !codes)) return -1;
-    int na = 0, np = 0;
-    const uint32_t* a = fslic::assign_forms(&na);
-    const uint32_t* p = fslic::preempt_forms(&np);
-    for (int i = 0; i < na + np && i < cap; i++) codes[i] = i < na ? a[i] : p[i - na];
-    return na + np;
+    const int na = fslic::assign_forms(codes, cap);
+    return na + fslic::preempt_forms(codes + std::min(na, cap), std::max(cap - na, 0));
 }
 
 // ---- SimpleCRF (src/simple-crf.{h,hpp,cpp}): host state and bookkeeping here, inference in crf.hip --------------------------------

@@ -47,37 +47,6 @@ static __device__ __forceinline__ uint32_t lds_ld(uint32_t* p) {
 static __device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// find with path halving.  The halving store races with concurrent atomicMin hooks, which is safe:
-// it only ever replaces a parent by one of its ancestors (cf. ECL-CC style concurrent union-find).
-static __device__ __forceinline__ uint32_t lds_find(uint32_t* par, uint32_t x) {
-    for (;;) {
-        const uint32_t p = lds_ld(par + x);
-        if (p == x) return x;
-        const uint32_t gp = lds_ld(par + p);
-        if (gp == p) return p;
-        lds_st(par + x, gp);
-        x = gp;
-    }
-}
-static __device__ __forceinline__ void lds_union(uint32_t* par, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = lds_find(par, a);
-        b = lds_find(par, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(par + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// read-only find (no halving stores), unrolled for the flatten pass
-static __device__ __forceinline__ uint32_t lds_find_ro(uint32_t* par, uint32_t x) {
-    uint32_t p = lds_ld(par + x);
-    while (p != x) { x = p; p = lds_ld(par + x); }
-    return x;
-}
-
 // ---- wavefront-mask helpers of the tile kernel.  A lane predicate that every lane computes from ONE comparison is a 64-bit mask in
 // scalar registers (v_cmp writes it), mask logic is scalar-ALU work, and a mask becomes a lane predicate again at no cost
 // (inverse ballot: the mask is the condition register).  Written with bools the same logic goes through the vector ALU: a
@@ -426,34 +395,13 @@ static __device__ __forceinline__ uint32_t node_of(const CcaDev& c, uint32_t p) 
     const int y = (int)(p / (uint32_t)c.W);
     return node_at(c, y, (int)(p - (uint32_t)y * (uint32_t)c.W), p);
 }
-static __device__ __forceinline__ uint32_t g_find(const CcaDev& c, uint32_t x) {
-    for (;;) {
-        const uint32_t p = g_load(n_parent(c, x));
-        if (p == x) return x;
-        const uint32_t gp = g_load(n_parent(c, p));
-        if (gp == p) return p;
-        __hip_atomic_store(n_parent(c, x), gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-}
-// The root whose leader (first pixel in raster order) is larger goes under the other: the root of a finished component is
-// the node that holds the component's leader, which is what src/cca.h:36-57 ends up with.  A node's leader never changes.
-static __device__ __forceinline__ void g_union(const CcaDev& c, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = g_find(c, a);
-        b = g_find(c, b);
-        if (a == b) return;
-        if (n_leader(c, a) < n_leader(c, b)) { const uint32_t t = a; a = b; b = t; }
-        if (atomicCAS(n_parent(c, a), a, b) == a) return;
-    }
-}
-
 // (parent, leader) of a node with ONE 8-byte load: a node's leader never changes, its parent only through the 32-bit CAS below
 static __device__ __forceinline__ uint2 g_load2(const CcaDev& c, uint32_t n) {
     const unsigned long long v = __hip_atomic_load(reinterpret_cast<unsigned long long*>(c.nrec + n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
 }
-// x -> its root (path halving as in g_find), returns the root's leader
+// x -> its root, returns the root's leader.  Find with path halving: the halving store races with concurrent CAS hooks, which is safe: it
+// only ever replaces a parent by one of its ancestors (cf. ECL-CC style concurrent union-find).
 static __device__ __forceinline__ uint32_t g_find_leader(const CcaDev& c, uint32_t& x, uint2 r) {      // r = g_load2(x), already fetched
     for (;;) {
         if (r.x == x) return r.y;
@@ -464,7 +412,9 @@ static __device__ __forceinline__ uint32_t g_find_leader(const CcaDev& c, uint32
         r = g_load2(c, x);
     }
 }
-// g_union with the two first look-ups in flight together and the leaders arriving with the parents: a contact between two nodes
+// Union of two nodes' components.  The root whose leader (first pixel in raster order) is larger goes under the other: the root of a
+// finished component is the node that holds the component's leader, which is what src/cca.h:36-57 ends up with.  A node's leader never
+// changes.  The two first look-ups are in flight together and the leaders arrive with the parents: a contact between two nodes
 // that are still roots (the rule: every node is, when this pass starts) costs one round trip for both records and one for the CAS
 static __device__ __forceinline__ void g_union2(const CcaDev& c, uint32_t a, uint32_t b) {
     uint2 ra = g_load2(c, a), rb = g_load2(c, b);

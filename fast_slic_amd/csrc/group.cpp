@@ -3,6 +3,7 @@
 // (src/context.cpp:108-197) enqueued operation by operation or replayed as one hipGraph, completion, the rare host
 // steps, and the write-back of the Cluster[K] blocks.  Part of the host engine, see engine_internal.h.
 #include "engine_internal.h"
+#include "forms.h"
 
 #include <time.h>
 
@@ -219,7 +220,7 @@ static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, 
     const bool fuse_wanted = false;
     (void)assign_blocks;
 #else
-    const bool fuse_wanted = knobs().fuse_bin == 2 || (knobs().fuse_bin == 1 && assign_blocks <= 640);
+    const bool fuse_wanted = knobs().fuse_bin == 2 || (knobs().fuse_bin == 1 && assign_blocks <= kBlocksFuseBin);
 #endif
     const bool plain_slic = p.variant == FSLIC_VARIANT_SLIC && p.preemptive == 0;
     // (H < stride: the passes of the residues >= H visit no row at all and launch nothing -- src/context.cpp:158-175 still runs update()

@@ -181,32 +181,26 @@ __global__ __launch_bounds__(1024) void k_preempt_update(FrameDev f, int rebin_a
     }
 }
 
+// The two forms (forms.h): per-cell lists in LDS (K <= 8192 and <= 4096 cells), and all pairs
+struct PreemptRow { uint32_t code; void (*kernel)(FrameDev, int, float); };
+constexpr PreemptRow kPreemptRows[] = {
+    {form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, false), k_preempt_update<true>},
+    {form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true), k_preempt_update<false>},
+};
+int preempt_forms(uint32_t* codes, int cap) { return row_codes(kPreemptRows, codes, cap); }
+
 void launch_preempt_update(const FrameDev& f_, int nframes, int buf, int sbuf, bool rebin_all, float l1_thres, hipStream_t st) {
     const FrameDev f = rotated(f_, buf, sbuf);
     const int ncell2 = f.pre_cw * f.pre_ch;
-    if (f.K <= 8192 && ncell2 <= 4096) {
-        const size_t lds = ((size_t)f.K + 2 * (size_t)ncell2 + 1) * 4 + (size_t)f.K * 2 + 16;
-        // the attribute belongs to the device that is current when it is set: once per DEVICE (launch.h), and a device on which it could
-        // not be set takes the all-pairs kernel instead of failing the launch
-        constexpr int kMaxLds = (8192 + 2 * 4096 + 1) * 4 + 8192 * 2 + 16;
-        static std::atomic<int> attr_state[64];
-        if (!max_dynamic_lds_on_this_device(k_preempt_update<true>, kMaxLds, attr_state) && lds > 64 * 1024) {
-            note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true));
-            launch(k_preempt_update<false>, dim3(nframes), dim3(1024), 0, st, f, rebin_all ? 1 : 0, l1_thres);
-            return;
-        }
-        note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, false));
-        launch(k_preempt_update<true>, dim3(nframes), dim3(1024), lds, st, f, rebin_all ? 1 : 0, l1_thres);
-    } else {
-        note_form(form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true));
-        launch(k_preempt_update<false>, dim3(nframes), dim3(1024), 0, st, f, rebin_all ? 1 : 0, l1_thres);
-    }
+    const size_t lds = ((size_t)f.K + 2 * (size_t)ncell2 + 1) * 4 + (size_t)f.K * 2 + 16;
+    // the attribute belongs to the device that is current when it is set: once per DEVICE (launch.h), and a device on which it could
+    // not be set takes the all-pairs kernel instead of failing the launch
+    constexpr int kMaxLds = (8192 + 2 * 4096 + 1) * 4 + 8192 * 2 + 16;
+    static std::atomic<int> attr_state[64];
+    const bool lists = f.K <= 8192 && ncell2 <= 4096 && (max_dynamic_lds_on_this_device(kPreemptRows[0].kernel, kMaxLds, attr_state) || lds <= 64 * 1024);
+    const PreemptRow& row = kPreemptRows[lists ? 0 : 1];
+    note_form(row.code);
+    launch(row.kernel, dim3(nframes), dim3(1024), lists ? lds : 0, st, f, rebin_all ? 1 : 0, l1_thres);
 }
-
-// the codes launch_preempt_update can note: the per-cell-list form (K <= 8192 and <= 4096 cells) and the all-pairs form (forms.h)
-static const uint32_t kPreemptForms[] = {
-    form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, false), form_code(kFormPreemptUpdate, 0, false, 0, kFormTabNone, false, true),
-};
-const uint32_t* preempt_forms(int* n) { *n = 2; return kPreemptForms; }
 
 }  // namespace fslic

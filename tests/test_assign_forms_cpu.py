@@ -39,3 +39,13 @@ def test_complete_list_has_no_duplicates_and_decodes_to_distinct_names():
     assert "blk r16 fused s2 rowvec nolab" in names and "preempt_update allpairs" in names and "k32 r8 fused srt lut lab" in names
     # every family of the dispatch appears
     assert {x.split()[0] for x in names} == set(B.FORM_FAMILIES.values())
+
+
+def test_the_set_of_forms_is_the_pinned_one():
+    """tests/golden/assign_forms.txt: the names of forms_all() as the library listed them before the forms became rows of one table
+    (csrc/assign.hip, csrc/preempt.hip).  A row lost or added is a form lost or added."""
+    pinned = open(os.path.join(ROOT, "tests", "golden", "assign_forms.txt")).read().split("\n")
+    pinned = [x for x in pinned if x]
+    assert len(pinned) == len(set(pinned)) == 65
+    names = set(B.forms_all())
+    assert names == set(pinned), (sorted(names - set(pinned)), sorted(set(pinned) - names))

@@ -132,8 +132,8 @@ def test_config4_all_64_frames():
 def test_one_group_of_eight_4k_frames():
     B.forms_seen(clear=True)
     _run_pipeline(2160, 3840, 1600, list(range(8)), 8, 2, 5)
-    # 8 x 3840x2160 is the one operating point whose full pass is large enough for 32 rows per wavefront (assign.hip,
-    # assign_rows_per_wave): read from the library's record, label-free or -- with the cluster pass fused in, FSLIC_FUSEBIN=2 -- storing
+    # 8 x 3840x2160 is the one operating point whose full pass is large enough for 32 rows per wavefront (forms.h,
+    # choose_form): read from the library's record, label-free or -- with the cluster pass fused in, FSLIC_FUSEBIN=2 -- storing
     forms = B.forms_seen()
     assert any(f.startswith("blk r32 full s1 rowvec") for f in forms), sorted(forms)
 
