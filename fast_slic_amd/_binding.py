@@ -44,7 +44,7 @@ EXPORTS = [
     "fslic_hip_last_device_times", "fslic_hip_set_launch_timing", "fslic_hip_last_assign_loop", "fslic_hip_last_group_frames", "fslic_hip_last_path", "fslic_hip_last_launch_mode", "fslic_hip_group_done", "fslic_hip_last_error", "fslic_hip_version",
     "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
     "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
-    "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
+    "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_overlapped_groups", "fslic_hip_pipeline_overlap", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
     "fslic_hip_debug_lsc_state", "fslic_hip_debug_forms_seen", "fslic_hip_debug_forms_all",
     # SimpleCRF (fast_slic_amd/crf.py)
     "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
@@ -176,6 +176,10 @@ def load_library():
         lib.fslic_hip_separate_pass_redos.argtypes = [vp, i32]
         if hasattr(lib, "fslic_hip_uncovered_redos"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it: it has no label-free passes)
             lib.fslic_hip_uncovered_redos.argtypes = [vp, i32]
+        if hasattr(lib, "fslic_hip_overlapped_groups"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it: its slot threads finish every group before the next)
+            lib.fslic_hip_overlapped_groups.argtypes = [vp]
+            lib.fslic_hip_overlapped_groups.restype = C.c_longlong
+            lib.fslic_hip_pipeline_overlap.argtypes = [vp, i32]
         if hasattr(lib, "fslic_hip_copy_bandwidth"):      # (an A/B build of an earlier round, FSLIC_LIB, may lack it)
             lib.fslic_hip_copy_bandwidth.argtypes = [vp, C.c_size_t, i32, C.POINTER(C.c_double)]
         lib.fslic_hip_group_done.argtypes = [vp, i32]
@@ -471,6 +475,18 @@ class Engine(object):
             return 0
         slots = range(self.n_slots) if slot is None else [int(slot)]
         return sum(int(lib.fslic_hip_uncovered_redos(self._h, s)) for s in slots)
+
+    def overlapped_groups(self):
+        """Groups of the submit / drain pipeline (since the engine was created) that a slot thread began while the slot's previous group
+        had not been collected yet (include/fslic_hip.h)."""
+        lib = load_library()
+        if not hasattr(lib, "fslic_hip_overlapped_groups"):      # (FSLIC_LIB: a build with the serial loop only)
+            return 0
+        return int(lib.fslic_hip_overlapped_groups(self._h))
+
+    def pipeline_overlap(self, on):
+        """False: the slot threads finish every group before they begin the next one (the serial loop); True is the default."""
+        _check(load_library().fslic_hip_pipeline_overlap(self._h, int(bool(on))))
 
     def copy_bandwidth(self, nbytes=1 << 30, reps=5):
         """Measured HBM rate of this GPU in GB/s: bytes read + written per second of a plain streaming copy of `nbytes`."""

@@ -12,7 +12,7 @@ void free_slot(Slot& s) {
     // the slot's host thread has been stopped by the caller (stop_slot_thread)
     for (auto& g : s.graphs) { if (g.exec) hipGraphExecDestroy(g.exec); if (g.graph) hipGraphDestroy(g.graph); }
     s.graphs.clear();
-    for (auto& e : s.ev) if (e) hipEventDestroy(e);
+    for (auto& ps : s.set) for (auto& e : ps.ev) if (e) hipEventDestroy(e);
     for (auto& e : s.ev_it) if (e) hipEventDestroy(e);
     if (s.st) hipStreamDestroy(s.st);
     s = Slot();                      // the buffers go with the old value
@@ -28,8 +28,9 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     if (G < s.cap_frames && s.keyH == H && s.keyW == W && s.keyK == K) G = s.cap_frames;
 
     int rc;
-    if ((rc = s.h_cl.reserve((size_t)G * 4 * K)) || (rc = s.h_misc.reserve((size_t)kStatusWords * kMaxGroup)) ||
-        (rc = s.h_lut.reserve(kLutMaxWords)) || (rc = s.h_tab.reserve(3 * kTabMaxBytes / sizeof(uint16_t))) ||
+    for (PinnedSet& ps : s.set)
+        if ((rc = ps.h_cl.reserve((size_t)G * 4 * K)) || (rc = ps.h_misc.reserve((size_t)kStatusWords * kMaxGroup))) return rc;
+    if ((rc = s.h_lut.reserve(kLutMaxWords)) || (rc = s.h_tab.reserve(3 * kTabMaxBytes / sizeof(uint16_t))) ||
         (rc = s.h_patchf.reserve(P * P)) || (rc = s.h_patch.reserve(P * P)))
         return rc;
 
@@ -136,11 +137,16 @@ int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
     return FSLIC_OK;
 }
 
-int ensure_prepared(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
+bool prepared_for(const fslic_engine* e, const Slot& s, int H, int W, int K, int G) {
     // room for the groups batching will form later (fslic_hip_pipeline_batching): applied HERE, so that every caller --
     // including the host-memory entry points, which stage frames into the arena before group_begin runs -- carves once
     G = std::max(G, std::min(e->reserve_frames.load(), (int)kMaxGroup));
-    if (s.keyH == H && s.keyW == W && s.keyK == K && s.cap_frames >= G) return FSLIC_OK;
+    return s.keyH == H && s.keyW == W && s.keyK == K && s.cap_frames >= G;
+}
+
+int ensure_prepared(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G) {
+    if (prepared_for(e, s, H, W, K, G)) return FSLIC_OK;
+    G = std::max(G, std::min(e->reserve_frames.load(), (int)kMaxGroup));
     HIPCHK(hipStreamSynchronize(s.st));
     return prepare(e, s, H, W, K, S, G);
 }

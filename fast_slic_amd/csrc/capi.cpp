@@ -41,11 +41,11 @@ int fslic_hip_create(int device, int n_slots, fslic_engine** out) {
     e->slots.resize(n_slots);
     for (auto& s : e->slots) {
         if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipStreamCreate failed"); }
-        for (auto& ev : s.ev)
+        for (auto& ps : s.set) for (auto& ev : ps.ev)
             if (hipEventCreate(&ev) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipEventCreate failed"); }
         for (auto& ev : s.ev_it)
             if (hipEventCreate(&ev) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipEventCreate failed"); }
-        if (s.d_ptrs.reserve(2 * kMaxGroup) || s.h_ptrs.reserve(2 * kMaxGroup) ||
+        if (s.d_ptrs.reserve(kPtrTable) || s.set[0].h_ptrs.reserve(kPtrTable) || s.set[1].h_ptrs.reserve(kPtrTable) ||
             s.d_gen.reserve(64) || hipMemset(s.d_gen, 0, 256) != hipSuccess) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "pointer table allocation failed"); }
     }
     if (e->d_gamma.reserve(sizeof ht.gamma / sizeof ht.gamma[0]) || e->d_labtbl.reserve(sizeof ht.lab / sizeof ht.lab[0])) { fslic_hip_destroy(e); return fail(FSLIC_E_HIP, "hipMalloc(tables) failed"); }
@@ -286,6 +286,14 @@ int fslic_hip_lab_force_generic(fslic_engine* e, int on) {
     return FSLIC_OK;
 }
 
+int fslic_hip_debug_fail_group(fslic_engine* e, int what, int after) {
+    if (!e || what < -1 || what > 2 || after < 0) return fail(FSLIC_E_INVALID, "bad arguments");
+    e->debug_fail_what.store(-1);
+    e->debug_fail_after.store(after);
+    e->debug_fail_what.store(what);
+    return FSLIC_OK;
+}
+
 int fslic_hip_last_assign_loop(fslic_engine* e, int slot, float* sum_ms, double* visited_px, int* launches) {
     if (!e || slot < 0 || slot >= (int)e->slots.size()) return fail(FSLIC_E_INVALID, "bad engine/slot");
     const Slot& s = e->slots[slot];
@@ -323,6 +331,11 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot) {
 int fslic_hip_uncovered_redos(fslic_engine* e, int slot) {
     if (!e || slot < 0 || slot >= (int)e->slots.size()) return -1;
     return __atomic_load_n(&e->slots[slot].n_uncovered_redo, __ATOMIC_RELAXED);
+}
+
+long long fslic_hip_overlapped_groups(fslic_engine* e) {
+    if (!e) return -1;
+    return e->overlapped_groups.load(std::memory_order_relaxed);
 }
 
 // ---- the form record (forms.h; the record itself is in host_utils.cpp) ----

@@ -1208,11 +1208,11 @@ __global__ __launch_bounds__(256) void k_cca_relabel(CcaDev c, ExportDev ex, int
         const size_t d = (size_t)z * ex.frame_bytes;
         const uint32_t* yx = ex.yx_cur; const uint32_t* rest = ex.lab_n_moved; const uint32_t* misc = ex.misc0;
         FrameDev::adv(yx, d); FrameDev::adv(rest, d); FrameDev::adv(misc, d);
-        uint32_t* out = ex.h_cl + (size_t)z * ex.h_stride;
+        uint32_t* out = ex.tab[0] + ex.h_off + (size_t)z * ex.h_stride;
         const int K = ex.K;
         for (int i = ((int)blockIdx.x - relabel_blocks) * blockDim.x + threadIdx.x; i < 4 * K; i += ((int)gridDim.x - relabel_blocks) * blockDim.x)
             out[i] = i < K ? yx[i] : rest[i - K];              // [0,K) positions, [K,4K) colour, member count, moved flag
-        if ((int)blockIdx.x == relabel_blocks && threadIdx.x < kStatusWords) ex.h_misc[kStatusWords * (size_t)z + threadIdx.x] = misc[threadIdx.x];
+        if ((int)blockIdx.x == relabel_blocks && threadIdx.x < kStatusWords) ex.tab[1][ex.misc_off + kStatusWords * (size_t)z + threadIdx.x] = misc[threadIdx.x];
         return;
     }
     c.select(z);

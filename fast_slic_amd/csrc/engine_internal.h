@@ -125,9 +125,43 @@ struct HostTables {
 };
 const HostTables& host_tables();
 
+// The device pointer table of a group (Slot::d_ptrs, copied per group by upload_ptrs): the callers' frame buffers, then the pinned blocks
+// of the group's set -- where its first kernel finds the staged centres and its last kernel puts the cluster state and the status words.
+constexpr int kPtrStage = 2 * kMaxGroup, kPtrExport = kPtrStage + 1, kPtrStatus = kPtrStage + 2, kPtrTable = kPtrStage + 3;
+
+// What a group owns on the host from its begin to its finish, twice per slot: while group N of a slot is still running, the slot's thread
+// stages and enqueues N + 1 on the other set (pipeline.cpp).  Nothing recorded in a graph names a set: the kernels take the blocks from
+// the pointer table.
+struct PinnedSet {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // 0..4 bracket the phases (4: the group's end), 5: nap_wait's
+    // pinned host (device-accessible: the first kernel reads the centres from it, the export blocks of the last kernel write the
+    // results into it -- no copy commands in a group's launch sequence)
+    Pinned<uint32_t> h_cl;           // per frame 4K words: in [0,K) yx; out (yx, lab, n, moved)
+    Pinned<uint32_t> h_misc;         // per frame its status words as the export left them: status(s, frame)
+    Pinned<void*> h_ptrs;            // the source of the pointer table's asynchronous copy
+};
+
+// A group between group_begin and its completion: everything the finish needs, so that the slot's per-call state may already be that
+// of the next group.
+struct InFlight {
+    GroupJob job;                    // geometry, parameters, frames, the callers' buffers and Cluster[K] blocks
+    int S = 0;
+    int par = 0;                     // its PinnedSet
+    bool generic = false;
+    int launch_mode = 0;             // Slot::last_launch_mode of its begin
+    double t_begun_us = 0;           // when group_begin returned (nap_wait's history counts from here)
+    // what its finish found, for whoever collects it (the slot's own fields of the same names belong to the group finished LAST)
+    float total_ms = 0;
+    int n_host_topk = 0;
+};
+
 struct Slot {
     hipStream_t st = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinnedSet set[2];
+    int par = 0;                     // the set of the current (last begun) group; group_begin takes the other one
+    InFlight fl[2];                  // by set
+    PinnedSet& pin() { return set[par]; }
+    const PinnedSet& pin() const { return set[par]; }
     // HIP events bracketing every subsampled assign launch of the loop (the roofline figure of bench.py sums them)
     static constexpr int kMaxTimedIters = 16;
     hipEvent_t ev_it[2 * kMaxTimedIters] = {};
@@ -152,18 +186,13 @@ struct Slot {
     int32_t* d_keep_leader = nullptr;
     uint16_t* d_keep_label = nullptr;
     // per-frame caller pointers of the current group: [0, kMaxGroup) inputs, [kMaxGroup, 2*kMaxGroup) outputs
-    Device<void*> d_ptrs;            // device copy (allocated with the slot)
-    Pinned<void*> h_ptrs;            // pinned staging
+    Device<void*> d_ptrs;            // device copy, kPtrTable entries (allocated with the slot; pinned staging: PinnedSet::h_ptrs)
     // shared tables
     uint16_t* d_patch = nullptr;
     uint32_t* d_lut = nullptr;
     Pinned<uint32_t> h_lut;
     uint16_t* d_tab = nullptr;
     Pinned<uint16_t> h_tab;
-    // pinned host (device-accessible: the first cluster pass reads the centres from it, the export kernel writes the
-    // results into it -- no copy commands in a group's launch sequence)
-    Pinned<uint32_t> h_cl;           // per frame 4K words: in [0,K) yx; out (yx, lab, n, moved)
-    Pinned<uint32_t> h_misc;         // per frame its status words as the export left them: status(s, frame)
     Pinned<uint16_t> h_patch;
     Pinned<int32_t> h_cand_leader;   // the host top-K step's candidates (cca_finish_group)
     Pinned<uint32_t> h_cand_area;
@@ -188,7 +217,7 @@ struct Slot {
     double t_begun_us = 0;           // FSLIC_HOST_TIMING: when group_begin returned
     // the slot's own host thread waits for a group by sleeping and polling instead of spinning (group.cpp, nap_wait)
     bool nap_wait = false;           // set for groups served by the slot thread
-    double recent_wait_us[4] = {1e30, 1e30, 1e30, 1e30};   // its last four waits (1e30: none yet)
+    double recent_wait_us[4] = {1e30, 1e30, 1e30, 1e30};   // its last four flights: group_begin's return to completion (1e30: none yet)
     unsigned recent_wait_i = 0;
     unsigned long long recent_wait_key = 0;   // the workload those waits belong to (geometry, group size, iterations, variant): another one starts a new history
     // per-call state
@@ -257,8 +286,9 @@ struct Slot {
     template <class T> T* at(T* p, int frame) const { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + (size_t)frame * frame_bytes); }
 };
 
-// the status words of frame `frame` of the slot's last group (host copy)
-inline uint32_t* status(const Slot& s, int frame) { return s.h_misc + (size_t)kStatusWords * frame; }
+// the status words of frame `frame` of the slot's current group, or of the group that owns set `par` (host copy)
+inline uint32_t* status(const Slot& s, int frame) { return s.pin().h_misc + (size_t)kStatusWords * frame; }
+inline uint32_t* status(const Slot& s, int par, int frame) { return s.set[par].h_misc + (size_t)kStatusWords * frame; }
 
 // Where the reference leaves a cluster after an update (src/context.cpp:368-380): one that has moved (an update with members) at its
 // integer centre `yx` (y << 16 | x) or, for 'noq', at its float centroid (y, x; NULL otherwise); one that has not at the caller's
@@ -298,12 +328,21 @@ struct fslic_engine {
     double pipe_last_submit_us = 0;  // (mu) when the last submission arrived: a companion is only waited for while submissions are arriving
     std::atomic<int> reserve_frames{0};   // arenas are carved for at least this many frames per group
     int sync_waiters = 0;                    // (mu) synchronous callers waiting for ANY slot (or all of them): the slot threads leave the submit queue alone meanwhile
-    std::atomic<int> lab_force_generic{0};   // testing aid (fslic_hip_lab_force_generic): the brute-force gather kernels instead of the tiled ones
+    std::atomic<bool> pipe_overlap{true};          // fslic_hip_pipeline_overlap: off, the slot threads finish every group before they begin the next one (the serial loop)
+    std::atomic<long long> overlapped_groups{0};   // groups begun while their slot's previous group had not been collected (fslic_hip_overlapped_groups)
+    std::atomic<int> lab_force_generic{0};
+    // testing aid (fslic_hip_debug_fail_group): the slot threads' groups pass point `debug_fail_what` (-1: none) `debug_fail_after` more times, then one fails there
+    std::atomic<int> debug_fail_what{-1}, debug_fail_after{0};   // testing aid (fslic_hip_lab_force_generic): the brute-force gather kernels instead of the tiled ones
 };
 
 // Testing aid, exported but deliberately NOT part of include/fslic_hip.h: every following group of the Slic variant on this engine
 // runs the brute-force gather kernel (k_assign_generic) instead of the tiled one -- the tests' independent cross-check.
 extern "C" int fslic_hip_lab_force_generic(fslic_engine* e, int on);
+// Testing aid, exported and NOT part of include/fslic_hip.h either: after `after` more groups of the slot threads have passed the point
+// `what`, the next one fails there with FSLIC_E_INTERNAL, once.  0: group_begin before it touches the slot; 1: group_begin after the group
+// has been enqueued (its kernels run; the slot's current set is the failed group's); 2: group_complete before the host steps and the
+// write-back.  Nothing on the device goes wrong: the error paths of the submit / drain pipeline run without a fault.  -1: disarm.
+extern "C" int fslic_hip_debug_fail_group(fslic_engine* e, int what, int after);
 
 namespace fslic {
 
@@ -315,6 +354,8 @@ int configure_patchf(Slot& s, int S, const fslic_params* p);
 void free_slot(Slot& s);
 int prepare(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G);
 int ensure_prepared(fslic_engine* e, Slot& s, int H, int W, int K, int S, int G);
+// whether ensure_prepared would leave the slot's buffers as they are
+bool prepared_for(const fslic_engine* e, const Slot& s, int H, int W, int K, int G);
 int prepare_lsc(Slot& s, int H, int W, int K, int S, int G, float compactness);
 
 // ---- group.cpp ----
@@ -331,6 +372,16 @@ int cca_finish_group(Slot& s, int first, int n, const uint16_t* d_in0, size_t in
 // record: the recording path of debug_mode (one frame; only fslic_hip_iterate / fslic_hip_iterate_device ask for it)
 int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record = false);
 int group_finish(fslic_engine* e, Slot& s);
+// The halves of group_finish, for a slot thread that has already begun the group's successor (pipeline.cpp).  group_wait: the group's
+// completion and its event times; with `successor` it waits for the group's own end event and leaves the stream alone.
+// group_needs_host: a frame came back with a kernel flag or for the host's top-K step.  group_complete: those host steps, then the
+// write-back of the Cluster[K] blocks; `from_scratch`: the device state of the group is gone (a successor has run over it), the frames
+// concerned are computed again first.  The host steps need the group to be the slot's current one (make_current) and the stream idle.
+int group_wait(Slot& s, InFlight& g, bool successor);
+bool group_prewait(Slot& s, const InFlight& g, int& rc);      // (group.cpp: when a slot thread looks for a successor)
+bool group_needs_host(const Slot& s, const InFlight& g);
+int make_current(Slot& s, const InFlight& g);
+int group_complete(fslic_engine* e, Slot& s, InFlight& g, bool from_scratch);
 // After a failure on the slot's stream: waits until nothing touches the caller's buffers any more; the error message survives.
 void drain_failed(Slot& s);
 // One group from start to completion: group_begin, group_finish, and drain_failed if either fails.

@@ -105,13 +105,17 @@ CcaDev cca_view(const Slot& s, int i0, const uint16_t* d_in0, size_t in_stride, 
     return c;
 }
 
-// Caller's per-frame buffers of the group -> device pointer arrays.
+// Caller's per-frame buffers of the group, and the pinned blocks of the slot's current set -> device pointer table.
 int upload_ptrs(Slot& s, int n, const uint8_t* const* d_rgb, uint16_t* const* d_out) {
+    PinnedSet& ps = s.pin();
     for (int i = 0; i < kMaxGroup; i++) {
-        s.h_ptrs[i] = (i < n && d_rgb) ? const_cast<uint8_t*>(d_rgb[i]) : nullptr;
-        s.h_ptrs[kMaxGroup + i] = (i < n && d_out) ? d_out[i] : nullptr;
+        ps.h_ptrs[i] = (i < n && d_rgb) ? const_cast<uint8_t*>(d_rgb[i]) : nullptr;
+        ps.h_ptrs[kMaxGroup + i] = (i < n && d_out) ? d_out[i] : nullptr;
     }
-    HIPCHK(hipMemcpyAsync(s.d_ptrs, s.h_ptrs, sizeof(void*) * 2 * kMaxGroup, hipMemcpyHostToDevice, s.st));
+    ps.h_ptrs[kPtrStage] = ps.h_cl.get();
+    ps.h_ptrs[kPtrExport] = ps.h_cl.get();
+    ps.h_ptrs[kPtrStatus] = ps.h_misc.get();
+    HIPCHK(hipMemcpyAsync(s.d_ptrs, ps.h_ptrs, sizeof(void*) * kPtrTable, hipMemcpyHostToDevice, s.st));
     return FSLIC_OK;
 }
 
@@ -180,7 +184,7 @@ void stage_group(fslic_engine* e, Slot& s, int i0, int n, bool timed) {
     const int H = s.H, W = s.W, K = s.K;
     for (int z = 0; z < n; z++) {
         const fslic_cluster* cl = s.clusters[i0 + z];
-        uint32_t* h = s.h_cl + (size_t)(i0 + z) * 4 * K;
+        uint32_t* h = s.pin().h_cl + (size_t)(i0 + z) * 4 * K;
         for (int k = 0; k < K; k++) {
             const int y = clampi((int)cl[k].y, 0, H - 1), x = clampi((int)cl[k].x, 0, W - 1);
             h[k] = ((uint32_t)y << 16) | (uint32_t)x;
@@ -272,6 +276,7 @@ static RecLayout rec_layout(const Slot& s) {
 int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool timed, bool separate_cluster_pass = false, bool store_labels = false) {
     const fslic_params* p = &s.p;
     const int K = s.K, S = s.S;
+    hipEvent_t* const ev = s.pin().ev;
     FrameDev f = s.f;
     f.rgbs = nullptr;
     f.select(i0);                                  // host-side: pointers of frame i0
@@ -307,7 +312,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     }
     // sums, bin counters, flags and cl_n / cl_moved start from zero: cleared by the LAB kernel below (two memset launches less)
 
-    if (timed) HIPCHK(hipEventRecord(s.ev[0], s.st));
+    if (timed) HIPCHK(hipEventRecord(ev[0], s.st));
     // + labels <- 0xFFFF (src/context.cpp:138-145); + a fresh range of bin generation stamps for this group's passes
     f.gen_base = s.d_gen;
     // (the integer SLIC path on the block / 32-bit kernels resets the assignment plane lazily, FrameDev::fv_mod: the LAB kernel then writes
@@ -323,8 +328,9 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     // label_free_allowed) is part of the graph key.
     const bool label_free = lazy_labels && !store_labels && label_free_allowed(s) && p->max_iter >= 1 && !s.recording && blk_kernel_applies(f, p->subsample_stride);
     launch_rgb_to_lab(f, n, p->convert_to_lab, e->tables, !lazy_labels, s.st, s.gen_step,
-                      s.at(s.zero_block, i0), s.zero_bytes, f.cl_n, 2 * (size_t)K, s.h_cl + (size_t)i0 * 4 * K, 4 * (size_t)K);      // (+ the staged centres -> cl_yx)
-    if (timed) HIPCHK(hipEventRecord(s.ev[1], s.st));
+                      s.at(s.zero_block, i0), s.zero_bytes, f.cl_n, 2 * (size_t)K,
+                      reinterpret_cast<const uint32_t* const*>(s.d_ptrs + kPtrStage), (size_t)i0 * 4 * K, 4 * (size_t)K);      // (+ the staged centres -> cl_yx)
+    if (timed) HIPCHK(hipEventRecord(ev[1], s.st));
     f.gen_off = 1;
     PassGeom pg{};
     // positions: the uploaded centres are in s.f.cl_yx; every cluster pass reads one buffer and writes the other
@@ -467,7 +473,7 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
         launch_preempt_update(f, n, (p->max_iter + 1) & 1, 0, true, pre_l1_thres, s.st);
         full_buf = (p->max_iter + 1) & 1;
     }
-    if (timed) HIPCHK(hipEventRecord(s.ev[2], s.st));
+    if (timed) HIPCHK(hipEventRecord(ev[2], s.st));
     // (lazy reset: the rows of the residues no subsampled pass came to are first looked at by the full pass)
     f.fv_mod = lazy_labels && p->max_iter < stride ? stride : 0; f.fv_from = p->max_iter < stride ? std::max(p->max_iter, 0) : 0;
     // (label-free group: no pass has written the plane, EVERY row is a first visit; an uncovered pixel gets its 0xFFFF -- the plane is
@@ -480,16 +486,18 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
     else if (rd) { f.cl_yx = yx_cur; launch_rd_assign(f, s.d_patchf, rd_l2, n, 0, 1, full_buf, 0, false, s.st); }
     else if (generic) launch_assign_generic(f, n, 0, 1, full_buf, 0, false, s.st);
     else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf, label_free);      // (full_buf: the bins of all clusters; max_iter & 1 unless preemptive)
-    if (timed) HIPCHK(hipEventRecord(s.ev[3], s.st));
+    if (timed) HIPCHK(hipEventRecord(ev[3], s.st));
     const CcaDev c = cca_view(s, i0, s.f.labels, fb, K, min_size_threshold(s));
     // cluster state, overflow flag and connectivity status back to the host: the last kernel of the connectivity pass
-    // writes them into the slot's pinned blocks (three 2-D copy commands per group before: blit kernels with their own
-    // barriers).  The status words are final once the select kernel has run, the cluster state since the loop ended.
+    // writes them into the pinned blocks of the group's set, which it finds in the pointer table (three 2-D copy commands per group
+    // before: blit kernels with their own barriers).  The status words are final once the select kernel has run, the cluster state
+    // since the loop ended.
     ExportDev ex{};
     ex.frame_bytes = fb; ex.K = K; ex.yx_cur = yx_cur; ex.lab_n_moved = yx_up + K; ex.misc0 = s.at(s.d_misc, i0);
-    ex.h_cl = s.h_cl + (size_t)i0 * 4 * K; ex.h_stride = 4 * (size_t)K; ex.h_misc = status(s, i0);
+    ex.tab = reinterpret_cast<uint32_t* const*>(s.d_ptrs + kPtrExport);      // [0] kPtrExport, [1] kPtrStatus
+    ex.h_off = (size_t)i0 * 4 * K; ex.h_stride = 4 * (size_t)K; ex.misc_off = (size_t)kStatusWords * i0;
     cca_enqueue(s, c, i0, n, &ex);
-    if (timed) HIPCHK(hipEventRecord(s.ev[4], s.st));
+    if (timed) HIPCHK(hipEventRecord(ev[4], s.st));
     if (pre) HIPCHK(hipMemcpy2DAsync(s.h_upd + (size_t)i0 * K, sizeof(uint32_t) * (size_t)K, f.cl_upd, fb,
                                      sizeof(uint32_t) * (size_t)K, (size_t)n, hipMemcpyDeviceToHost, s.st));
     if (noq) HIPCHK(hipMemcpy2DAsync(s.h_clf + (size_t)i0 * 8 * K, sizeof(float) * 8 * (size_t)K, f.cl_f, fb,
@@ -528,7 +536,8 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
     std::vector<unsigned char> key;
     auto put = [&](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; key.insert(key.end(), b, b + bytes); };
     const int hdr[9] = {s.H, s.W, s.K, s.S, n, s.generic ? 1 : 0, (int)s.gen_step, s.sp_patch_uploaded ? 1 : 0, label_free_allowed(s) ? 1 : 0};
-    const void* const ptrs[9] = {s.h_cl, s.h_misc, s.d_ptrs, s.h_patch, s.d_gen, s.lsc_zero, s.d_patchf, s.h_clf, s.h_upd};   // baked into copy nodes / arguments
+    // (the pinned blocks of the group's set are not among them: the kernels read their addresses from the pointer table, one sequence serves both sets)
+    const void* const ptrs[7] = {s.d_ptrs, s.h_patch, s.d_gen, s.lsc_zero, s.d_patchf, s.h_clf, s.h_upd};   // baked into copy nodes / arguments
     put(hdr, sizeof hdr); put(ptrs, sizeof ptrs); put(&s.p, sizeof s.p); put(&s.f, sizeof s.f); put(&s.c, sizeof s.c);
     if (s.p.variant == FSLIC_VARIANT_LSC) put(&s.l, sizeof s.l);
     Slot::GraphEntry* ge = nullptr;
@@ -569,10 +578,18 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
         s.last_launch_mode = 2;
     }
     // the whole group between two real event records: total device time stays available, the per-phase split does not
-    HIPCHK(hipEventRecord(s.ev[0], s.st));
+    HIPCHK(hipEventRecord(s.pin().ev[0], s.st));
     HIPCHK(hipGraphLaunch(ge->exec, s.st));
-    HIPCHK(hipEventRecord(s.ev[4], s.st));
+    HIPCHK(hipEventRecord(s.pin().ev[4], s.st));
     return FSLIC_OK;
+}
+
+// testing aid (fslic_hip_debug_fail_group): whether this passage of point `what` by a slot thread's group is the one that fails
+static bool debug_fail_here(fslic_engine* e, const Slot& s, int what) {
+    if (!s.nap_wait || e->debug_fail_what.load(std::memory_order_relaxed) != what) return false;
+    if (e->debug_fail_after.fetch_sub(1) != 0) return false;
+    e->debug_fail_what.store(-1);
+    return true;
 }
 
 int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
@@ -584,9 +601,11 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     int rc = check_job(job, S);
     if (rc) return rc;
     if (record && n != 1) return fail(FSLIC_E_INTERNAL, "a recording group holds one frame");
+    if (debug_fail_here(e, s, 0)) return fail(FSLIC_E_INTERNAL, "testing aid: group_begin failed before it touched the slot");
     rc = ensure_prepared(e, s, H, W, K, S, n);           // (carves for at least the engine's batching reserve)
     if (rc) return rc;
     const int cap_frames = s.cap_frames;
+    s.par ^= 1;                      // the other set: the previous group may still be running on its own (a slot thread's successor)
     s.H = H; s.W = W; s.K = K; s.S = S; s.p = *p; s.nframes = n;
     // the sticky fallback of the label-free passes belongs to one work
     if (s.store_labels && !(H == s.store_H && W == s.store_W && K == s.store_K && memcmp(&s.store_p, p, sizeof(fslic_params)) == 0)) { s.store_labels = false; s.store_seen_credit = false; }
@@ -619,8 +638,12 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     stage_group(e, s, 0, n, true);
     rc = launch_group(e, s, n);
     if (rc) return rc;
+    if (debug_fail_here(e, s, 1)) return fail(FSLIC_E_INTERNAL, "testing aid: group_begin failed after it enqueued the group");
     s.have_pre = true;
     s.last_path = s.generic ? 1 : 0;
+    InFlight& g = s.fl[s.par];
+    g.job = job; g.S = S; g.par = s.par; g.generic = s.generic; g.launch_mode = s.last_launch_mode;
+    g.t_begun_us = now_us();
     if (knobs().host_timing) {
         fprintf(stderr, "[fslic host] group_begin n=%d: %.1f us | slot %d begin %.1f .. %.1f\n", n, now_us() - t_begin, (int)(&s - e->slots.data()), t_begin, now_us());
         s.t_begun_us = now_us();
@@ -628,74 +651,167 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     return FSLIC_OK;
 }
 
-// Wait for the group, serve the rare host-side steps frame by frame (candidate-list overflow -> generic redo, more
-// connectivity candidates than the device sorts -> std::partial_sort on the host), then write the cluster state back.
-// Completion of everything enqueued on the slot's stream, for a slot's OWN host thread (the submit / drain pipeline): hipStreamSynchronize
-// spins, and six slot threads spinning cost a rank 0.77 ms of CPU per 0.153 ms step (five cores; forty on an 8-GPU node).  Here the
-// thread sleeps through the first half of the wait -- half of the SHORTEST of its last four waits, so that a group that finishes
-// sooner than its predecessors (the pipeline draining) is not slept past -- and then looks at an event behind the stream's work every
-// ten microseconds (the slot threads run with a timer slack of 1 us, pipeline.cpp).  A synchronous caller's thread keeps the spin:
-// its timer slack is its own, and one frame per call is a latency measurement.
-static int nap_wait(Slot& s) {
-    const double t0 = now_us();
-    HIPCHK(hipEventRecord(s.ev[5], s.st));
-    // The history belongs to ONE workload: after a switch from long groups (16 x 4K: ~10 ms) to short ones (0.15 ms) the first short
-    // groups would otherwise sleep 5, 2.5, 1.25 .. ms before the minimum converged.
-    const unsigned long long key = ((unsigned long long)(uint32_t)s.H << 48) ^ ((unsigned long long)(uint32_t)s.W << 32) ^ ((unsigned long long)(uint32_t)s.K << 16) ^
-                                   ((unsigned long long)(uint32_t)s.nframes << 8) ^ ((unsigned long long)(uint32_t)s.p.max_iter << 4) ^ (unsigned long long)(uint32_t)s.p.variant ^
-                                   ((unsigned long long)(uint32_t)s.p.preemptive << 60) ^ ((unsigned long long)(uint32_t)s.p.subsample_stride << 56);
+// The shortest of the slot thread's last four flight times (from the return of group_begin to the group's completion) for the
+// workload of `g`; 1e30: none yet.  The history belongs to ONE workload: after a switch from long groups (16 x 4K: ~10 ms) to short ones
+// (0.15 ms) the first short groups would otherwise sleep 5, 2.5, 1.25 .. ms before the minimum converged.
+static double shortest_flight(Slot& s, const InFlight& g) {
+    const GroupJob& j = g.job;
+    const unsigned long long key = ((unsigned long long)(uint32_t)j.H << 48) ^ ((unsigned long long)(uint32_t)j.W << 32) ^ ((unsigned long long)(uint32_t)j.K << 16) ^
+                                   ((unsigned long long)(uint32_t)j.n << 8) ^ ((unsigned long long)(uint32_t)j.p.max_iter << 4) ^ (unsigned long long)(uint32_t)j.p.variant ^
+                                   ((unsigned long long)(uint32_t)j.p.preemptive << 60) ^ ((unsigned long long)(uint32_t)j.p.subsample_stride << 56);
     if (key != s.recent_wait_key) {
         s.recent_wait_key = key;
         for (double& w : s.recent_wait_us) w = 1e30;
     }
     double shortest = 1e30;
     for (double w : s.recent_wait_us) shortest = std::min(shortest, w);
+    return shortest;
+}
+
+// Sleep through the first half of the shortest flight, then look at `ev` every ten microseconds until it is complete or `deadline_us` has passed.
+static int nap_poll(const InFlight& g, hipEvent_t ev, double shortest, double deadline_us, bool& done) {
     auto nap = [](double us) { struct timespec ts; ts.tv_sec = 0; ts.tv_nsec = (long)(us * 1000.0); nanosleep(&ts, nullptr); };
-    if (shortest < 1e29 && shortest * 0.5 > 30.0) nap(std::min(shortest * 0.5, 20000.0));
+    if (shortest < 1e29 && shortest * 0.5 > 30.0) {
+        const double rest = std::min(g.t_begun_us + std::min(shortest * 0.5, 20000.0), deadline_us) - now_us();
+        if (rest > 1.0) nap(rest);
+    }
     for (;;) {
-        const hipError_t q = hipEventQuery(s.ev[5]);
-        if (q == hipSuccess) break;
+        const hipError_t q = hipEventQuery(ev);
+        done = q == hipSuccess;
+        if (done) return FSLIC_OK;
         if (q != hipErrorNotReady) return fail(FSLIC_E_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
+        if (now_us() >= deadline_us) return FSLIC_OK;
         nap(10.0);
     }
-    s.recent_wait_us[s.recent_wait_i++ & 3] = now_us() - t0;
+}
+
+// Completion of everything enqueued on the slot's stream, for a slot's OWN host thread (the submit / drain pipeline): hipStreamSynchronize
+// spins, and six slot threads spinning cost a rank 0.77 ms of CPU per 0.153 ms step (five cores; forty on an 8-GPU node).  Here the
+// thread sleeps through the first half of the wait -- half of the SHORTEST of its last four flights, so that a group that finishes
+// sooner than its predecessors (the pipeline draining) is not slept past -- and then looks at an event behind the stream's work every
+// ten microseconds (the slot threads run with a timer slack of 1 us, pipeline.cpp).  A synchronous caller's thread keeps the spin:
+// its timer slack is its own, and one frame per call is a latency measurement.
+// (`successor`: the slot's thread has already enqueued the group's successor.  The event is then the group's OWN end event: one recorded
+// at the stream's tail, or a stream synchronisation, would wait for the successor as well.)
+static int nap_wait(Slot& s, const InFlight& g, bool successor) {
+    const hipEvent_t ev = s.set[g.par].ev[successor ? 4 : 5];
+    if (!successor) HIPCHK(hipEventRecord(ev, s.st));
+    bool done = false;
+    const int rc = nap_poll(g, ev, shortest_flight(s, g), 1e300, done);
+    if (rc) return rc;
+    s.recent_wait_us[s.recent_wait_i++ & 3] = now_us() - g.t_begun_us;
     return FSLIC_OK;
 }
 
-int group_finish(fslic_engine* e, Slot& s) {
-    const double t_begin = now_us();
-    if (s.nap_wait) { const int rc = nap_wait(s); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(s.st));
-    const double t_sync = now_us();
-    const int n = s.nframes, K = s.K, H = s.H, W = s.W;
+constexpr double kOverlapMaxFlightUs = 4000.0;
+// How long before the expected end of the running group its thread looks for a successor: the host's part of a group start (~100 us)
+// with room to spare.  The same for every slot, NOT a share of the flight: streams that share a hardware queue fly twice as long as
+// those that have one to themselves, and with a proportional lead their threads looked -- and took the last submissions of a burst --
+// before the threads of the faster slots did.
+constexpr double kSuccessorLeadUs = 200.0;
+
+// For a slot thread with `g` running and nothing behind it: waits -- in nap_wait's manner, on the group's own end event -- until the group
+// is complete or only the last part of its expected flight is left, which is when the thread looks for a successor.  Committing a
+// submission to this slot's stream any earlier would take it from a slot that becomes free sooner (the end of a burst: the slots that
+// finish first take what is left, as they do without overlap); any later and the stream runs dry.  false: no history of this workload
+// yet, the group is finished without a successor.
+bool group_prewait(Slot& s, const InFlight& g, int& rc) {
+    rc = FSLIC_OK;
+    const double shortest = shortest_flight(s, g);
+    if (shortest > 1e29) return false;
+    // What a successor saves is the host's part between two groups, some 100 us.  Beside a flight of several milliseconds that is below
+    // what a measurement resolves, and two such groups queued on every stream cost more than it: 16 x 3840x2160 per group (flights of
+    // ~9 ms) ran 1 % slower with successors than without (profiles/r15_overlapped_groups.txt).  Such groups are finished one by one.
+    if (shortest > kOverlapMaxFlightUs) return false;
+    bool done = false;
+    rc = nap_poll(g, s.set[g.par].ev[4], shortest, g.t_begun_us + shortest - kSuccessorLeadUs, done);
+    return rc == FSLIC_OK;
+}
+
+int group_wait(Slot& s, InFlight& g, bool successor) {
+    PinnedSet& ps = s.set[g.par];
+    if (successor) {
+        const int rc = nap_wait(s, g, true);
+        if (rc) return rc;
+        HIPCHK(hipEventSynchronize(ps.ev[4]));      // (complete: returns at once)
+    } else {
+        if (s.nap_wait) { const int rc = nap_wait(s, g, false); if (rc) return rc; }
+        HIPCHK(hipStreamSynchronize(s.st));
+    }
     auto elapsed = [](float& ms, hipEvent_t a, hipEvent_t b) { if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { ms = 0; (void)hipGetLastError(); } };
-    elapsed(s.total_ms, s.ev[0], s.ev[4]);
-    if (s.last_launch_mode == 0) {
-        elapsed(s.lab_ms, s.ev[0], s.ev[1]);
-        elapsed(s.loop_ms, s.ev[1], s.ev[2]);
-        elapsed(s.fa_ms, s.ev[2], s.ev[3]);
-        elapsed(s.cca_ms, s.ev[3], s.ev[4]);
+    elapsed(s.total_ms, ps.ev[0], ps.ev[4]);
+    g.total_ms = s.total_ms;
+    if (g.launch_mode == 0) {
+        elapsed(s.lab_ms, ps.ev[0], ps.ev[1]);
+        elapsed(s.loop_ms, ps.ev[1], ps.ev[2]);
+        elapsed(s.fa_ms, ps.ev[2], ps.ev[3]);
+        elapsed(s.cca_ms, ps.ev[3], ps.ev[4]);
     } else {
         s.lab_ms = s.loop_ms = s.fa_ms = s.cca_ms = 0;       // graph replay: only the group total is event-timed
     }
     s.assign_loop_ms = 0;
-    for (int it = 0; it < s.n_timed_iters; it++) {
+    for (int it = 0; it < s.n_timed_iters; it++) {           // (per-launch timing: never with a successor enqueued)
         float ms = 0;
         elapsed(ms, s.ev_it[2 * it], s.ev_it[2 * it + 1]);
         s.assign_loop_ms += ms;
     }
-    const int thres = min_size_threshold(s);
+    return FSLIC_OK;
+}
+
+bool group_needs_host(const Slot& s, const InFlight& g) {
+    for (int i = 0; i < g.job.n; i++) {
+        const uint32_t* hm = status(s, g.par, i);
+        if (hm[kStSelect] == kSelectHost || (!g.generic && hm[kStFlags] != 0)) return true;
+    }
+    return false;
+}
+
+// After a successor has been finished and collected: the slot's per-call state, its current set and the device pointer table are
+// those of `g` again, so that frames of `g` can be enqueued once more (same work, same prepared buffers: what group_begin set up
+// beyond these still stands).
+int make_current(Slot& s, const InFlight& g) {
+    const GroupJob& j = g.job;
+    s.par = g.par;
+    s.H = j.H; s.W = j.W; s.K = j.K; s.S = g.S; s.p = j.p; s.nframes = j.n;
+    s.generic = g.generic; s.recording = false;
+    std::copy(j.clusters, j.clusters + j.n, s.clusters);
+    return upload_ptrs(s, j.n, j.d_rgb, j.d_out);
+}
+
+int group_complete(fslic_engine* e, Slot& s, InFlight& g, bool from_scratch) {
+    if (debug_fail_here(e, s, 2)) return fail(FSLIC_E_INTERNAL, "testing aid: group_complete failed before the write-back");
     const double t_ev = now_us();
+    const GroupJob& job = g.job;
+    const fslic_params& p = job.p;
+    const int n = job.n, K = job.K, H = job.H, W = job.W;
+    const PinnedSet& ps = s.set[g.par];
     int n_host_topk = 0;
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n; i++) n_host_topk += status(s, g.par, i)[kStSelect] == kSelectHost;
+    // The host steps work on the slot's current group (stage_group, enqueue_frames, cca_finish_group read the slot): a caller with a
+    // successor on the stream has finished that one first and made `g` current again (make_current).
+    const bool host_steps = group_needs_host(s, g);
+    if (host_steps && s.par != g.par) return fail(FSLIC_E_INTERNAL, "host steps of a group that is not the slot's current one");
+    const int thres = min_size_threshold(s);
+    for (int i = 0; host_steps && i < n; i++) {
         const uint32_t* hm = status(s, i);
-        n_host_topk += hm[kStSelect] == kSelectHost;
+        // A successor's kernels have run over the device state of this group.  A frame that only wants the host's top-K step has no
+        // candidate lists left to gather: it is computed again the way the group ran it, and takes the steps below from there.
+        if (from_scratch && hm[kStSelect] == kSelectHost && (s.generic || hm[kStFlags] == 0)) {
+            stage_group(e, s, i, 1, false);
+            s.gen_step = s.gen_span_prev;
+            s.gen_host += s.gen_step;
+            const bool separate = !cluster_pass_fused(s.f, s.p, n, W, H, s.generic, false);      // (the group's own choice, not a one-frame launch's)
+            const int rc = enqueue_frames(e, s, i, 1, s.generic, false, separate);
+            if (rc) return rc;
+            HIPCHK(hipStreamSynchronize(s.st));
+        }
         // Flags of the tiled kernels.  kFlagStalePixel: a visited pixel that no window covered kept its label while the cluster pass was
         // fused into the assign kernel (its sums reached the owner through global atomics that nothing orders before the owner's
         // finaliser): that frame alone is redone with the separate cluster pass.  kFlagListOverflow: a block's candidate list overflowed: that
         // frame alone is redone with the generic kernel.  kFlagUncoveredPixel: a pass of a label-free group met a visited pixel no window
         // covered (the one place where an earlier pass's label is needed): that frame alone is redone with storing passes, and the slot keeps
-        // to them for this work.
+        // to them for this work.  (Every redo starts from the caller's Cluster[K] block, which is written only below: it serves a group
+        // whose device state is gone just as well.)
         for (int attempt = 0; attempt < 2 && !s.generic && hm[kStFlags] != 0; attempt++) {
             const bool overflow = (hm[kStFlags] & kFlagListOverflow) != 0;
             const bool uncovered = (hm[kStFlags] & kFlagUncoveredPixel) != 0;
@@ -722,20 +838,20 @@ int group_finish(fslic_engine* e, Slot& s) {
         }
         if (!s.generic && hm[kStFlags] != 0) return fail(FSLIC_E_INTERNAL, "a redone frame still carries a kernel flag");
     }
-    {
+    if (host_steps) {
         int rc = cca_finish_group(s, 0, n, s.f.labels, s.frame_bytes, K, thres);
         if (rc) return rc;
     }
-    s.n_host_topk = n_host_topk;
+    s.n_host_topk = g.n_host_topk = n_host_topk;
     const double t_cca = now_us();
     // write the cluster state back the way the reference leaves it
-    const bool noq = s.p.variant == FSLIC_VARIANT_REALDIST_NOQ;
+    const bool noq = p.variant == FSLIC_VARIANT_REALDIST_NOQ;
     for (int i = 0; i < n; i++) {
-        const uint32_t* yx = s.h_cl + (size_t)i * 4 * K;
+        const uint32_t* yx = ps.h_cl + (size_t)i * 4 * K;
         const uint32_t* lab = yx + K;
         const uint32_t* nm = yx + 2 * (size_t)K;
         const uint32_t* moved = yx + 3 * (size_t)K;
-        fslic_cluster* cl = s.clusters[i];
+        fslic_cluster* cl = job.clusters[i];
         for (int k = 0; k < K; k++) {
             cl[k].r = (float)(lab[k] & 255u);                 // src/context.cpp:132-134 / :370-372
             cl[k].g = (float)((lab[k] >> 8) & 255u);
@@ -743,15 +859,26 @@ int group_finish(fslic_engine* e, Slot& s) {
             const float* c = noq ? s.h_clf + ((size_t)i * K + k) * 8 : nullptr;
             if (moved[k] && c) { cl[k].r = c[2]; cl[k].g = c[3]; cl[k].b = c[4]; }      // src/context.cpp:374-380
             cluster_position(moved[k] != 0, yx[k], c, cl[k], H, W, cl[k].y, cl[k].x);
-            if (s.p.max_iter > 0) cl[k].num_members = nm[k];  // src/context.cpp:362
-            cl[k].is_updatable = s.p.preemptive ? (uint8_t)s.h_upd[(size_t)i * K + k] : 2;   // src/preemptive.h:59-67, :131-139
+            if (p.max_iter > 0) cl[k].num_members = nm[k];  // src/context.cpp:362
+            cl[k].is_updatable = p.preemptive ? (uint8_t)s.h_upd[(size_t)i * K + k] : 2;   // src/preemptive.h:59-67, :131-139
             cl[k].is_active = 1;                               // src/preemptive.h:69-74
         }
     }
     if (knobs().host_timing)
-        fprintf(stderr, "[fslic host] group_finish n=%d slot %d at %.1f .. %.1f: sync wait %.1f us, events %.1f us, host top-K (%d frames) %.1f us, write-back %.1f us (device %.1f us)\n",
-                n, (int)(&s - e->slots.data()), t_begin, now_us(), t_sync - t_begin, t_ev - t_sync, n_host_topk, t_cca - t_ev, now_us() - t_cca, s.total_ms * 1e3);
+        fprintf(stderr, "[fslic host] group_complete n=%d slot %d .. %.1f: host steps (%d frames for top-K) %.1f us, write-back %.1f us (device %.1f us)\n",
+                n, (int)(&s - e->slots.data()), now_us(), n_host_topk, t_cca - t_ev, now_us() - t_cca, s.total_ms * 1e3);
     return FSLIC_OK;
+}
+
+// Wait for the slot's current group, serve the rare host-side steps frame by frame (candidate-list overflow -> generic redo, more
+// connectivity candidates than the device sorts -> std::partial_sort on the host), then write the cluster state back.
+int group_finish(fslic_engine* e, Slot& s) {
+    const double t_begin = now_us();
+    InFlight& g = s.fl[s.par];
+    int rc = group_wait(s, g, false);
+    if (rc) return rc;
+    if (knobs().host_timing) fprintf(stderr, "[fslic host] group_finish n=%d slot %d at %.1f: wait + events %.1f us\n", g.job.n, (int)(&s - e->slots.data()), t_begin, now_us() - t_begin);
+    return group_complete(e, s, g, false);
 }
 
 void drain_failed(Slot& s) {

@@ -322,12 +322,12 @@ int fslic_hip_copy_bandwidth(fslic_engine* e, size_t bytes, int reps, double* gb
     hipError_t err = hipMemsetAsync(a, 1, bytes, s.st);
     double best = 0.0;
     for (int r = 0; r <= reps && err == hipSuccess; r++) {
-        err = hipEventRecord(s.ev[0], s.st);
+        err = hipEventRecord(s.pin().ev[0], s.st);
         launch_copy16(a, b, bytes, s.st);
-        if (err == hipSuccess) err = hipEventRecord(s.ev[1], s.st);
+        if (err == hipSuccess) err = hipEventRecord(s.pin().ev[1], s.st);
         if (err == hipSuccess) err = hipStreamSynchronize(s.st);
         float ms = 0.0f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&ms, s.ev[0], s.ev[1]);
+        if (err == hipSuccess) err = hipEventElapsedTime(&ms, s.pin().ev[0], s.pin().ev[1]);
         if (r > 0 && ms > 0.0f) best = std::max(best, 2.0 * (double)bytes / ((double)ms * 1e-3) / 1e9);
     }
     if (err != hipSuccess) return fail(FSLIC_E_HIP, std::string("copy probe: ") + hipGetErrorString(err));

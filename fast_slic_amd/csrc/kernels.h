@@ -291,11 +291,12 @@ struct LabTables {
 // gen_step != 0: first kernel of a group, advances FrameDev::gen_base by gen_step (more than the group's bin passes)
 // zero_a / zero_b: optional per-frame regions (frame 0's address; zero_a_bytes a multiple of 16, zero_b_words dwords) the
 // kernel clears as well -- the accumulators, bin counters and flags a group starts from (no separate memset launches)
-// stage_yx != nullptr: the group's cluster centres as the host staged them (pinned memory, stage_stride words per frame): blocks of their own
+// stage_tab != nullptr: the group's cluster centres as the host staged them (pinned memory; *stage_tab, an entry of the group's device
+// pointer table, is the block, the group's first frame stage_off words into it, stage_stride words per frame): blocks of their own
 // copy them into FrameDev::cl_yx beside the conversion, and the first cluster pass reads device memory
 void launch_rgb_to_lab(const FrameDev& f, int nframes, int convert, const LabTables& t, bool init_labels, hipStream_t st, uint32_t gen_step = 0,
                        void* zero_a = nullptr, size_t zero_a_bytes = 0, uint32_t* zero_b = nullptr, size_t zero_b_words = 0,
-                       const uint32_t* stage_yx = nullptr, size_t stage_stride = 0);
+                       const uint32_t* const* stage_tab = nullptr, size_t stage_off = 0, size_t stage_stride = 0);
 // mode 0: resample colours at the current centres (src/context.cpp:128-135) and bin;
 // mode 1: integer centroid update from `sums` (src/context.cpp:356-373), zero sums, and bin.
 // mode 0 with src_yx != nullptr: the centres come from there (the engine's pinned staging block, read in place; frame z at
@@ -360,17 +361,18 @@ void launch_cca_phase1(const CcaDev& c, int nframes, hipStream_t st);   // local
 // device top-K + ranking, including the area tie at the cut; status word kStSelect (see k_cca_select)
 void launch_cca_select(const CcaDev& c, int nframes, hipStream_t st);
 // End of a group: what the last kernel also writes into the engine's pinned host blocks (device-accessible), so that a
-// group's launch sequence holds no copy command.  Pointers are frame 0's (frame z: + z * frame_bytes); frame z lands at
-// h_cl + z * h_stride words: [0,K) positions, [K,4K) colour / member count / moved flag; h_misc + kStatusWords * z: the status words.
+// group's launch sequence holds no copy command.  Pointers are frame 0's (frame z: + z * frame_bytes).  The pinned blocks are read
+// from the group's device pointer table (tab[0] the cluster block, tab[1] the status words: a slot has two sets of them and one
+// recorded sequence); frame z lands at tab[0] + h_off + z * h_stride words: [0,K) positions, [K,4K) colour / member count / moved
+// flag; tab[1] + misc_off + kStatusWords * z: the status words.
 struct ExportDev {
     size_t frame_bytes;
     int K;                          // 0: nothing to export
     const uint32_t* yx_cur;         // the current position buffer
     const uint32_t* lab_n_moved;    // FrameDev::cl_lab (cl_n and cl_moved follow it, K words each)
     const uint32_t* misc0;          // the frame's status words
-    uint32_t* h_cl;
-    size_t h_stride;
-    uint32_t* h_misc;
+    uint32_t* const* tab;
+    size_t h_off, h_stride, misc_off;
 };
 void launch_cca_phase2(const CcaDev& c, int nframes, hipStream_t st, const ExportDev* ex = nullptr);   // chain resolution + relabel (+ export)
 // host top-K path, one frame at a time (the CcaDev passed in is already advanced to that frame)

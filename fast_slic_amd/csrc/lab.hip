@@ -53,7 +53,7 @@ template <bool CONVERT>
 __global__ __launch_bounds__(1024) void k_rgb_to_lab(FrameDev f, const uint16_t* __restrict__ g_gamma,
                                                      const uint16_t* __restrict__ g_labtbl, LabConst kc, int init_labels, uint32_t gen_step,
                                                      char* zero_a, unsigned zero_a_quads, uint32_t* zero_b, unsigned zero_b_words,
-                                                     const uint32_t* __restrict__ stage_yx, size_t stage_stride, int stage_K, int conv_blocks) {
+                                                     const uint32_t* const* __restrict__ stage_tab, size_t stage_off, size_t stage_stride, int stage_K, int conv_blocks) {
     __shared__ uint32_t s_gamma32[CONVERT ? 256 * 32 : 1];      // 32 copies of the gamma table, one per LDS bank (see lab_px): 32 KB
     __shared__ uint16_t s_lab[8194];
     // first kernel of a group: new generation of bin stamps (nothing in this kernel reads them; the stream orders the rest)
@@ -61,8 +61,9 @@ __global__ __launch_bounds__(1024) void k_rgb_to_lab(FrameDev f, const uint16_t*
     f.select(blockIdx.y);
     if ((int)blockIdx.x >= conv_blocks) {
         // blocks behind the conversion's: the group's cluster centres from where the host staged them (pinned memory) into device memory
-        // -- the read over the bus (~2 us) runs beside the conversion instead of at the head of the first cluster pass
-        const uint32_t* src = stage_yx + (size_t)blockIdx.y * stage_stride;
+        // -- the read over the bus (~2 us) runs beside the conversion instead of at the head of the first cluster pass.  The block's address
+        // comes from the group's pointer table (this group's pinned set: the launch arguments are the same for either set)
+        const uint32_t* src = *stage_tab + stage_off + (size_t)blockIdx.y * stage_stride;
         for (int i = ((int)blockIdx.x - conv_blocks) * (int)blockDim.x + (int)threadIdx.x; i < stage_K; i += ((int)gridDim.x - conv_blocks) * (int)blockDim.x)
             f.cl_yx[i] = src[i];
         return;
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(1024) void k_rgb_to_lab(FrameDev f, const uint16_t*
 }
 
 void launch_rgb_to_lab(const FrameDev& f, int nframes, int convert, const LabTables& t, bool init_labels, hipStream_t st, uint32_t gen_step,
-                       void* zero_a, size_t zero_a_bytes, uint32_t* zero_b, size_t zero_b_words, const uint32_t* stage_yx, size_t stage_stride) {
+                       void* zero_a, size_t zero_a_bytes, uint32_t* zero_b, size_t zero_b_words, const uint32_t* const* stage_tab, size_t stage_off, size_t stage_stride) {
     LabConst kc;
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++)
@@ -163,13 +164,13 @@ void launch_rgb_to_lab(const FrameDev& f, int nframes, int convert, const LabTab
     const int cap = (512 + nframes - 1) / nframes;   // about two resident blocks per CU over the whole group, grid-stride
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
-    const int stage_blocks = stage_yx ? (f.K + 1023) / 1024 : 0;      // the centres' prefetch (see the kernel)
+    const int stage_blocks = stage_tab ? (f.K + 1023) / 1024 : 0;      // the centres' prefetch (see the kernel)
     if (convert)
         launch(k_rgb_to_lab<true>, dim3(blocks + stage_blocks, nframes), dim3(1024), 0, st, f, t.gamma, t.labtbl, kc, init_labels ? 1 : 0, gen_step, (char*)zero_a, (unsigned)(zero_a_bytes / 16), zero_b, (unsigned)zero_b_words,
-               stage_yx, stage_stride, f.K, blocks);
+               stage_tab, stage_off, stage_stride, f.K, blocks);
     else
         launch(k_rgb_to_lab<false>, dim3(blocks + stage_blocks, nframes), dim3(1024), 0, st, f, t.gamma, t.labtbl, kc, init_labels ? 1 : 0, gen_step, (char*)zero_a, (unsigned)(zero_a_bytes / 16), zero_b, (unsigned)zero_b_words,
-               stage_yx, stage_stride, f.K, blocks);
+               stage_tab, stage_off, stage_stride, f.K, blocks);
 }
 
 }  // namespace fslic

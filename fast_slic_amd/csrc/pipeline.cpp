@@ -134,41 +134,107 @@ void release_all_slots(fslic_engine* e) {
     e->cv.notify_all(); e->cv_work.notify_all();
 }
 
-// ---- the slot's host thread: one group at a time, begin + finish ---------------------------------------------------
+// ---- the slot's host thread: begin the next group, then finish the previous one ---------------------------------------
+//
+// A group taken from the submit queue is begun (staged, enqueued) and left running; the thread comes back for it after it has looked at
+// the queue once more, towards the end of the group's expected flight.  If the queue's head asks for the same work and the slot's
+// buffers serve it as they are, the head is begun on the slot's other pinned set BEHIND the running group -- the stream never runs dry
+// between the two -- and only then is the running group waited for (its own end event), written back and collected.  Otherwise the
+// running group is finished at once, exactly as a serial begin + finish.  Never more than two groups of a slot are uncollected.
+// (DESIGN.md "Overlapped groups".)
 namespace {
 
-// caller holds e->mu: fold a completed pipeline group into the engine's totals and free its slot
-void pipeline_collect(fslic_engine* e, Slot& s) {
+// caller holds e->mu: fold a completed pipeline group into the engine's totals; the slot is free once none of its groups is left
+// (g: the group's record; NULL for a group whose begin failed -- no device time, no host step)
+void pipeline_collect(fslic_engine* e, Slot& s, const InFlight* g, int rc, const std::string& err, int frames, bool last_of_slot) {
     Slot::Async& a = *s.async;
-    if (a.rc != FSLIC_OK && e->pipe_rc == FSLIC_OK) { e->pipe_rc = a.rc; e->pipe_err = a.err; }
-    e->pipe_device_ms += s.total_ms;
+    if (rc != FSLIC_OK && e->pipe_rc == FSLIC_OK) { e->pipe_rc = rc; e->pipe_err = err; }
+    e->pipe_device_ms += g ? g->total_ms : 0.0f;
     e->pipe_groups += 1;
-    e->pipe_frames += s.nframes;
-    e->pipe_host_topk += s.n_host_topk;
-    s.pending = false;
+    e->pipe_frames += frames;
+    e->pipe_host_topk += g ? g->n_host_topk : 0;
+    e->pipe_inflight--;
+    if (last_of_slot) {
+        a.rc = rc; a.err = err;
+        a.done = true;
+        a.from_queue = false;
+        s.pending = false;
+    }
 }
 
 bool same_work(const GroupJob& a, const GroupJob& b) {
     return a.H == b.H && a.W == b.W && a.K == b.K && memcmp(&a.p, &b.p, sizeof(fslic_params)) == 0;
 }
 
+// caller holds e->mu: whether the submission `head` may be begun on slot `s` while `prev` is still running there.  The same work on
+// buffers that stay as they are (nothing is re-carved or re-uploaded under the running group), no per-launch timing and no recording
+// (their events and ring exist once), not the variants whose staging blocks exist once (h_upd, h_clf) -- and nobody else to take it:
+// a submission that an idle slot could start now is not queued behind a running group.
+bool may_follow(const fslic_engine* e, const Slot& s, const InFlight& prev, const GroupJob& head) {
+    if (!e->pipe_overlap.load(std::memory_order_relaxed) || e->launch_timing || s.launch_timing) return false;
+    if (!same_work(prev.job, head) || head.p.debug_mode || head.p.preemptive || head.p.variant == FSLIC_VARIANT_REALDIST_NOQ) return false;
+    if (!prepared_for(e, s, head.H, head.W, head.K, head.n)) return false;
+    for (const Slot& o : e->slots)
+        if (!o.pending && !o.busy && o.wanted == 0) return false;
+    return true;
+}
+
 void slot_worker(fslic_engine* e, Slot* s) {
     Slot::Async& a = *s->async;
     (void)hipSetDevice(e->device);
     (void)prctl(PR_SET_TIMERSLACK, 1000UL);      // this thread's 10 us naps (group.cpp, nap_wait) are not rounded up to the default 50 us slack
+    InFlight* prev = nullptr;                    // the group from the queue that this thread has begun and not yet finished
+    // one group of the queue's, complete on the device or failed: reported and counted
+    auto collect = [&](const InFlight* g, int rc, int frames, bool last_of_slot) {
+        {
+            std::lock_guard<std::mutex> lk(e->mu);
+            pipeline_collect(e, *s, g, rc, rc ? last_error() : std::string(), frames, last_of_slot);
+        }
+        e->cv.notify_all();
+    };
+    // `g` to its end; `next` (may be null) has been enqueued behind it.  A frame of `g` that wants a host step cannot be served from
+    // device state that next's kernels have run over: next is finished and collected first, then those frames of `g` are computed again
+    // on the idle stream.  Returns with `next_done` set in that case.  (The same after a successor whose begin failed half-way: the slot's
+    // current set is no longer g's.)
+    auto finish = [&](InFlight& g, InFlight* next, bool& next_done) {
+        next_done = false;
+        g.total_ms = 0; g.n_host_topk = 0;
+        int rc = group_wait(*s, g, next != nullptr);
+        if (rc == FSLIC_OK && (next || s->par != g.par) && group_needs_host(*s, g)) {
+            if (next) {
+                next->total_ms = 0; next->n_host_topk = 0;
+                int rn = group_wait(*s, *next, false);
+                if (rn == FSLIC_OK) rn = group_complete(e, *s, *next, false);
+                if (rn != FSLIC_OK) drain_failed(*s);
+                collect(next, rn, next->job.n, false);
+                next_done = true;
+            }
+            rc = make_current(*s, g);
+            if (rc == FSLIC_OK) rc = group_complete(e, *s, g, true);
+        } else if (rc == FSLIC_OK) {
+            rc = group_complete(e, *s, g, false);
+        }
+        if (rc != FSLIC_OK) drain_failed(*s);      // (also waits for a successor's kernels: it is finished from its pinned set afterwards)
+        return rc;
+    };
     for (;;) {
         bool took = false;
+        // with a group running: not before the last part of its flight (group.cpp, group_prewait)
+        bool look = false;
+        if (prev) { int rc_ignored; look = group_prewait(*s, *prev, rc_ignored); }      // (an error shows again when the group is waited for)
         {
             std::unique_lock<std::mutex> lk(e->mu);
-            e->cv_work.wait(lk, [&] { return a.has_job || a.quit || (!e->pipe_q.empty() && !e->pipe_gathering && !s->busy && !s->pending && e->sync_waiters == 0 && s->wanted == 0); });
-            if (a.quit) return;
-            if (!a.has_job) {
+            auto queue_open = [&] { return !e->pipe_q.empty() && !e->pipe_gathering && !s->busy && e->sync_waiters == 0 && s->wanted == 0; };
+            e->cv_work.wait(lk, [&] { return a.has_job || a.quit || prev || (queue_open() && !s->pending); });
+            if (a.quit && !prev) return;
+            if (!a.has_job && !a.quit && queue_open() && (!prev || (look && may_follow(e, *s, *prev, e->pipe_q.front())))) {
                 // the submit queue's head, plus -- with batching on -- the submissions behind it that ask for the same work,
                 // as long as the group stays within the frame limit
                 GroupJob& g = a.job;
                 const int unit = e->pipe_q.front().n;
                 g = e->pipe_q.front(); g.n = 0; a.jobs = 0;      // the head's work; its frames arrive with the first gather
-                const int limit = std::min(e->pipe_batch_frames, (int)kMaxGroup);
+                // (behind a running group: no more frames than the arena is carved for)
+                const int limit = std::min(std::min(e->pipe_batch_frames, (int)kMaxGroup), prev ? s->cap_frames : (int)kMaxGroup);
                 auto gather = [&](int max_jobs) {
                     while (!e->pipe_q.empty() && a.jobs < max_jobs) {
                         const GroupJob& j = e->pipe_q.front();
@@ -199,12 +265,49 @@ void slot_worker(fslic_engine* e, Slot* s) {
                     gather(kMaxGroup);
                 }
                 s->launch_timing = e->launch_timing;
-                a.has_job = true;
                 took = true;
             }
         }
-        if (took) { e->cv.notify_all(); e->cv_work.notify_all(); }      // room in the queue (callers); the gathering wait is over (the other slot threads)
-        s->nap_wait = true;          // (read by group_finish alone)
+        if (took) {
+            e->cv.notify_all(); e->cv_work.notify_all();      // room in the queue (callers); the gathering wait is over (the other slot threads)
+            s->nap_wait = true;          // (read by group_wait alone)
+            const int frames = a.job.n;
+            int rc = group_begin(e, *s, a.job);
+            InFlight* const cur = rc == FSLIC_OK ? &s->fl[s->par] : nullptr;
+            if (prev && cur) e->overlapped_groups.fetch_add(1, std::memory_order_relaxed);
+            const std::string err = rc ? last_error() : std::string();
+            if (rc != FSLIC_OK) drain_failed(*s);             // (nothing of the failed group runs any more; a predecessor is complete on the device)
+            bool cur_done = false;
+            int rp = FSLIC_OK;
+            if (prev) {
+                rp = finish(*prev, cur, cur_done);
+                collect(prev, rp, prev->job.n, cur_done);
+                prev = nullptr;
+            }
+            if (rc != FSLIC_OK) {        // a failing group is the slot's last until it has been reported
+                set_last_error(err);
+                collect(nullptr, rc, frames, true);
+            } else if (!cur_done) {
+                // comes back for it after a look at the queue -- unless its predecessor has just failed: nothing more is begun on this slot
+                // before the successor that was already enqueued has been finished too
+                if (rp == FSLIC_OK && e->pipe_overlap.load(std::memory_order_relaxed)) prev = cur;
+                else { bool unused; const int rf = finish(*cur, nullptr, unused); collect(cur, rf, frames, true); }
+            }
+            s->nap_wait = false;
+            continue;
+        }
+        if (prev) {                      // nothing to begin behind it: finished at once
+            s->nap_wait = true;
+            bool unused;
+            const int rp = finish(*prev, nullptr, unused);
+            s->nap_wait = false;
+            collect(prev, rp, prev->job.n, true);
+            prev = nullptr;
+            continue;
+        }
+        if (!a.has_job) continue;
+        // a group handed over by slot number (fslic_hip_submit_group): begin + finish, collected by the caller's fslic_hip_wait_group
+        s->nap_wait = true;
         const int rc = run_group(e, *s, a.job);      // (on a failure nothing runs against the caller's buffers any more once the group is reported done)
         s->nap_wait = false;
         {
@@ -213,11 +316,6 @@ void slot_worker(fslic_engine* e, Slot* s) {
             a.err = rc ? last_error() : std::string();
             a.has_job = false;
             a.done = true;
-            if (a.from_queue) {                  // nobody waits for this slot by number: collected here
-                pipeline_collect(e, *s);
-                a.from_queue = false;
-                e->pipe_inflight--;
-            }
         }
         e->cv.notify_all();
     }
@@ -344,6 +442,12 @@ int fslic_hip_pipeline_batching(fslic_engine* e, int max_frames_per_group) {
     std::lock_guard<std::mutex> lk(e->mu);
     e->pipe_batch_frames = max_frames_per_group;
     e->reserve_frames.store(max_frames_per_group);
+    return FSLIC_OK;
+}
+
+int fslic_hip_pipeline_overlap(fslic_engine* e, int on) {
+    if (!e) return fail(FSLIC_E_INVALID, "engine is NULL");
+    e->pipe_overlap.store(on != 0, std::memory_order_relaxed);      // (read by the slot threads when they look at the queue: groups already begun are finished as they were begun)
     return FSLIC_OK;
 }
 

@@ -272,6 +272,19 @@ int fslic_hip_separate_pass_redos(fslic_engine* e, int slot);
  * can.  Diagnostics aid. */
 int fslic_hip_uncovered_redos(fslic_engine* e, int slot);
 
+/* Groups of the submit / drain pipeline, since the engine was created, that a slot's thread began while the slot's previous group had not
+ * been collected yet: the slot's stream received the next group's kernels behind those of the running one, and the running group was
+ * waited for, written back and collected afterwards.  A slot thread does this when the submission at the head of the queue asks for the
+ * same work (H, W, K, params) as the group it has running, the slot's buffers serve it as they are, no other slot is free to take it, and
+ * neither per-launch timing, preemptive mode nor the 'noq' variant is involved; never for fslic_hip_submit_group or the synchronous
+ * entry points.  Results do not depend on it.  -1: no engine.  Diagnostics aid. */
+long long fslic_hip_overlapped_groups(fslic_engine* e);
+
+/* on == 0: the slot threads of this engine finish every group before they begin the next one (the serial loop: depth one, as for
+ * fslic_hip_submit_group), and fslic_hip_overlapped_groups stops counting; on != 0 (the default): as described above.  Takes effect
+ * with the next submission a slot thread takes from the queue.  For A/B measurements and tests. */
+int fslic_hip_pipeline_overlap(fslic_engine* e, int on);
+
 /* Debug entries, for tests only: the record of kernel FORMS.  The assign pass is a family of template instantiations picked by the
  * spatial table, the stride, the launch size and the mode, and the preemptive update has two forms; every launch site notes a code for the
  * instantiation it chose when it enqueues the launch or records it into a graph (a replay adds nothing).  The record is the process-wide
