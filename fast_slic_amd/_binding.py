@@ -67,6 +67,8 @@ EXPORTS = [
     "fslic_hip_crf_tensor_grad_workspace_size", "fslic_hip_crf_tensor_inference_saved", "fslic_hip_crf_tensor_backward",
     "fslic_hip_crf_tensor_energies", "fslic_hip_crf_tensor_energies_backward_workspace_size", "fslic_hip_crf_tensor_energies_backward",
     "fslic_hip_crf_tensor_inference_energies", "fslic_hip_crf_tensor_inference_saved_energies", "fslic_hip_crf_tensor_backward_energies",
+    # soft superpixel assignment on feature tensors (fast_slic_amd/soft.py)
+    "fslic_hip_soft_assign", "fslic_hip_soft_assign_backward", "fslic_hip_soft_pool", "fslic_hip_soft_unpool", "fslic_hip_soft_dot",
 ]
 
 _lib = None
@@ -221,6 +223,8 @@ def load_library():
             _declare_compare(lib)
         if hasattr(lib, "fslic_hip_crf_tensor_inference"):
             _declare_crf_tensor(lib)
+        if hasattr(lib, "fslic_hip_soft_assign"):
+            _declare_soft(lib)
         _lib = lib
         return lib
 
@@ -306,6 +310,19 @@ def _declare_crf_tensor(lib):
         for name in ("energies", "energies_backward_workspace_size", "energies_backward", "inference_energies", "inference_saved_energies",
                      "backward_energies"):
             getattr(lib, "fslic_hip_crf_tensor_" + name).restype = i32
+
+
+def _declare_soft(lib):
+    """Signatures of the soft superpixel assignment entry points (include/fslic_hip.h)."""
+    vp, i32 = C.c_void_p, C.c_int
+    geom = [i32, vp, i32, i32, i32, i32, i32, i32]      # device, stream, N, C, H, W, gh, gw
+    lib.fslic_hip_soft_assign.argtypes = geom + [vp, vp, vp]
+    lib.fslic_hip_soft_assign_backward.argtypes = geom + [vp, vp, vp, vp, vp, vp]
+    lib.fslic_hip_soft_pool.argtypes = geom + [vp, vp, vp, vp, vp]
+    lib.fslic_hip_soft_unpool.argtypes = geom + [vp, vp, vp]
+    lib.fslic_hip_soft_dot.argtypes = geom + [vp, vp, vp, vp]
+    for name in ("soft_assign", "soft_assign_backward", "soft_pool", "soft_unpool", "soft_dot"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _raise(rc):

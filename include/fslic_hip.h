@@ -560,6 +560,35 @@ int fslic_hip_crf_tensor_backward_energies(int device, void* stream, int N, int 
                                            float* grad_unaries, float* grad_q0, float* grad_compat, float* grad_edge, float* grad_links,
                                            void* workspace, size_t workspace_bytes);
 
+/* ---- Soft superpixel assignment on feature planes (NEW surface, no counterpart in the reference; Python: fast_slic_amd/soft.py) ----
+ * SLIC's k-means on float feature planes over a regular grid of gh x gw seed cells with soft assignments: every pixel is distributed over
+ * the 3 x 3 cells around its own (Superpixel Sampling Networks, Jampani et al. 2018).  Entries as for pooling: a device index and a
+ * stream, no synchronisation, no allocation, no workspace, the caller's device restored, every argument checked before the first HIP call
+ * (FSLIC_E_INVALID): N, C >= 1, H * W < 2^31, 1 <= gh <= H, 1 <= gw <= W, K = gh * gw <= 65534.
+ *   features : float [N][C][H][W]     centres, values, sums : float [N][C][K]     q, grad_q, grad_d : float [N][9][H][W]     weights : float [N][K]
+ * Pixel (y, x) lies in cell (cy, cx) = ((y * gh) / H, (x * gw) / W) (integers).  Slot j = 3 (dy + 1) + (dx + 1), dy, dx in {-1, 0, 1}, of
+ * a pixel names cell (cy + dy, cx + dx), superpixel k_j = (cy + dy) * gw + (cx + dx); a slot outside the grid is invalid: it takes part
+ * in no sum, and every output plane holds +0.0 there.  j_k(p) is the slot of pixel p that names k.  No atomics: every result is
+ * bitwise reproducible and independent of the batch position and of the other channels. */
+/* d_j = sum_c (F[c][p] - S[c][k_j])^2;  q_j = exp(-(d_j - min d)) / sum over the valid slots. */
+int fslic_hip_soft_assign(int device, void* stream, int N, int C, int H, int W, int gh, int gw, const float* features,
+                          const float* centres, float* q);
+/* grad_d_j = -q_j (grad_q_j - sum_i grad_q_i q_i);  grad_features[c][p] = 2 sum_j grad_d_j (F[c][p] - S[c][k_j]).  The gradient of the
+ * centres is -2 times fslic_hip_soft_pool(features, grad_d, centres). */
+int fslic_hip_soft_assign_backward(int device, void* stream, int N, int C, int H, int W, int gh, int gw, const float* features,
+                                   const float* centres, const float* q, const float* grad_q, float* grad_d, float* grad_features);
+/* sums[c][k] = sum_p q_{j_k(p)}(p) F[c][p] over the pixels of the 3 x 3 cell window of k, with centres (optional) the sum of
+ * q_{j_k(p)}(p) (F[c][p] - centres[c][k]);  weights (optional) [k] = sum_p q_{j_k(p)}(p). */
+int fslic_hip_soft_pool(int device, void* stream, int N, int C, int H, int W, int gh, int gw, const float* features, const float* q,
+                        const float* centres, float* sums, float* weights);
+/* out[c][p] = sum over the valid slots of q_j(p) values[c][k_j]. */
+int fslic_hip_soft_unpool(int device, void* stream, int N, int C, int H, int W, int gh, int gw, const float* values, const float* q,
+                          float* out);
+/* out_j(p) = sum_c a[c][p] b[c][k_j] + bias[k_j] (a: [N][C][H][W], b: [N][C][K], bias: [N][K] or NULL): the gradient of soft_pool and
+ * of soft_unpool with respect to q. */
+int fslic_hip_soft_dot(int device, void* stream, int N, int C, int H, int W, int gh, int gw, const float* a, const float* b,
+                       const float* bias, float* out);
+
 const char* fslic_hip_last_error(void);
 const char* fslic_hip_version(void);
 
