@@ -17,6 +17,13 @@ namespace fslic {
 constexpr int kSoftChunk = 16;         // channels of one k_soft_pool item (one accumulator register each)
 constexpr int kSoftStage = 4096;       // pixels of a window staged in LDS at a time (weight and pixel offset: 32 KB)
 constexpr int kSoftMaxK = 65534;
+// Launch rule.  Every kernel runs one 256-thread block per item (a pixel kernel: N * ceil(H W / 256) blocks; k_soft_pool: N * K *
+// ceil(C / kSoftChunk)), and the entries admit both counts up to 2^31 - 1.  The HIP runtime supports no launch of 2^32 or more threads
+// in a grid dimension, that is 2^24 blocks of 256, and it does not refuse one: measured on the MI355X, a grid of b >= 2^24 blocks
+// returns hipSuccess and runs b mod 2^24 of them, so the rest of the output stays unwritten.  The launches of soft.hip therefore go
+// out in slices of at most kSoftMaxBlocks blocks, in order on the stream, each with the flat index of its first block as the kernel's
+// last argument: a block computes what it would in one launch, bit for bit, and below 2^24 blocks there is one launch as before.
+constexpr unsigned long long kSoftMaxBlocks = (1ull << 24) - 1ull;     // 2^32 - 256 threads: the largest launch the runtime supports
 
 // d_j = sum_c (F[c][p] - S[c][k_j])^2 in ascending c; Q_j = exp(-(d_j - min d)) / sum over the valid slots
 void launch_soft_assign(const float* feat, const float* centres, float* q, int N, int C, int H, int W, int gh, int gw, hipStream_t st);

@@ -52,14 +52,15 @@ static __device__ __forceinline__ uint32_t soft_slots(const SoftGrid& g, uint32_
     return ok;
 }
 
+// `first`: the flat block index of the launch's block 0 (launch_sliced)
 #define SOFT_PIXEL()                                                           \
-    const uint32_t n = blockIdx.x / bpf, p = (blockIdx.x - n * bpf) * 256u + threadIdx.x; \
+    const uint32_t blk = first + blockIdx.x, n = blk / bpf, p = (blk - n * bpf) * 256u + threadIdx.x; \
     if (p >= HW) return;                                                       \
     uint32_t k[9];                                                             \
     const uint32_t ok = soft_slots(g, p, k)
 
 __global__ __launch_bounds__(256) void k_soft_assign(const float* __restrict__ feat, const float* __restrict__ cen, float* __restrict__ q,
-                                                     SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf) {
+                                                     SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf, uint32_t first) {
     SOFT_PIXEL();
     const float* __restrict__ f = feat + (size_t)n * C * HW + p;
     const float* __restrict__ s = cen + (size_t)n * C * K;
@@ -90,7 +91,8 @@ __global__ __launch_bounds__(256) void k_soft_assign(const float* __restrict__ f
 
 __global__ __launch_bounds__(256) void k_soft_assign_bwd(const float* __restrict__ feat, const float* __restrict__ cen,
                                                          const float* __restrict__ q, const float* __restrict__ gq, float* __restrict__ gd,
-                                                         float* __restrict__ gfeat, SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf) {
+                                                         float* __restrict__ gfeat, SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf,
+                                                         uint32_t first) {
     SOFT_PIXEL();
     const size_t qoff = (size_t)n * 9u * HW + p;
     float qq[9], gg[9], dot = 0.0f;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(256) void k_soft_assign_bwd(const float* __restrict
 }
 
 __global__ __launch_bounds__(256) void k_soft_unpool(const float* __restrict__ values, const float* __restrict__ q, float* __restrict__ out,
-                                                     SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf) {
+                                                     SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf, uint32_t first) {
     SOFT_PIXEL();
     const size_t qoff = (size_t)n * 9u * HW + p;
     float qq[9];
@@ -135,7 +137,8 @@ __global__ __launch_bounds__(256) void k_soft_unpool(const float* __restrict__ v
 }
 
 __global__ __launch_bounds__(256) void k_soft_dot(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ bias,
-                                                  float* __restrict__ out, SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf) {
+                                                  float* __restrict__ out, SoftGrid g, int C, uint32_t HW, uint32_t K, uint32_t bpf,
+                                                  uint32_t first) {
     SOFT_PIXEL();
     const float* __restrict__ f = a + (size_t)n * C * HW + p;
     const float* __restrict__ t = b + (size_t)n * C * K;
@@ -180,12 +183,12 @@ static __device__ __forceinline__ void soft_pool_piece(const float* s_w, const u
 template <bool kCentred>
 __global__ __launch_bounds__(256) void k_soft_pool(const float* __restrict__ feat, const float* __restrict__ q, const float* __restrict__ cen,
                                                    float* __restrict__ sums, float* __restrict__ weights, SoftGrid g, int C, uint32_t HW,
-                                                   uint32_t K, uint32_t nchunk) {
+                                                   uint32_t K, uint32_t nchunk, uint32_t first) {
     __shared__ float s_w[kSoftStage];
     __shared__ uint32_t s_p[kSoftStage];
     __shared__ float s_part[4][kSoftChunk + 1];
     const uint32_t tid = threadIdx.x;
-    const uint32_t chunk = blockIdx.x % nchunk, nk = blockIdx.x / nchunk, k = nk % K, n = nk / K;
+    const uint32_t item = first + blockIdx.x, chunk = item % nchunk, nk = item / nchunk, k = nk % K, n = nk / K;
     const uint32_t cy = k / g.gw, cx = k - cy * g.gw;
     // the window: the cells (cy - 1 .. cy + 1) x (cx - 1 .. cx + 1) inside the grid, as a pixel rectangle; yb1, yb2 (xb1, xb2) are
     // the first rows (columns) of k's own cell and of the cell behind it
@@ -234,41 +237,51 @@ __global__ __launch_bounds__(256) void k_soft_pool(const float* __restrict__ fea
         weights[(size_t)n * K + k] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
 }
 
-// ---- launches (the entries of softapi.cpp have checked every argument: N * ceil(H W / 256) and the pool items fit a grid) ----
+// ---- launches (the entries of softapi.cpp have checked every argument: N * ceil(H W / 256) and the pool items are below 2^31) ----
+// One block per item, issued in slices of at most kSoftMaxBlocks blocks (soft.h has the rule and why).  A kernel's last argument is
+// the flat index of its slice's first block, so every block computes exactly what it would in a single launch.
+template <typename... KArgs, typename... Args>
+static void launch_sliced(void (*kernel)(KArgs...), unsigned long long blocks, hipStream_t st, Args... args) {
+    for (unsigned long long first = 0; first < blocks; first += kSoftMaxBlocks) {
+        const unsigned long long nb = blocks - first < kSoftMaxBlocks ? blocks - first : kSoftMaxBlocks;
+        launch(kernel, dim3((uint32_t)nb), dim3(256), 0, st, args..., (uint32_t)first);
+    }
+}
+
 #define SOFT_PIXEL_GRID()                                                  \
     const uint32_t HW = (uint32_t)H * (uint32_t)W, bpf = (HW + 255u) / 256u; \
-    const dim3 grid(bpf * (uint32_t)N);                                    \
+    const unsigned long long blocks = (unsigned long long)bpf * (unsigned long long)N; \
     const SoftGrid g = soft_grid(H, W, gh, gw);                            \
     const uint32_t K = (uint32_t)gh * (uint32_t)gw
 
 void launch_soft_assign(const float* feat, const float* centres, float* q, int N, int C, int H, int W, int gh, int gw, hipStream_t st) {
     SOFT_PIXEL_GRID();
-    launch(k_soft_assign, grid, dim3(256), 0, st, feat, centres, q, g, C, HW, K, bpf);
+    launch_sliced(k_soft_assign, blocks, st, feat, centres, q, g, C, HW, K, bpf);
 }
 
 void launch_soft_assign_bwd(const float* feat, const float* centres, const float* q, const float* gq, float* gd, float* gfeat,
                             int N, int C, int H, int W, int gh, int gw, hipStream_t st) {
     SOFT_PIXEL_GRID();
-    launch(k_soft_assign_bwd, grid, dim3(256), 0, st, feat, centres, q, gq, gd, gfeat, g, C, HW, K, bpf);
+    launch_sliced(k_soft_assign_bwd, blocks, st, feat, centres, q, gq, gd, gfeat, g, C, HW, K, bpf);
 }
 
 void launch_soft_unpool(const float* values, const float* q, float* out, int N, int C, int H, int W, int gh, int gw, hipStream_t st) {
     SOFT_PIXEL_GRID();
-    launch(k_soft_unpool, grid, dim3(256), 0, st, values, q, out, g, C, HW, K, bpf);
+    launch_sliced(k_soft_unpool, blocks, st, values, q, out, g, C, HW, K, bpf);
 }
 
 void launch_soft_dot(const float* a, const float* b, const float* bias, float* out, int N, int C, int H, int W, int gh, int gw, hipStream_t st) {
     SOFT_PIXEL_GRID();
-    launch(k_soft_dot, grid, dim3(256), 0, st, a, b, bias, out, g, C, HW, K, bpf);
+    launch_sliced(k_soft_dot, blocks, st, a, b, bias, out, g, C, HW, K, bpf);
 }
 
 void launch_soft_pool(const float* feat, const float* q, const float* centres, float* sums, float* weights,
                       int N, int C, int H, int W, int gh, int gw, hipStream_t st) {
     const uint32_t HW = (uint32_t)H * (uint32_t)W, K = (uint32_t)gh * (uint32_t)gw, nchunk = (uint32_t)((C + kSoftChunk - 1) / kSoftChunk);
-    const dim3 grid((uint32_t)soft_pool_items(N, C, (int)K));
+    const unsigned long long items = soft_pool_items(N, C, (int)K);
     const SoftGrid g = soft_grid(H, W, gh, gw);
-    if (centres) launch(k_soft_pool<true>, grid, dim3(256), 0, st, feat, q, centres, sums, weights, g, C, HW, K, nchunk);
-    else launch(k_soft_pool<false>, grid, dim3(256), 0, st, feat, q, centres, sums, weights, g, C, HW, K, nchunk);
+    if (centres) launch_sliced(k_soft_pool<true>, items, st, feat, q, centres, sums, weights, g, C, HW, K, nchunk);
+    else launch_sliced(k_soft_pool<false>, items, st, feat, q, centres, sums, weights, g, C, HW, K, nchunk);
 }
 
 }  // namespace fslic

@@ -8,6 +8,8 @@ using namespace fslic;
 
 namespace {
 
+// The two block counts are admitted up to 2^31 - 1 and all of them are served: soft.hip issues a launch in slices the runtime
+// supports (soft.h, the launch rule).
 int check_soft(int device, int N, int C, int H, int W, int gh, int gw) {
     if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
     if (N < 1 || C < 1) return fail(FSLIC_E_INVALID, "N and C must be positive");

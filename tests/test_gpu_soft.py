@@ -18,11 +18,10 @@ from fast_slic_amd.pool import superpixel_pool, superpixel_unpool
 from fast_slic_amd.rag import superpixel_graph
 from fast_slic_amd.soft import _pool_raw, soft_assign, soft_labels, soft_pool, soft_slic, soft_unpool, with_coords
 from fast_slic_amd.synth import variant as synth
+from soft_cases import DEV, FLOOR, Case, bits_equal, hold, rel                     # shared with test_gpu_soft_edges.py
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-FLOOR = 2.0 ** -20
-N = 3
+N = 3                                       # Case's default number of frames
 # the smallest shapes at which the kernels can go wrong: cell sizes that do not divide; K = 1 (only slot 4 is valid); a strip each
 # way; one-pixel-tall and 65-pixel-wide cells with rows that cross a wavefront; a window of 36 864 pixels, past the staging buffer
 SHAPES = [(37, 53, (3, 5)), (9, 9, (1, 1)), (5, 64, (1, 7)), (64, 5, (7, 1)), (16, 130, (16, 2)), (192, 192, (1, 1))]
@@ -31,73 +30,11 @@ CASES = [(H, W, g, Cc) for (H, W, g) in SHAPES for Cc in CHANNELS]
 _cache = {}
 
 
-def rel(x, ref):
-    """max |x - ref| / max |ref| (the plain max |x - ref| where the reference is zero everywhere: K = 1 has no gradient to assign)"""
-    scale = float(ref.abs().max())
-    return float((x.detach().cpu().double() - ref).abs().max()) / (scale if scale > 0 else 1.0)
-
-
-def hold(name, got, ref64, ref32):
-    err, b = rel(got, ref64), rel(ref32, ref64)
-    bound = max(8.0 * b, FLOOR)
-    print("%-16s err %.3e  b %.3e  bound %.3e  err/bound %.3f" % (name, err, b, bound, err / bound))
-    assert err <= bound, "%s: err %.3e above max(8 b, 2^-20) = %.3e" % (name, err, bound)
-    return err / bound
-
-
-class Case(object):
-    """Random inputs of one shape and the model's results in float64 and float32, computed once."""
-    NAMES = ("F", "S", "Q", "V", "gQ", "gS", "gW", "gO")
-
-    def __init__(self, H, W, grid, Cc):
-        g = torch.Generator().manual_seed(1000 * H + 10 * W + Cc)
-        K = grid[0] * grid[1]
-        rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)
-        self.H, self.W, self.grid, self.Cc, self.K = H, W, grid, Cc, K
-        self.F = rnd(N, Cc, H, W) * 0.5
-        first = R.soft_pool(self.F.double(), R.one_hot(N, H, W), grid)
-        self.S = (first + rnd(N, Cc, K).double() * (0.6 / Cc ** 0.5)).float()       # spreads Q over the slots
-        self.V = rnd(N, Cc, K)
-        self.gQ, self.gS, self.gW, self.gO = rnd(N, 9, H, W), rnd(N, Cc, K), rnd(N, K), rnd(N, Cc, H, W)
-        self.Q = R.soft_assign(self.F, self.S, grid)                                # the float32 model's Q feeds pool and unpool
-        self.ref = {dt: self.run(self.tensors("cpu", dt), R.soft_assign, R.soft_pool_raw, R.soft_unpool)
-                    for dt in (torch.float64, torch.float32)}
-
-    def tensors(self, device, dtype=torch.float32, frames=slice(None)):
-        return {n: getattr(self, n)[frames].to(device=device, dtype=dtype) for n in self.NAMES}
-
-    def run(self, t, assign, pool, unpool):
-        """the three stages and their backwards through one implementation, on the tensors t -> dict of detached results"""
-        leaf = lambda x: x.clone().requires_grad_(True)
-        out = {}
-        F, S = leaf(t["F"]), leaf(t["S"])
-        q = assign(F, S, self.grid)
-        out["assign Q"] = q
-        out["assign gF"], out["assign gS"] = torch.autograd.grad((q * t["gQ"]).sum(), (F, S))
-        F, Q = leaf(t["F"]), leaf(t["Q"])
-        sums, weights = pool(F, Q, self.grid)
-        out["pool sums"], out["pool weights"] = sums, weights
-        out["pool gF"], out["pool gQ"] = torch.autograd.grad((sums * t["gS"]).sum() + (weights * t["gW"]).sum(), (F, Q))
-        V, Q = leaf(t["V"]), leaf(t["Q"])
-        o = unpool(V, Q, self.grid)
-        out["unpool out"] = o
-        out["unpool gV"], out["unpool gQ"] = torch.autograd.grad((o * t["gO"]).sum(), (V, Q))
-        return {k: v.detach() for k, v in out.items()}
-
-    def gpu(self, frames=slice(None), t=None):
-        pool = lambda f, q, grid: soft_pool(f, q, grid, normalize=False, return_weights=True)
-        return self.run(self.tensors(DEV, frames=frames) if t is None else t, soft_assign, pool, soft_unpool)
-
-
 def case(H, W, grid, Cc):
     key = (H, W, grid, Cc)
     if key not in _cache:
         _cache[key] = Case(H, W, grid, Cc)
     return _cache[key]
-
-
-def bits_equal(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---- every stage against the model, and the properties that hold bit for bit ----
