@@ -69,6 +69,8 @@ EXPORTS = [
     "fslic_hip_crf_tensor_inference_energies", "fslic_hip_crf_tensor_inference_saved_energies", "fslic_hip_crf_tensor_backward_energies",
     # soft superpixel assignment on feature tensors (fast_slic_amd/soft.py)
     "fslic_hip_soft_assign", "fslic_hip_soft_assign_backward", "fslic_hip_soft_pool", "fslic_hip_soft_unpool", "fslic_hip_soft_dot",
+    # connectivity on label tensors (fast_slic_amd/connect.py)
+    "fslic_hip_connect_workspace_size", "fslic_hip_connected_components", "fslic_hip_connect_enforce",
 ]
 
 _lib = None
@@ -225,8 +227,21 @@ def load_library():
             _declare_crf_tensor(lib)
         if hasattr(lib, "fslic_hip_soft_assign"):
             _declare_soft(lib)
+        if hasattr(lib, "fslic_hip_connect_enforce"):
+            _declare_connect(lib)
         _lib = lib
         return lib
+
+
+def _declare_connect(lib):
+    """Signatures of the entry points of the connectivity pass on label tensors (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    head = [i32, vp, i32, i32, i32, vp, i32]      # device, stream, N, H, W, labels, label_type
+    lib.fslic_hip_connect_workspace_size.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.fslic_hip_connected_components.argtypes = head + [vp, vp, vp, sz]
+    lib.fslic_hip_connect_enforce.argtypes = head + [i64, vp, vp, vp, sz]
+    for name in ("connect_workspace_size", "connected_components", "connect_enforce"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _declare_crf(lib):

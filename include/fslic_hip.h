@@ -459,6 +459,28 @@ int fslic_hip_overlap_compact(int device, void* stream, int N, long long capacit
 int fslic_hip_boundary_match(int device, void* stream, int N, int H, int W, const void* labels, int label_type,
                              const void* other, int other_type, int tolerance, int64_t* counts);
 
+/* ---- Connectivity on label tensors (NEW surface; Python: fast_slic_amd/connect.py, which states the rules) ----
+ * The 4-connected components of equal labels of every frame, and the merge of the components below a minimum area: the reference's
+ * ConnectivityEnforcer::execute (src/cca.cpp:178-265) without its cut at K labels, on device memory.  Entries as for pooling: a device
+ * index and a stream, no synchronisation, no allocation, no copy to the host, no host path for any input, the caller's device
+ * restored, every argument checked before the first HIP call (FSLIC_E_INVALID).
+ *   labels : [N][H][W] of label_type (FSLIC_LABEL_*), N * H * W < 2^31; values are compared for equality only, at their own width
+ *   out    : int32 [N][H][W], overlaps neither the labels nor the workspace        counts : int32 [N]
+ * A component's leader is its first pixel in raster order; components are numbered 0, 1, ... in ascending leader order.
+ * The workspace holds 8 bytes per pixel (two uint32 planes, each rounded up to 16 bytes: the leader of every pixel; the area, then the
+ * label, of every leader) and 4 bytes per 1024 pixels of a frame (rounded up likewise).  It needs no clearing.  All integer
+ * arithmetic; a component's root is always its smallest raster index, so the result does not depend on the order of execution. */
+int fslic_hip_connect_workspace_size(int N, int H, int W, size_t* bytes);
+/* components[n][p] = the number of p's component, counts[n] = the components of frame n. */
+int fslic_hip_connected_components(int device, void* stream, int N, int H, int W, const void* labels, int label_type,
+                                   int32_t* components, int32_t* counts, void* workspace, size_t workspace_bytes);
+/* The components of at least min_size (>= 0) pixels are kept and take the labels 0, 1, ... in ascending leader order.  Component 0,
+ * when it is not kept, takes label 0; every other component that is not kept takes the final label of the component of the pixel
+ * left of its leader (above it for a leader in column 0).  counts[n] = the kept components of frame n, 1 when there are none: the
+ * labels 0 .. counts[n] - 1 all occur, and counts[n] <= H * W / min_size for min_size >= 1. */
+int fslic_hip_connect_enforce(int device, void* stream, int N, int H, int W, const void* labels, int label_type, long long min_size,
+                              int32_t* out, int32_t* counts, void* workspace, size_t workspace_bytes);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
