@@ -21,6 +21,7 @@
 #include <condition_variable>
 #include <deque>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -80,10 +81,19 @@ public:
 template <class T> using Pinned = Buffer<T, false>;
 template <class T> using Device = Buffer<T, true>;
 
-// One group request as the C entry points receive it: up to kMaxGroup frames of one geometry under one parameter set.
-struct GroupJob {
+// One work: a geometry under one parameter set.  Frames of the same work share launch groups (pipeline.cpp), a running group may be
+// followed by one of the same work (may_follow), and the sticky fallback of the label-free passes belongs to one (Slot::store_work).
+struct Work {
     fslic_params p{};
-    int H = 0, W = 0, K = 0, n = 0;
+    int H = 0, W = 0, K = 0;
+};
+inline bool same_work(const Work& a, const Work& b) {
+    return a.H == b.H && a.W == b.W && a.K == b.K && memcmp(&a.p, &b.p, sizeof(fslic_params)) == 0;
+}
+
+// One group request as the C entry points receive it: up to kMaxGroup frames of one work.
+struct GroupJob : Work {
+    int n = 0;
     const uint8_t* d_rgb[kMaxGroup] = {};
     fslic_cluster* clusters[kMaxGroup] = {};
     uint16_t* d_out[kMaxGroup] = {};
@@ -141,13 +151,28 @@ struct PinnedSet {
     Pinned<void*> h_ptrs;            // the source of the pointer table's asynchronous copy
 };
 
+// What enqueue_frames runs for a launch beyond the values of its launch arguments: decided once per launch by choose_passes (group.cpp),
+// part of the graph key byte by byte (all members are bool: no padding), and kept by the group (InFlight::choice).
+struct PassChoice {
+    // the family: which assign loop runs, and on which kernels
+    bool generic;                    // the brute-force gather kernel (k_assign_generic) for the integer SLIC path
+    bool rec;                        // debug_mode: the recording forms and a snapshot after every cluster pass
+    bool pre;                        // preemptive mode
+    bool lsc;                        // the LSC loop
+    bool rd, rd_l2, noq;             // the float-distance loop (RealDist, RealDistL2, RealDistNoQ), and which of its kinds
+    bool need_patch;                 // the (2S+1)^2 patch of the generic kernel has to be on the device
+    bool fused;                      // the cluster passes run inside the assign launches (launch_assign_fused_bin)
+    bool lazy_labels;                // the LAB kernel leaves the label plane alone, first visits reset it (FrameDev::fv_mod)
+    bool label_free;                 // the subsampled passes store no labels at all (DESIGN.md "Deferred labels")
+};
+
 // A group between group_begin and its completion: everything the finish needs, so that the slot's per-call state may already be that
 // of the next group.
 struct InFlight {
     GroupJob job;                    // geometry, parameters, frames, the callers' buffers and Cluster[K] blocks
     int S = 0;
     int par = 0;                     // its PinnedSet
-    bool generic = false;
+    PassChoice choice{};             // what its begin chose: a frame computed again from scratch runs the same passes
     int launch_mode = 0;             // Slot::last_launch_mode of its begin
     double t_begun_us = 0;           // when group_begin returned (nap_wait's history counts from here)
     // what its finish found, for whoever collects it (the slot's own fields of the same names belong to the group finished LAST)
@@ -230,14 +255,13 @@ struct Slot {
     int last_path = 0;
     int n_host_topk = 0;             // frames of the last group whose top-K step ran on the host
     int n_separate_redo = 0;         // (accessed with __atomic builtins) frames (since the slot was created) redone with the separate cluster pass because of a stale pixel
-    // Label-free passes (group.cpp, enqueue_frames): once a frame of this slot had to be redone because a visited pixel lay outside every
-    // window, the slot keeps to the storing passes for that work (H, W, K, params: same_work's notion) -- a stream of scattered warm
-    // starts pays the redo once, not in every group; another work starts afresh.
+    // Label-free passes (group.cpp, choose_passes): once a frame of this slot had to be redone because a visited pixel lay outside every
+    // window, the slot keeps to the storing passes for that work (same_work) -- a stream of scattered warm starts pays the redo once,
+    // not in every group; another work starts afresh.
     int n_uncovered_redo = 0;        // (accessed with __atomic builtins) frames (since the slot was created) redone with storing passes because of kFlagUncoveredPixel
-    bool store_labels = false;       // the sticky fallback is in force for (store_H, store_W, store_K, store_p)
+    bool store_labels = false;       // the sticky fallback is in force for store_work
     bool store_seen_credit = false;  // the fallback has just begun: the group that caused it counts as the first sighting of the storing sequence (launch_group)
-    int store_H = 0, store_W = 0, store_K = 0;
-    fslic_params store_p{};
+    Work store_work;
     bool have_pre = false;
     // Ownership (guarded by fslic_engine::mu): `busy` while a synchronous call or a stage utility runs on the slot,
     // `pending` from the submission of an asynchronous group until it has been collected.

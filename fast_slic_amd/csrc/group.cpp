@@ -8,6 +8,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <cassert>
 #include <charconv>
 #include <chrono>
 #include <cmath>
@@ -213,11 +214,11 @@ void stage_group(fslic_engine* e, Slot& s, int i0, int n, bool timed) {
     }
 }
 
-// Whether a group's cluster passes run inside its assign launches (the per-cluster fused form, assign.hip: k_assign_bin): the integer
-// SLIC path on the block kernel, launches that do not fill the chip (FSLIC_FUSEBIN=1, the default) or all of them (=2).
-static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, int W, int H, bool generic, bool separate_cluster_pass) {
-    const int stride = p.subsample_stride;
-    const int assign_blocks = assign_blocks8(W, visited_rows(H, 0, stride), n);      // (the first pass's: launch_assign_fused_bin's own count)
+// Whether a launch of `n` frames wants its cluster passes inside its assign launches (the per-cluster fused form, assign.hip:
+// k_assign_bin): launches that do not fill the chip (FSLIC_FUSEBIN=1, the default) or all of them (=2), where every pass has rows.
+static bool cluster_pass_fused(const Slot& s, int n) {
+    const int stride = s.p.subsample_stride;
+    const int assign_blocks = assign_blocks8(s.W, visited_rows(s.H, 0, stride), n);      // (the first pass's: launch_assign_fused_bin's own count)
 #if defined(FSLIC_LAB) && FSLIC_LAB == 3
     // lab build 3 turns st_stream into plain stores; the fused cluster pass hands partial sums from block to block through
     // written-through (sc1) stores and agent-scope loads and would read stale lines of another XCD's L2: never fused there
@@ -226,17 +227,59 @@ static bool cluster_pass_fused(const FrameDev& f, const fslic_params& p, int n, 
 #else
     const bool fuse_wanted = knobs().fuse_bin == 2 || (knobs().fuse_bin == 1 && assign_blocks <= kBlocksFuseBin);
 #endif
-    const bool plain_slic = p.variant == FSLIC_VARIANT_SLIC && p.preemptive == 0;
     // (H < stride: the passes of the residues >= H visit no row at all and launch nothing -- src/context.cpp:158-175 still runs update()
     // for them: every cluster's num_members becomes 0, positions stay; a cluster pass that rides on the assign blocks would not happen.
     // Found on a 71x1 frame, tests/fuzz_parity.py FUZZ_SHAPES=tiny seed 5 case 3100.)
-    const bool every_pass_has_rows = H >= stride;
-    return fuse_wanted && !separate_cluster_pass && plain_slic && !generic && every_pass_has_rows && blk_kernel_applies(f, stride);
+    const bool every_pass_has_rows = s.H >= stride;
+    return fuse_wanted && every_pass_has_rows;
 }
 
 // Whether the slot's current work may take the label-free passes at all: not under the sticky fallback of a slot that has had to redo a
-// frame of this work (Slot::store_labels).  An input of enqueue_frames' choice that no launch argument shows: in the graph key.
+// frame of this work (Slot::store_labels).
 static bool label_free_allowed(const Slot& s) { return !s.store_labels; }
+
+// What a launch asks of choose_passes beyond the slot's current work.  The defaults are a group's own launch; a frame redone because
+// of a kernel flag asks for the conservative passes (group_complete).
+struct ChoiceRequest {
+    int count = 0;                   // frames of the launch: what the fusing rule is judged by
+    bool force_generic = false;      // the generic kernel whatever the slot's geometry allows (a candidate list overflowed)
+    bool allow_fused = true;         // false: the separate cluster pass
+    bool allow_label_free = true;    // false: storing passes
+};
+
+// The ONE place where the passes of a launch are decided, from the slot's current work (geometry, parameters, Slot::generic,
+// Slot::recording, the sticky fallback) and the request.  Everything here that no launch argument shows reaches the graph key with the
+// value (launch_group).
+static PassChoice choose_passes(const Slot& s, const ChoiceRequest& rq) {
+    const fslic_params& p = s.p;
+    const bool slic = p.variant == FSLIC_VARIANT_SLIC;
+    const bool blk = blk_kernel_applies(s.f, p.subsample_stride);
+    PassChoice c{};
+    c.generic = s.generic || rq.force_generic;
+    c.rec = s.recording && rq.count == 1;
+    c.pre = p.preemptive != 0;
+    c.lsc = p.variant == FSLIC_VARIANT_LSC;
+    c.noq = p.variant == FSLIC_VARIANT_REALDIST_NOQ;
+    c.rd_l2 = p.variant == FSLIC_VARIANT_REALDIST_L2;
+    c.rd = p.variant == FSLIC_VARIANT_REALDIST || c.rd_l2 || c.noq;
+    // the patch also where a preemptive Slic group falls back to the generic kernel for its subsampled passes (geometries outside the
+    // block kernel: launch_assign_pre returns false)
+    c.need_patch = c.generic || (c.pre && slic && !blk);
+    // the cluster pass rides on the assign blocks of the integer SLIC path on the block kernel only
+    c.fused = rq.allow_fused && slic && !c.pre && !c.generic && blk && cluster_pass_fused(s, rq.count);
+    // The integer SLIC path on the block / 32-bit kernels resets the assignment plane lazily (FrameDev::fv_mod): the LAB kernel then
+    // writes 4 B/px instead of 6; every other path -- variants, generic kernel, preemptive mode -- has the plane filled by the LAB kernel.
+    // ... except under the fused cluster pass (launches that do not fill the chip: one or two frames per group): there every block drains
+    // its label stores before it counts itself in, and stores into a plane the LAB kernel has just written find their lines in the
+    // memory-side cache -- without the fill each of the ten launches of a one-frame group takes 0.35 us longer (8.54 against 8.18 us,
+    // same-box A/B, profiles/r06_experiments.txt) for the 0.6 us the LAB kernel saves once.
+    c.lazy_labels = slic && !c.generic && !c.pre && !c.fused;
+    // Label-free group (DESIGN.md "Deferred labels"; FrameDev::fv_mod): the subsampled passes store no labels, the full pass defines the
+    // whole plane.
+    c.label_free = c.lazy_labels && rq.allow_label_free && label_free_allowed(s) && p.max_iter >= 1 && !s.recording && blk;
+    assert(!(c.fused && c.lazy_labels));      // (the fused loop knows no first visits: first_visit_rule)
+    return c;
+}
 
 // enforce_connectivity's minimum component size of the slot's current call, src/context.cpp:14-20
 static int min_size_threshold(const Slot& s) { return (int)round((double)(s.S * s.S) * (double)s.p.min_size_factor); }
@@ -267,34 +310,104 @@ static RecLayout rec_layout(const Slot& s) {
     return L;
 }
 
-// Device half: everything of iterate() for frames [i0, i0+n) of the slot's current group, enqueued asynchronously on
-// the slot's stream: LAB, the first cluster pass (reads the staged centres), the assign/update loop, full assign,
-// connectivity, export of the cluster state.  Pure
-// stream work with no per-call values in any launch argument (caller pointers sit in the device pointer table, bin
-// generations come from device memory), so the same sequence can be recorded once as a graph and replayed (launch_group).
-// store_labels: never the label-free passes (a frame redone because of kFlagUncoveredPixel).
-int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool timed, bool separate_cluster_pass = false, bool store_labels = false) {
-    const fslic_params* p = &s.p;
-    const int K = s.K, S = s.S;
-    hipEvent_t* const ev = s.pin().ev;
-    FrameDev f = s.f;
-    f.rgbs = nullptr;
-    f.select(i0);                                  // host-side: pointers of frame i0
-    f.rgbs = reinterpret_cast<const uint8_t* const*>(s.d_ptrs + i0);
-    const size_t fb = s.frame_bytes;
+// ---- the device half of a group: enqueue_frames and its steps ----
+#define FSLIC_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)
 
-    // copies the graph recorder has no node for (launch.h): such a group is always enqueued directly
-    // the (2S+1)^2 patch of the generic kernel: also where a preemptive Slic group falls back to that kernel for its subsampled passes
-    // (geometries outside the block kernel: launch_assign_pre returns false)
-    const bool need_patch = generic || (p->preemptive != 0 && p->variant == FSLIC_VARIANT_SLIC && !blk_kernel_applies(f, p->subsample_stride));
-    if ((p->preemptive != 0 || p->variant == FSLIC_VARIANT_REALDIST_NOQ || (need_patch && !s.sp_patch_uploaded)) && recording_unsupported()) return FSLIC_OK;
-    if (need_patch && !s.sp_patch_uploaded) {
+// Which frames of the slot's current group a call of enqueue_frames serves, and whether it brackets the phases with event records.
+struct FramesRequest {
+    int first = 0, count = 0;
+    bool timed = false;
+};
+static FramesRequest frames(int first, int count) { FramesRequest rq; rq.first = first; rq.count = count; return rq; }
+static FramesRequest timed_frames(int first, int count) { FramesRequest rq = frames(first, count); rq.timed = true; return rq; }
+
+// What the steps of one enqueue_frames call share.
+struct Enqueue {
+    Slot& s;
+    const PassChoice c;
+    const int i0, n;
+    const bool timed;
+    FrameDev f;                      // the working copy every launch takes by value: frame i0's pointers, the pass's buffers and stamps
+    LscDev l;
+    // positions: the uploaded centres are in yx_up (s.f.cl_yx); every cluster pass reads one buffer and writes the other
+    uint32_t *yx_up = nullptr, *yx_a = nullptr, *yx_b = nullptr;   // this frame's cl_yx, d_yx_alt[0], d_yx_alt[1]
+    uint32_t* yx_cur = nullptr;      // where the last cluster pass put them
+    int rem = 0;                     // the residue of the next subsampled pass's rows
+    RecLayout rl{};                  // debug_mode: the snapshot ring
+    float noq_coef = 0.0f, pre_l1_thres = 0.0f;
+};
+
+// FrameDev::fv_mod's rule (kernels.h) for a pass of the integer SLIC path on the block / 32-bit kernels: subsampled pass `it`, or the
+// full pass (kFullPass).  The fused loop and the other families keep (0, 0): their plane is filled by the LAB kernel.
+constexpr int kFullPass = -1;
+static void first_visit_rule(FrameDev& f, const PassChoice& c, const fslic_params& p, int it) {
+    const int stride = p.subsample_stride;
+    if (it != kFullPass) {
+        f.fv_mod = c.lazy_labels && it < stride ? 1 : 0; f.fv_from = 0;       // all of its rows, while the residues are new
+    } else if (c.label_free) {
+        // no pass has written the plane, EVERY row is a first visit; an uncovered pixel gets its 0xFFFF -- the plane is defined before the
+        // connectivity kernels run -- and flags the frame
+        f.fv_mod = 1; f.fv_from = 0;
+    } else {
+        // the rows of the residues no subsampled pass came to are first looked at by the full pass
+        f.fv_mod = c.lazy_labels && p.max_iter < stride ? stride : 0; f.fv_from = p.max_iter < stride ? std::max(p.max_iter, 0) : 0;
+    }
+    f.fv_rcp = f.fv_mod > 1 ? 0xFFFFFFFFu / (uint32_t)f.fv_mod : 0u;
+}
+
+// debug_mode: snapshot `idx` (iteration idx - 1) of the label plane and the cluster state into the ring; rec_dist(idx) is the
+// snapshot's distance plane, which the recording assign kernels write
+static void* rec_dist(const Enqueue& q, int idx) { return q.c.rec ? q.s.d_rec + q.rl.dist_off + (size_t)idx * q.rl.N * q.rl.dsize : nullptr; }
+static int snapshot(const Enqueue& q, int idx, const uint32_t* yx) {
+    Slot& s = q.s;
+    const FrameDev& f = q.f;
+    const RecLayout& rl = q.rl;
+    const int K = s.K;
+    HIPCHK(hipMemcpyAsync(s.d_rec + (size_t)idx * rl.N * 2, f.labels, rl.N * 2, hipMemcpyDeviceToDevice, s.st));
+    uint32_t* c = reinterpret_cast<uint32_t*>(s.d_rec + rl.cl_off) + (size_t)idx * kRecWords * K;
+    const size_t kb = sizeof(uint32_t) * (size_t)K;
+    HIPCHK(hipMemcpyAsync(c, yx, kb, hipMemcpyDeviceToDevice, s.st));
+    HIPCHK(hipMemcpyAsync(c + K, f.cl_lab, kb, hipMemcpyDeviceToDevice, s.st));
+    HIPCHK(hipMemcpyAsync(c + 2 * (size_t)K, f.cl_n, kb, hipMemcpyDeviceToDevice, s.st));
+    HIPCHK(hipMemcpyAsync(c + 3 * (size_t)K, f.cl_moved, kb, hipMemcpyDeviceToDevice, s.st));
+    if (q.c.pre) {
+        HIPCHK(hipMemcpyAsync(c + 4 * (size_t)K, f.cl_upd, kb, hipMemcpyDeviceToDevice, s.st));
+        HIPCHK(hipMemcpyAsync(c + 5 * (size_t)K, f.cl_act, kb, hipMemcpyDeviceToDevice, s.st));
+    }
+    if (q.c.noq) HIPCHK(hipMemcpyAsync(c + 6 * (size_t)K, f.cl_f, 8 * kb, hipMemcpyDeviceToDevice, s.st));
+    return FSLIC_OK;
+}
+
+// The scaffolding of a subsampled pass, the same in the four loops.  assign_mark: per-launch timing, the event before (edge 0) and
+// after (edge 1) the assign launch of pass `it`.  flip_positions: the coming cluster pass reads the current buffer and writes the other.
+// end_pass: the cluster pass has been enqueued -- its output is current, the recorder takes its snapshot, the next pass's rows.
+static int assign_mark(const Enqueue& q, int it, int edge) {
+    if (q.timed && q.s.launch_timing && it < Slot::kMaxTimedIters) HIPCHK(hipEventRecord(q.s.ev_it[2 * it + edge], q.s.st));
+    return FSLIC_OK;
+}
+static void flip_positions(Enqueue& q) { q.f.cl_yx = q.yx_cur; q.f.cl_yx_out = (q.yx_cur == q.yx_a) ? q.yx_b : q.yx_a; }
+static int end_pass(Enqueue& q, int it) {
+    q.yx_cur = q.f.cl_yx_out;
+    if (q.c.rec) FSLIC_TRY(snapshot(q, it + 1, q.yx_cur));
+    q.rem = (q.rem + 1) % q.s.p.subsample_stride;
+    return FSLIC_OK;
+}
+
+// Patch upload, the preemptive and 'noq' initial state, LAB, the first cluster pass (reads the staged centres), the LSC prepare and the
+// recorder's first snapshot.
+static int prologue(fslic_engine* e, Enqueue& q) {
+    Slot& s = q.s;
+    const PassChoice& c = q.c;
+    const fslic_params& p = s.p;
+    FrameDev& f = q.f;
+    const int K = s.K, S = s.S, i0 = q.i0, n = q.n;
+    hipEvent_t* const ev = s.pin().ev;
+    if (c.need_patch && !s.sp_patch_uploaded) {
         HIPCHK(hipMemcpyAsync(s.d_patch, s.h_patch, (size_t)(2 * S + 1) * (2 * S + 1) * sizeof(uint16_t), hipMemcpyHostToDevice, s.st));
         s.sp_patch_uploaded = true;
     }
     // cluster centres: staged by stage_group() into the pinned block the first cluster pass reads (no copy command)
-    const bool pre = p->preemptive != 0;
-    if (pre) {
+    if (c.pre) {
         // PreemptiveGrid::initialize, src/preemptive.h:59-67: every counter = cooldown, everything active
         uint32_t* base = s.at(s.d_pre, i0);
         f.cl_upd = base; f.cl_act = base + K; f.cell_act = base + 2 * (size_t)K; f.pre_flags = f.cell_act + (size_t)f.pre_cw * f.pre_ch;
@@ -304,205 +417,218 @@ int enqueue_frames(fslic_engine* e, Slot& s, int i0, int n, bool generic, bool t
             HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(bz + 2 * (size_t)K + (size_t)f.pre_cw * f.pre_ch), 1, 1, s.st));   // all_active
         }
     }
-    const bool noq = p->variant == FSLIC_VARIANT_REALDIST_NOQ;
-    if (noq) {
+    if (c.noq) {
         f.cl_f = s.at(s.d_clf, i0);
-        HIPCHK(hipMemcpy2DAsync(f.cl_f, fb, s.h_clf + (size_t)i0 * 8 * K, sizeof(float) * 8 * (size_t)K,
+        HIPCHK(hipMemcpy2DAsync(f.cl_f, s.frame_bytes, s.h_clf + (size_t)i0 * 8 * K, sizeof(float) * 8 * (size_t)K,
                                 sizeof(float) * 8 * (size_t)K, (size_t)n, hipMemcpyHostToDevice, s.st));
     }
     // sums, bin counters, flags and cl_n / cl_moved start from zero: cleared by the LAB kernel below (two memset launches less)
 
-    if (timed) HIPCHK(hipEventRecord(ev[0], s.st));
-    // + labels <- 0xFFFF (src/context.cpp:138-145); + a fresh range of bin generation stamps for this group's passes
+    if (q.timed) HIPCHK(hipEventRecord(ev[0], s.st));
+    // + labels <- 0xFFFF (src/context.cpp:138-145) unless they are reset lazily; + a fresh range of bin generation stamps for this group's passes
     f.gen_base = s.d_gen;
-    // (the integer SLIC path on the block / 32-bit kernels resets the assignment plane lazily, FrameDev::fv_mod: the LAB kernel then writes
-    // 4 B/px instead of 6; every other path -- variants, generic kernel, preemptive mode -- has the plane filled here)
-    // ... except where the cluster pass is fused into the assign kernel (launches that do not fill the chip: one or two frames per group):
-    // there every block drains its label stores before it counts itself in, and stores into a plane the LAB kernel has just written
-    // find their lines in the memory-side cache -- without the fill each of the ten launches of a one-frame group takes 0.35 us longer
-    // (8.54 against 8.18 us, same-box A/B, profiles/r06_experiments.txt) for the 0.6 us the LAB kernel saves once.
-    const bool fusebin = cluster_pass_fused(f, *p, n, s.W, s.H, generic, separate_cluster_pass);      // (see the fused loop below)
-    const bool lazy_labels = p->variant == FSLIC_VARIANT_SLIC && !generic && p->preemptive == 0 && !fusebin;
-    // Label-free group (DESIGN.md "Deferred labels"; FrameDev::fv_mod): the subsampled passes store no labels, the full pass defines the
-    // whole plane.  The ONE place where this is decided; what it depends on beyond the launch arguments (the slot's sticky fallback,
-    // label_free_allowed) is part of the graph key.
-    const bool label_free = lazy_labels && !store_labels && label_free_allowed(s) && p->max_iter >= 1 && !s.recording && blk_kernel_applies(f, p->subsample_stride);
-    launch_rgb_to_lab(f, n, p->convert_to_lab, e->tables, !lazy_labels, s.st, s.gen_step,
+    launch_rgb_to_lab(f, n, p.convert_to_lab, e->tables, !c.lazy_labels, s.st, s.gen_step,
                       s.at(s.zero_block, i0), s.zero_bytes, f.cl_n, 2 * (size_t)K,
                       reinterpret_cast<const uint32_t* const*>(s.d_ptrs + kPtrStage), (size_t)i0 * 4 * K, 4 * (size_t)K);      // (+ the staged centres -> cl_yx)
-    if (timed) HIPCHK(hipEventRecord(ev[1], s.st));
+    if (q.timed) HIPCHK(hipEventRecord(ev[1], s.st));
     f.gen_off = 1;
-    PassGeom pg{};
-    // positions: the uploaded centres are in s.f.cl_yx; every cluster pass reads one buffer and writes the other
-    uint32_t* const yx_up = f.cl_yx;
-    uint32_t* const yx_a = yx_up + 6 * (size_t)K;       // this frame's d_yx_alt[0]
-    uint32_t* const yx_b = yx_up + 7 * (size_t)K;       // this frame's d_yx_alt[1]
-    f.cl_yx = yx_up; f.cl_yx_out = yx_a;
-    const int stride = p->subsample_stride;
-    const bool lsc = p->variant == FSLIC_VARIANT_LSC;
-    launch_bin_clusters(f, n, 0, 0, 0, pg, s.st);      // (the centres are in cl_yx: copied from the host's staging block by the LAB kernel)
-    uint32_t* yx_cur = yx_a;
-    int rem = 0;
-    LscDev l = s.l;
-    if (lsc) {
-        l.select(i0);
+    f.cl_yx = q.yx_up; f.cl_yx_out = q.yx_a;
+    launch_bin_clusters(f, n, 0, 0, 0, PassGeom{}, s.st);      // (the centres are in cl_yx: copied from the host's staging block by the LAB kernel)
+    q.yx_cur = q.yx_a;
+    if (c.lsc) {
+        q.l.select(i0);
         HIPCHK(clear_rows(s.lsc_zero + (size_t)i0 * s.lsc_frame_bytes, s.lsc_frame_bytes, s.lsc_zero_bytes, (size_t)n, s.st));
-        launch_lsc_prepare(f, l, n, s.st);                        // before_iteration, src/lsc.cpp:12-15
+        launch_lsc_prepare(f, q.l, n, s.st);                      // before_iteration, src/lsc.cpp:12-15
     }
-    // debug_mode: snapshot `idx` (iteration idx - 1) of the label plane and the cluster state into the ring; `dist(idx)` is the
-    // snapshot's distance plane, which the recording assign kernels write
-    const bool rec = s.recording && n == 1;
-    const RecLayout rl = rec ? rec_layout(s) : RecLayout{};
-    auto rec_dist = [&](int idx) -> void* { return rec ? s.d_rec + rl.dist_off + (size_t)idx * rl.N * rl.dsize : nullptr; };
-    auto snapshot = [&](int idx, const uint32_t* yx) -> int {
-        HIPCHK(hipMemcpyAsync(s.d_rec + (size_t)idx * rl.N * 2, f.labels, rl.N * 2, hipMemcpyDeviceToDevice, s.st));
-        uint32_t* c = reinterpret_cast<uint32_t*>(s.d_rec + rl.cl_off) + (size_t)idx * kRecWords * K;
-        const size_t kb = sizeof(uint32_t) * (size_t)K;
-        HIPCHK(hipMemcpyAsync(c, yx, kb, hipMemcpyDeviceToDevice, s.st));
-        HIPCHK(hipMemcpyAsync(c + K, f.cl_lab, kb, hipMemcpyDeviceToDevice, s.st));
-        HIPCHK(hipMemcpyAsync(c + 2 * (size_t)K, f.cl_n, kb, hipMemcpyDeviceToDevice, s.st));
-        HIPCHK(hipMemcpyAsync(c + 3 * (size_t)K, f.cl_moved, kb, hipMemcpyDeviceToDevice, s.st));
-        if (pre) {
-            HIPCHK(hipMemcpyAsync(c + 4 * (size_t)K, f.cl_upd, kb, hipMemcpyDeviceToDevice, s.st));
-            HIPCHK(hipMemcpyAsync(c + 5 * (size_t)K, f.cl_act, kb, hipMemcpyDeviceToDevice, s.st));
-        }
-        if (noq) HIPCHK(hipMemcpyAsync(c + 6 * (size_t)K, f.cl_f, 8 * kb, hipMemcpyDeviceToDevice, s.st));
-        return FSLIC_OK;
-    };
-    if (rec) {
+    if (c.rec) {
         // distance planes: -1 zero, 0 .. max_iter-1 the type's maximum; cluster state zero
+        const RecLayout& rl = q.rl;
         HIPCHK(hipMemsetAsync(s.d_rec + rl.dist_off, 0, rl.N * rl.dsize, s.st));
-        if (p->max_iter > 0) {
-            if (rl.dsize == 2) HIPCHK(hipMemsetAsync(rec_dist(1), 0xFF, (size_t)p->max_iter * rl.N * 2, s.st));
-            else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)rec_dist(1), 0x7F7FFFFFu, (size_t)p->max_iter * rl.N, s.st));     // FLT_MAX
+        if (p.max_iter > 0) {
+            if (rl.dsize == 2) HIPCHK(hipMemsetAsync(rec_dist(q, 1), 0xFF, (size_t)p.max_iter * rl.N * 2, s.st));
+            else HIPCHK(hipMemsetD32Async((hipDeviceptr_t)rec_dist(q, 1), 0x7F7FFFFFu, (size_t)p.max_iter * rl.N, s.st));     // FLT_MAX
         }
         HIPCHK(hipMemsetAsync(s.d_rec + rl.cl_off, 0, rl.nsnap * kRecWords * rl.K * 4, s.st));
-        const int rc = snapshot(0, yx_up);              // after the colour fetch, the label reset and before_iteration()
-        if (rc) return rc;
+        FSLIC_TRY(snapshot(q, 0, q.yx_up));             // after the colour fetch, the label reset and before_iteration()
     }
-    const bool rd = p->variant == FSLIC_VARIANT_REALDIST || p->variant == FSLIC_VARIANT_REALDIST_L2 || noq;
-    const bool rd_l2 = p->variant == FSLIC_VARIANT_REALDIST_L2;
-    float noq_coef = 1.0f / ((float)S / p->compactness);        // src/context.cpp:463-464
-    noq_coef *= (1 << (p->convert_to_lab ? 1 : 0));
-    const bool noq_manhattan = p->manhattan_spatial_dist != 0;
-    const float pre_l1_thres = std::max(roundf(2 * S * p->preemptive_thres), 1.0f);      // src/preemptive.h:129
-    for (int it = 0; rd && it < p->max_iter; it++) {            // src/context.cpp:158-175, BaseContext<float>
-        const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
-        f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
-        float* const dist = static_cast<float*>(rec_dist(it + 1));
-        if (noq) launch_noq_assign(f, noq_coef, noq_manhattan, n, rem, stride, it & 1, it & 1, true, s.st, dist);
-        else launch_rd_assign(f, s.d_patchf, rd_l2, n, rem, stride, it & 1, it & 1, true, s.st, dist);
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
-        launch_member_sums(f, n, rem, stride, it & 1, noq ? 1 : 0, s.st);
+    return FSLIC_OK;
+}
+
+// src/context.cpp:158-175, BaseContext<float>
+static int float_distance_loop(Enqueue& q) {
+    Slot& s = q.s;
+    const PassChoice& c = q.c;
+    const fslic_params& p = s.p;
+    FrameDev& f = q.f;
+    const int n = q.n, stride = p.subsample_stride;
+    for (int it = 0; it < p.max_iter; it++) {
+        flip_positions(q);
+        FSLIC_TRY(assign_mark(q, it, 0));
+        float* const dist = static_cast<float*>(rec_dist(q, it + 1));
+        if (c.noq) launch_noq_assign(f, q.noq_coef, p.manhattan_spatial_dist != 0, n, q.rem, stride, it & 1, it & 1, true, s.st, dist);
+        else launch_rd_assign(f, s.d_patchf, c.rd_l2, n, q.rem, stride, it & 1, it & 1, true, s.st, dist);
+        FSLIC_TRY(assign_mark(q, it, 1));
+        launch_member_sums(f, n, q.rem, stride, it & 1, c.noq ? 1 : 0, s.st);
         f.gen_off++;
-        pg = PassGeom{};
-        if (pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, pre_l1_thres, s.st);      // update() + set_new_clusters(), src/context.cpp:356-387
-        else launch_bin_clusters(f, n, 1, (it + 1) & 1, it & 1, pg, s.st);
-        yx_cur = f.cl_yx_out;
-        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
-        rem = (rem + 1) % stride;
+        if (c.pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, q.pre_l1_thres, s.st);      // update() + set_new_clusters(), src/context.cpp:356-387
+        else launch_bin_clusters(f, n, 1, (it + 1) & 1, it & 1, PassGeom{}, s.st);
+        FSLIC_TRY(end_pass(q, it));
     }
-    for (int it = 0; lsc && it < p->max_iter; it++) {           // src/context.cpp:158-175 with ContextLSC's hooks
-        const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
-        f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
-        launch_lsc_assign(f, l, n, rem, stride, it & 1, it & 1, !pre, s.st, static_cast<float*>(rec_dist(it + 1)));      // (preemptive: the assignment alone, the sums follow)
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
-        if (pre) {
+    return FSLIC_OK;
+}
+
+// src/context.cpp:158-175 with ContextLSC's hooks
+static int lsc_loop(Enqueue& q) {
+    Slot& s = q.s;
+    const PassChoice& c = q.c;
+    FrameDev& f = q.f;
+    const int n = q.n, stride = s.p.subsample_stride;
+    for (int it = 0; it < s.p.max_iter; it++) {
+        flip_positions(q);
+        FSLIC_TRY(assign_mark(q, it, 0));
+        launch_lsc_assign(f, q.l, n, q.rem, stride, it & 1, it & 1, !c.pre, s.st, static_cast<float*>(rec_dist(q, it + 1)));      // (preemptive: the assignment alone, the sums follow)
+        FSLIC_TRY(assign_mark(q, it, 1));
+        if (c.pre) {
             // update() under the activity state the pass started with, set_new_clusters(), then after_update() under the new one
             // (src/context.cpp:301-387, src/preemptive.h:114-178, src/lsc.cpp:226-307): lsc.hip, "preemptive mode"
-            launch_lsc_pre_sums(f, n, rem, stride, it & 1, s.st);
+            launch_lsc_pre_sums(f, n, q.rem, stride, it & 1, s.st);
             f.gen_off++;
-            launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, pre_l1_thres, s.st);
-            launch_lsc_pre_feats(f, l, n, rem, stride, s.st);
+            launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, q.pre_l1_thres, s.st);
+            launch_lsc_pre_feats(f, q.l, n, q.rem, stride, s.st);
         } else {
             f.gen_off++;
-            pg = PassGeom{};                                          // use_slots = 0: everything is in FrameDev::sums
-            launch_bin_clusters_lsc(f, l, n, (it + 1) & 1, it & 1, s.st);   // update() sums + after_update(), re-binning: one launch
+            launch_bin_clusters_lsc(f, q.l, n, (it + 1) & 1, it & 1, s.st);   // update() sums + after_update(), re-binning: one launch (everything is in FrameDev::sums)
         }
-        yx_cur = f.cl_yx_out;
-        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
-        rem = (rem + 1) % stride;
+        FSLIC_TRY(end_pass(q, it));
     }
-    // The cluster pass between two assign passes (centroids from the sums, re-binning) is done by the assign kernel itself where
-    // the block kernel applies: its last block to deliver sums of a cluster finalises it (launch_assign_fused_bin), so the loop is
-    // max_iter launches instead of 2 * max_iter.  Positions then live in ONE buffer (yx_a, where the first cluster pass put them).
-    // Measured (profiles/r03_fused_cluster_pass.txt): one 1280x720 frame per group 168 instead of 183 us (the loop is ten launches
-    // of 9.9 us instead of twenty of 6.7 + 4.9), eight frames 315 instead of 333 us -- but the pipelined rate of 16-frame groups
-    // drops from 51.8 to 45.3 GP/s: the finaliser is a chain of dependent memory round trips at the end of every block and
-    // vector work a 1600-thread cluster pass does once.  So: fused where a launch does not fill the chip (latency-bound: the
-    // reference's own one-frame-per-call pattern), separate where it does.  FSLIC_FUSEBIN=0 / 2: never / always.
-    int full_obuf = -1;
-    for (int it = 0; fusebin && it < p->max_iter; it++) {
-        const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
-        f.cl_yx = yx_a; f.cl_yx_out = yx_a;
-        f.fv_mod = lazy_labels && it < stride ? 1 : 0; f.fv_from = 0;
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
-        launch_assign_fused_bin(f, n, rem, stride, it, s.st);
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
+    return FSLIC_OK;
+}
+
+// The cluster pass between two assign passes (centroids from the sums, re-binning) is done by the assign kernel itself where
+// the block kernel applies: its last block to deliver sums of a cluster finalises it (launch_assign_fused_bin), so the loop is
+// max_iter launches instead of 2 * max_iter.  Positions then live in ONE buffer (yx_a, where the first cluster pass put them).
+// Measured (profiles/r03_fused_cluster_pass.txt): one 1280x720 frame per group 168 instead of 183 us (the loop is ten launches
+// of 9.9 us instead of twenty of 6.7 + 4.9), eight frames 315 instead of 333 us -- but the pipelined rate of 16-frame groups
+// drops from 51.8 to 45.3 GP/s: the finaliser is a chain of dependent memory round trips at the end of every block and
+// vector work a 1600-thread cluster pass does once.  So: fused where a launch does not fill the chip (latency-bound: the
+// reference's own one-frame-per-call pattern), separate where it does.  FSLIC_FUSEBIN=0 / 2: never / always.
+// Pass `it` reads spill list it % 3 and appends to (it + 1) % 3, which is the list the full pass reads (full_pass).
+static int fused_slic_loop(Enqueue& q) {
+    Slot& s = q.s;
+    FrameDev& f = q.f;
+    for (int it = 0; it < s.p.max_iter; it++) {
+        f.cl_yx = q.yx_a; f.cl_yx_out = q.yx_a;
+        FSLIC_TRY(assign_mark(q, it, 0));
+        launch_assign_fused_bin(f, q.n, q.rem, s.p.subsample_stride, it, s.st);
+        FSLIC_TRY(assign_mark(q, it, 1));
         f.gen_off++;
-        yx_cur = yx_a;
-        rem = (rem + 1) % stride;
-        full_obuf = (it + 1) % 3;
+        FSLIC_TRY(end_pass(q, it));
     }
-    if (fusebin && full_obuf < 0) full_obuf = 0;
-    for (int it = 0; !fusebin && !lsc && !rd && it < p->max_iter; it++) {   // src/context.cpp:158-175
-        pg = PassGeom{};
-        const bool tme = timed && s.launch_timing && it < Slot::kMaxTimedIters;
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it], s.st));
+    return FSLIC_OK;
+}
+
+// src/context.cpp:158-175: the assign launch (which still sees the previous pass's buffers in f), then the flip and the cluster pass
+static int slic_loop(Enqueue& q) {
+    Slot& s = q.s;
+    const PassChoice& c = q.c;
+    FrameDev& f = q.f;
+    const int n = q.n, stride = s.p.subsample_stride;
+    for (int it = 0; it < s.p.max_iter; it++) {
+        PassGeom pg{};
+        FSLIC_TRY(assign_mark(q, it, 0));
         // (preemptive mode: the block kernel on the bins of the active clusters where the geometry takes it, round 5; until then the
         // generic kernel served every preemptive frame)
-        f.fv_mod = lazy_labels && it < stride ? 1 : 0; f.fv_from = 0;
-        if (rec) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st, static_cast<uint16_t*>(rec_dist(it + 1)));     // (rec: generic)
-        else if (generic || (pre && !launch_assign_pre(f, n, rem, stride, it & 1, it & 1, s.st))) launch_assign_generic(f, n, rem, stride, it & 1, it & 1, true, s.st);
-        else if (!pre) pg = launch_assign(f, n, rem, stride, it & 1, it & 1, true, s.st, -1, label_free);
-        if (tme) HIPCHK(hipEventRecord(s.ev_it[2 * it + 1], s.st));
+        first_visit_rule(f, c, s.p, it);
+        if (c.rec) launch_assign_generic(f, n, q.rem, stride, it & 1, it & 1, true, s.st, static_cast<uint16_t*>(rec_dist(q, it + 1)));     // (rec: generic)
+        else if (c.generic || (c.pre && !launch_assign_pre(f, n, q.rem, stride, it & 1, it & 1, s.st))) launch_assign_generic(f, n, q.rem, stride, it & 1, it & 1, true, s.st);
+        else if (!c.pre) pg = launch_assign(f, n, q.rem, stride, it & 1, it & 1, true, s.st, -1, c.label_free);
+        FSLIC_TRY(assign_mark(q, it, 1));
         f.gen_off++;
-        f.cl_yx = yx_cur; f.cl_yx_out = (yx_cur == yx_a) ? yx_b : yx_a;
-        if (pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, pre_l1_thres, s.st);     // update() + set_new_clusters()
+        flip_positions(q);
+        if (c.pre) launch_preempt_update(f, n, (it + 1) & 1, it & 1, false, q.pre_l1_thres, s.st);     // update() + set_new_clusters()
         else launch_bin_clusters(f, n, 1, (it + 1) & 1, it & 1, pg, s.st);
-        yx_cur = f.cl_yx_out;
-        if (rec) { const int rc = snapshot(it + 1, yx_cur); if (rc) return rc; }
-        rem = (rem + 1) % stride;
+        FSLIC_TRY(end_pass(q, it));
     }
-    int full_buf = p->max_iter & 1;
-    if (pre) {       // PreemptiveGrid::finalize (src/preemptive.h:69-74): every cluster takes part in the full assignment
-        f.gen_off++;
-        f.cl_yx = yx_cur;
-        launch_preempt_update(f, n, (p->max_iter + 1) & 1, 0, true, pre_l1_thres, s.st);
-        full_buf = (p->max_iter + 1) & 1;
-    }
-    if (timed) HIPCHK(hipEventRecord(ev[2], s.st));
-    // (lazy reset: the rows of the residues no subsampled pass came to are first looked at by the full pass)
-    f.fv_mod = lazy_labels && p->max_iter < stride ? stride : 0; f.fv_from = p->max_iter < stride ? std::max(p->max_iter, 0) : 0;
-    // (label-free group: no pass has written the plane, EVERY row is a first visit; an uncovered pixel gets its 0xFFFF -- the plane is
-    // defined before the connectivity kernels run -- and flags the frame)
-    if (label_free) { f.fv_mod = 1; f.fv_from = 0; }
-    f.fv_rcp = f.fv_mod > 1 ? 0xFFFFFFFFu / (uint32_t)f.fv_mod : 0u;
-    // full_assign: stride 1, rem 0, no update afterwards (src/context.cpp:246-256)
-    if (lsc) { f.cl_yx = yx_cur; launch_lsc_assign(f, l, n, 0, 1, full_buf, 0, false, s.st); }
-    else if (noq) { f.cl_yx = yx_cur; launch_noq_assign(f, noq_coef, noq_manhattan, n, 0, 1, full_buf, 0, false, s.st); }
-    else if (rd) { f.cl_yx = yx_cur; launch_rd_assign(f, s.d_patchf, rd_l2, n, 0, 1, full_buf, 0, false, s.st); }
-    else if (generic) launch_assign_generic(f, n, 0, 1, full_buf, 0, false, s.st);
-    else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf, label_free);      // (full_buf: the bins of all clusters; max_iter & 1 unless preemptive)
-    if (timed) HIPCHK(hipEventRecord(ev[3], s.st));
+    return FSLIC_OK;
+}
+
+// PreemptiveGrid::finalize (src/preemptive.h:69-74): every cluster takes part in the full assignment
+static void preemptive_finalise(Enqueue& q) {
+    q.f.gen_off++;
+    q.f.cl_yx = q.yx_cur;
+    launch_preempt_update(q.f, q.n, (q.s.p.max_iter + 1) & 1, 0, true, q.pre_l1_thres, q.s.st);
+}
+
+// full_assign: stride 1, rem 0, no update afterwards (src/context.cpp:246-256)
+static void full_pass(Enqueue& q) {
+    Slot& s = q.s;
+    const PassChoice& c = q.c;
+    const fslic_params& p = s.p;
+    FrameDev& f = q.f;
+    const int n = q.n;
+    const int full_buf = (p.max_iter + (c.pre ? 1 : 0)) & 1;      // the bins of all clusters: the finalise has written one set more
+    const int full_obuf = c.fused ? p.max_iter % 3 : -1;          // the spill list the fused loop's last pass appended to
+    first_visit_rule(f, c, p, kFullPass);
+    if (c.lsc) { f.cl_yx = q.yx_cur; launch_lsc_assign(f, q.l, n, 0, 1, full_buf, 0, false, s.st); }
+    else if (c.noq) { f.cl_yx = q.yx_cur; launch_noq_assign(f, q.noq_coef, p.manhattan_spatial_dist != 0, n, 0, 1, full_buf, 0, false, s.st); }
+    else if (c.rd) { f.cl_yx = q.yx_cur; launch_rd_assign(f, s.d_patchf, c.rd_l2, n, 0, 1, full_buf, 0, false, s.st); }
+    else if (c.generic) launch_assign_generic(f, n, 0, 1, full_buf, 0, false, s.st);
+    else (void)launch_assign(f, n, 0, 1, full_buf, 0, false, s.st, full_obuf, c.label_free);
+}
+
+// Connectivity, with the cluster state, overflow flag and connectivity status back to the host: the last kernel of the connectivity
+// pass writes them into the pinned blocks of the group's set, which it finds in the pointer table (three 2-D copy commands per group
+// before: blit kernels with their own barriers).  The status words are final once the select kernel has run, the cluster state
+// since the loop ended.  Then the copies back of the variants' own state.
+static int connectivity_and_export(Enqueue& q) {
+    Slot& s = q.s;
+    const int K = s.K, i0 = q.i0, n = q.n;
+    const size_t fb = s.frame_bytes;
     const CcaDev c = cca_view(s, i0, s.f.labels, fb, K, min_size_threshold(s));
-    // cluster state, overflow flag and connectivity status back to the host: the last kernel of the connectivity pass
-    // writes them into the pinned blocks of the group's set, which it finds in the pointer table (three 2-D copy commands per group
-    // before: blit kernels with their own barriers).  The status words are final once the select kernel has run, the cluster state
-    // since the loop ended.
     ExportDev ex{};
-    ex.frame_bytes = fb; ex.K = K; ex.yx_cur = yx_cur; ex.lab_n_moved = yx_up + K; ex.misc0 = s.at(s.d_misc, i0);
+    ex.frame_bytes = fb; ex.K = K; ex.yx_cur = q.yx_cur; ex.lab_n_moved = q.yx_up + K; ex.misc0 = s.at(s.d_misc, i0);
     ex.tab = reinterpret_cast<uint32_t* const*>(s.d_ptrs + kPtrExport);      // [0] kPtrExport, [1] kPtrStatus
     ex.h_off = (size_t)i0 * 4 * K; ex.h_stride = 4 * (size_t)K; ex.misc_off = (size_t)kStatusWords * i0;
     cca_enqueue(s, c, i0, n, &ex);
-    if (timed) HIPCHK(hipEventRecord(ev[4], s.st));
-    if (pre) HIPCHK(hipMemcpy2DAsync(s.h_upd + (size_t)i0 * K, sizeof(uint32_t) * (size_t)K, f.cl_upd, fb,
-                                     sizeof(uint32_t) * (size_t)K, (size_t)n, hipMemcpyDeviceToHost, s.st));
-    if (noq) HIPCHK(hipMemcpy2DAsync(s.h_clf + (size_t)i0 * 8 * K, sizeof(float) * 8 * (size_t)K, f.cl_f, fb,
-                                     sizeof(float) * 8 * (size_t)K, (size_t)n, hipMemcpyDeviceToHost, s.st));
+    if (q.timed) HIPCHK(hipEventRecord(s.pin().ev[4], s.st));
+    if (q.c.pre) HIPCHK(hipMemcpy2DAsync(s.h_upd + (size_t)i0 * K, sizeof(uint32_t) * (size_t)K, q.f.cl_upd, fb,
+                                         sizeof(uint32_t) * (size_t)K, (size_t)n, hipMemcpyDeviceToHost, s.st));
+    if (q.c.noq) HIPCHK(hipMemcpy2DAsync(s.h_clf + (size_t)i0 * 8 * K, sizeof(float) * 8 * (size_t)K, q.f.cl_f, fb,
+                                         sizeof(float) * 8 * (size_t)K, (size_t)n, hipMemcpyDeviceToHost, s.st));
     return FSLIC_OK;
+}
+
+// Device half: everything of iterate() for the frames `rq` names of the slot's current group, on the passes `c` (choose_passes),
+// enqueued asynchronously on the slot's stream.  Pure stream work with no per-call values in any launch argument (caller pointers sit
+// in the device pointer table, bin generations come from device memory), so the same sequence can be recorded once as a graph and
+// replayed (launch_group).
+static int enqueue_frames(fslic_engine* e, Slot& s, const PassChoice& c, const FramesRequest& rq) {
+    const fslic_params& p = s.p;
+    // copies the graph recorder has no node for (launch.h): such a group is always enqueued directly
+    if ((c.pre || c.noq || (c.need_patch && !s.sp_patch_uploaded)) && recording_unsupported()) return FSLIC_OK;
+    Enqueue q{s, c, rq.first, rq.count, rq.timed, s.f, s.l};
+    if (c.rec) q.rl = rec_layout(s);
+    q.f.rgbs = nullptr;
+    q.f.select(rq.first);                          // host-side: pointers of frame `first`
+    q.f.rgbs = reinterpret_cast<const uint8_t* const*>(s.d_ptrs + rq.first);
+    q.yx_up = q.f.cl_yx;
+    q.yx_a = q.yx_up + 6 * (size_t)s.K;
+    q.yx_b = q.yx_up + 7 * (size_t)s.K;
+    q.noq_coef = 1.0f / ((float)s.S / p.compactness);        // src/context.cpp:463-464
+    q.noq_coef *= (1 << (p.convert_to_lab ? 1 : 0));
+    q.pre_l1_thres = std::max(roundf(2 * s.S * p.preemptive_thres), 1.0f);      // src/preemptive.h:129
+    hipEvent_t* const ev = s.pin().ev;
+
+    FSLIC_TRY(prologue(e, q));
+    if (c.rd) FSLIC_TRY(float_distance_loop(q));
+    else if (c.lsc) FSLIC_TRY(lsc_loop(q));
+    else if (c.fused) FSLIC_TRY(fused_slic_loop(q));
+    else FSLIC_TRY(slic_loop(q));
+    if (c.pre) preemptive_finalise(q);
+    if (rq.timed) HIPCHK(hipEventRecord(ev[2], s.st));
+    full_pass(q);
+    if (rq.timed) HIPCHK(hipEventRecord(ev[3], s.st));
+    return connectivity_and_export(q);
 }
 
 GraphRecorder*& current_recorder() {
@@ -510,9 +636,12 @@ GraphRecorder*& current_recorder() {
     return rec;
 }
 
-// The device half of a group start, replayed from a graph when this exact sequence has been seen before.
-int launch_group(fslic_engine* e, Slot& s, int n) {
+// The device half of a group start, replayed from a graph when this exact sequence has been seen before.  `c`: the passes it chose.
+static int launch_group(fslic_engine* e, Slot& s, int n, PassChoice& c) {
     s.last_launch_mode = 0;
+    ChoiceRequest want;
+    want.count = n;
+    c = choose_passes(s, want);
     {   // Bin slots are validated by a u32 generation stamp; a group uses max_iter + 3 consecutive values above the base
         // (device word *d_gen, mirrored here).  Long before it could wrap, start over: stamps and base back to zero.
         // The base moves past the stamps of the PREVIOUS group at the start of this one (a group of fewer iterations after one
@@ -530,15 +659,14 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
     // Per-launch timing wants real event records between the launches; events replayed inside a graph keep the time
     // stamps of an earlier execution.  Timed groups therefore take the direct path.
     // (debug_mode: the recording path, always direct)
-    if (s.recording) return enqueue_frames(e, s, 0, n, s.generic, true, true);
-    if (!knobs().use_graphs || s.launch_timing) return enqueue_frames(e, s, 0, n, s.generic, true);
-    // everything a launch argument can depend on
+    if (s.recording || !knobs().use_graphs || s.launch_timing) return enqueue_frames(e, s, c, timed_frames(0, n));
+    // everything a launch argument can depend on, and the choice of the passes itself
     std::vector<unsigned char> key;
     auto put = [&](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; key.insert(key.end(), b, b + bytes); };
-    const int hdr[9] = {s.H, s.W, s.K, s.S, n, s.generic ? 1 : 0, (int)s.gen_step, s.sp_patch_uploaded ? 1 : 0, label_free_allowed(s) ? 1 : 0};
+    const int hdr[7] = {s.H, s.W, s.K, s.S, n, (int)s.gen_step, s.sp_patch_uploaded ? 1 : 0};
     // (the pinned blocks of the group's set are not among them: the kernels read their addresses from the pointer table, one sequence serves both sets)
     const void* const ptrs[7] = {s.d_ptrs, s.h_patch, s.d_gen, s.lsc_zero, s.d_patchf, s.h_clf, s.h_upd};   // baked into copy nodes / arguments
-    put(hdr, sizeof hdr); put(ptrs, sizeof ptrs); put(&s.p, sizeof s.p); put(&s.f, sizeof s.f); put(&s.c, sizeof s.c);
+    put(hdr, sizeof hdr); put(&c, sizeof c); put(ptrs, sizeof ptrs); put(&s.p, sizeof s.p); put(&s.f, sizeof s.f); put(&s.c, sizeof s.c);
     if (s.p.variant == FSLIC_VARIANT_LSC) put(&s.l, sizeof s.l);
     Slot::GraphEntry* ge = nullptr;
     for (auto& g : s.graphs) if (g.key == key) { ge = &g; break; }
@@ -558,19 +686,19 @@ int launch_group(fslic_engine* e, Slot& s, int n) {
         s.store_seen_credit = false;
     }
     if (!ge->exec) {
-        if (ge->failed || ge->seen++ == 0) return enqueue_frames(e, s, 0, n, s.generic, true);   // first sighting: direct (also warms one-time setup)
+        if (ge->failed || ge->seen++ == 0) return enqueue_frames(e, s, c, timed_frames(0, n));   // first sighting: direct (also warms one-time setup)
         // second sighting: the same calls with a recorder current on this thread build the graph, node by node (launch.h)
         GraphRecorder rec;
-        if (hipGraphCreate(&rec.graph, 0) != hipSuccess) { ge->failed = true; (void)hipGetLastError(); return enqueue_frames(e, s, 0, n, s.generic, true); }
+        if (hipGraphCreate(&rec.graph, 0) != hipSuccess) { ge->failed = true; (void)hipGetLastError(); return enqueue_frames(e, s, c, timed_frames(0, n)); }
         current_recorder() = &rec;
-        const int rc = enqueue_frames(e, s, 0, n, s.generic, false);     // no event records inside the graph
+        const int rc = enqueue_frames(e, s, c, frames(0, n));     // no event records inside the graph
         current_recorder() = nullptr;
         if (rc != FSLIC_OK || rec.err != hipSuccess || rec.nodes == 0 || hipGraphInstantiate(&ge->exec, rec.graph, nullptr, nullptr, 0) != hipSuccess) {
             hipGraphDestroy(rec.graph);
             ge->exec = nullptr; ge->failed = true;
             (void)hipGetLastError();
             if (rc != FSLIC_OK) return rc;
-            return enqueue_frames(e, s, 0, n, s.generic, true);
+            return enqueue_frames(e, s, c, timed_frames(0, n));
         }
         ge->graph = rec.graph;
         s.last_launch_mode = 1;
@@ -608,7 +736,7 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     s.par ^= 1;                      // the other set: the previous group may still be running on its own (a slot thread's successor)
     s.H = H; s.W = W; s.K = K; s.S = S; s.p = *p; s.nframes = n;
     // the sticky fallback of the label-free passes belongs to one work
-    if (s.store_labels && !(H == s.store_H && W == s.store_W && K == s.store_K && memcmp(&s.store_p, p, sizeof(fslic_params)) == 0)) { s.store_labels = false; s.store_seen_credit = false; }
+    if (s.store_labels && !same_work(s.store_work, job)) { s.store_labels = false; s.store_seen_credit = false; }
     std::copy(job.clusters, job.clusters + n, s.clusters);
     rc = configure_spatial(s, S, p);
     if (rc) return rc;
@@ -636,13 +764,14 @@ int group_begin(fslic_engine* e, Slot& s, const GroupJob& job, bool record) {
     s.generic = p->variant == FSLIC_VARIANT_SLIC && (e->lab_force_generic.load() != 0 || !s.sp_tiled_ok || record);
     if (p->preemptive && (rc = s.h_upd.reserve((size_t)s.cap_frames * K))) return rc;
     stage_group(e, s, 0, n, true);
-    rc = launch_group(e, s, n);
+    PassChoice choice{};
+    rc = launch_group(e, s, n, choice);
     if (rc) return rc;
     if (debug_fail_here(e, s, 1)) return fail(FSLIC_E_INTERNAL, "testing aid: group_begin failed after it enqueued the group");
     s.have_pre = true;
     s.last_path = s.generic ? 1 : 0;
     InFlight& g = s.fl[s.par];
-    g.job = job; g.S = S; g.par = s.par; g.generic = s.generic; g.launch_mode = s.last_launch_mode;
+    g.job = job; g.S = S; g.par = s.par; g.choice = choice; g.launch_mode = s.last_launch_mode;
     g.t_begun_us = now_us();
     if (knobs().host_timing) {
         fprintf(stderr, "[fslic host] group_begin n=%d: %.1f us | slot %d begin %.1f .. %.1f\n", n, now_us() - t_begin, (int)(&s - e->slots.data()), t_begin, now_us());
@@ -761,7 +890,7 @@ int group_wait(Slot& s, InFlight& g, bool successor) {
 bool group_needs_host(const Slot& s, const InFlight& g) {
     for (int i = 0; i < g.job.n; i++) {
         const uint32_t* hm = status(s, g.par, i);
-        if (hm[kStSelect] == kSelectHost || (!g.generic && hm[kStFlags] != 0)) return true;
+        if (hm[kStSelect] == kSelectHost || (!g.choice.generic && hm[kStFlags] != 0)) return true;
     }
     return false;
 }
@@ -773,9 +902,21 @@ int make_current(Slot& s, const InFlight& g) {
     const GroupJob& j = g.job;
     s.par = g.par;
     s.H = j.H; s.W = j.W; s.K = j.K; s.S = g.S; s.p = j.p; s.nframes = j.n;
-    s.generic = g.generic; s.recording = false;
+    s.generic = g.choice.generic; s.recording = false;
     std::copy(j.clusters, j.clusters + j.n, s.clusters);
     return upload_ptrs(s, j.n, j.d_rgb, j.d_out);
+}
+
+// Frame `i` of the slot's current group once more, alone and to completion, on the passes `c`: from the caller's Cluster[K] block, with
+// generation stamps past those of the pass just made (same span).
+static int redo_frame(fslic_engine* e, Slot& s, int i, const PassChoice& c) {
+    stage_group(e, s, i, 1, false);
+    s.gen_step = s.gen_span_prev;
+    s.gen_host += s.gen_step;
+    const int rc = enqueue_frames(e, s, c, frames(i, 1));
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s.st));
+    return FSLIC_OK;
 }
 
 int group_complete(fslic_engine* e, Slot& s, InFlight& g, bool from_scratch) {
@@ -797,13 +938,8 @@ int group_complete(fslic_engine* e, Slot& s, InFlight& g, bool from_scratch) {
         // A successor's kernels have run over the device state of this group.  A frame that only wants the host's top-K step has no
         // candidate lists left to gather: it is computed again the way the group ran it, and takes the steps below from there.
         if (from_scratch && hm[kStSelect] == kSelectHost && (s.generic || hm[kStFlags] == 0)) {
-            stage_group(e, s, i, 1, false);
-            s.gen_step = s.gen_span_prev;
-            s.gen_host += s.gen_step;
-            const bool separate = !cluster_pass_fused(s.f, s.p, n, W, H, s.generic, false);      // (the group's own choice, not a one-frame launch's)
-            const int rc = enqueue_frames(e, s, i, 1, s.generic, false, separate);
+            const int rc = redo_frame(e, s, i, g.choice);      // (the group's own choice, not a one-frame launch's)
             if (rc) return rc;
-            HIPCHK(hipStreamSynchronize(s.st));
         }
         // Flags of the tiled kernels.  kFlagStalePixel: a visited pixel that no window covered kept its label while the cluster pass was
         // fused into the assign kernel (its sums reached the owner through global atomics that nothing orders before the owner's
@@ -819,16 +955,15 @@ int group_complete(fslic_engine* e, Slot& s, InFlight& g, bool from_scratch) {
             // the flag then is a by-product, the redo is the generic one, and neither the counter nor the slot's fallback is concerned)
             if (uncovered && !overflow) {
                 if (!s.store_labels) s.store_seen_credit = true;
-                s.store_labels = true; s.store_H = H; s.store_W = W; s.store_K = K; s.store_p = s.p;
+                s.store_labels = true; s.store_work = job;
                 __atomic_fetch_add(&s.n_uncovered_redo, 1, __ATOMIC_RELAXED);      // (read by fslic_hip_uncovered_redos without the engine lock)
             }
             if (knobs().host_timing) fprintf(stderr, "[fslic host] frame %d redone with %s\n", i, overflow ? "the generic kernel (candidate-list overflow)" : uncovered ? "storing assign passes (uncovered pixel)" : "the separate cluster pass (stale pixel)");
-            stage_group(e, s, i, 1, false);
-            s.gen_step = s.gen_span_prev;                 // past the stamps of the pass just made (same span)
-            s.gen_host += s.gen_step;
-            int rc = enqueue_frames(e, s, i, 1, overflow, false, true, true);
+            // the conservative passes: separate cluster pass, storing, generic where the candidate list overflowed
+            ChoiceRequest want;
+            want.count = 1; want.force_generic = overflow; want.allow_fused = false; want.allow_label_free = false;
+            const int rc = redo_frame(e, s, i, choose_passes(s, want));
             if (rc) return rc;
-            HIPCHK(hipStreamSynchronize(s.st));
             if (overflow) {
                 if (hm[kStFlags] != 0) return fail(FSLIC_E_INTERNAL, "generic path reported a candidate overflow");
                 s.last_path = 1;

@@ -162,10 +162,6 @@ void pipeline_collect(fslic_engine* e, Slot& s, const InFlight* g, int rc, const
     }
 }
 
-bool same_work(const GroupJob& a, const GroupJob& b) {
-    return a.H == b.H && a.W == b.W && a.K == b.K && memcmp(&a.p, &b.p, sizeof(fslic_params)) == 0;
-}
-
 // caller holds e->mu: whether the submission `head` may be begun on slot `s` while `prev` is still running there.  The same work on
 // buffers that stay as they are (nothing is re-carved or re-uploaded under the running group), no per-launch timing and no recording
 // (their events and ring exist once), not the variants whose staging blocks exist once (h_upd, h_clf) -- and nobody else to take it:
