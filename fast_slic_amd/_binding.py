@@ -71,6 +71,9 @@ EXPORTS = [
     "fslic_hip_soft_assign", "fslic_hip_soft_assign_backward", "fslic_hip_soft_pool", "fslic_hip_soft_unpool", "fslic_hip_soft_dot",
     # connectivity on label tensors (fast_slic_amd/connect.py)
     "fslic_hip_connect_workspace_size", "fslic_hip_connected_components", "fslic_hip_connect_enforce",
+    # merging on the region adjacency graph (fast_slic_amd/merge.py)
+    "fslic_hip_merge_best_workspace_size", "fslic_hip_merge_best_edges", "fslic_hip_merge_components_workspace_size",
+    "fslic_hip_merge_components", "fslic_hip_merge_labels", "fslic_hip_merge_contract_accumulate",
 ]
 
 _lib = None
@@ -229,6 +232,8 @@ def load_library():
             _declare_soft(lib)
         if hasattr(lib, "fslic_hip_connect_enforce"):
             _declare_connect(lib)
+        if hasattr(lib, "fslic_hip_merge_components"):
+            _declare_merge(lib)
         _lib = lib
         return lib
 
@@ -242,6 +247,20 @@ def _declare_connect(lib):
     lib.fslic_hip_connect_enforce.argtypes = head + [i64, vp, vp, vp, sz]
     for name in ("connect_workspace_size", "connected_components", "connect_enforce"):
         getattr(lib, "fslic_hip_" + name).restype = i32
+
+
+def _declare_merge(lib):
+    """Signatures of the entry points of merging on the region adjacency graph (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    graph = [i32, vp, i32, i32, i64, vp, vp]      # device, stream, N, K, E, edge_index, offsets
+    lib.fslic_hip_merge_best_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
+    lib.fslic_hip_merge_best_edges.argtypes = graph + [vp, i32, C.c_double, vp, vp, sz]
+    lib.fslic_hip_merge_components_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
+    lib.fslic_hip_merge_components.argtypes = graph + [vp, vp, i32, vp, vp, vp, sz]
+    lib.fslic_hip_merge_labels.argtypes = [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp]
+    lib.fslic_hip_merge_contract_accumulate.argtypes = [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, sz]
+    for name in ("best_workspace_size", "best_edges", "components_workspace_size", "components", "labels", "contract_accumulate"):
+        getattr(lib, "fslic_hip_merge_" + name).restype = i32
 
 
 def _declare_crf(lib):

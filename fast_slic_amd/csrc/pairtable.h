@@ -68,11 +68,12 @@ static __device__ __forceinline__ bool pair_pass_lost(PairHeader* hdr) {
 
 // One update of frame n's table: finds or claims the slot of `key`, then adds the count and, with kSums, the C channel sums.  The
 // table is declared full -- more than half of it taken, or a probe run longer than kPairMaxProbe -- by setting the header's flag;
-// the update is then lost, and so is the whole pass (the caller starts over with a larger table).
-template <bool kSums>
+// the update is then lost, and so is the whole pass (the caller starts over with a larger table).  S: the type of the addends of
+// the sums, uint32_t (the graph's pixel tiles) or unsigned long long (merge.hip, whose addends are sums already).
+template <bool kSums, class S = uint32_t>
 static __device__ __forceinline__ void pair_table_add(PairHeader* __restrict__ hdr, uint32_t* __restrict__ tkey, uint32_t* __restrict__ tcnt,
                                                       unsigned long long* __restrict__ tsum, int n, uint32_t cap_mask, uint32_t key,
-                                                      uint32_t cnt, int C = 0, const uint32_t* s = nullptr) {
+                                                      uint32_t cnt, int C = 0, const S* s = nullptr) {
     const size_t base = (size_t)n * ((size_t)cap_mask + 1);
     uint32_t h = pair_hash(key) & cap_mask;
     for (uint32_t probe = 0; probe <= min(cap_mask, kPairMaxProbe); ++probe) {

@@ -481,6 +481,45 @@ int fslic_hip_connected_components(int device, void* stream, int N, int H, int W
 int fslic_hip_connect_enforce(int device, void* stream, int N, int H, int W, const void* labels, int label_type, long long min_size,
                               int32_t* out, int32_t* counts, void* workspace, size_t workspace_bytes);
 
+/* ---- Merging on the region adjacency graph (NEW surface; Python: fast_slic_amd/merge.py, which states the rules) ----
+ * A graph is what fslic_hip_rag_compact delivers once sorted: N frames of K nodes (K in [1, 65534], N * K < 2^31) and E < 2^31 edges,
+ *   edge_index : int64 [2][E], row 0 the node a and row 1 the node b of every edge        offsets : int64 [N + 1]
+ * the edges of frame f at [offsets[f], offsets[f + 1]); the position of an edge is its index minus offsets[f].  Entries as for
+ * pooling: a device index and a stream, no synchronisation, no allocation, no copy to the host, the caller's device restored, every
+ * argument checked before the first HIP call (FSLIC_E_INVALID).  What the device arrays hold is checked by the kernels before it
+ * becomes an index: an edge with a node outside [0, K) takes part in nothing, and the frame of an edge is found by a search in
+ * offsets[1 .. N] whose result is a frame whatever they hold.  All integer arithmetic and comparison: exact, the same from run to run.
+ *
+ * Best edges.  weight : float [E], >= 0 (-0.0 counts as +0.0; NaN or negative values leave the result unspecified).  An edge is
+ * eligible if has_threshold == 0 or weight < threshold; a node's best edge is the eligible edge at it with the smallest
+ * (weight, position); join[e] (uint8, 0 or 1) says whether e is the best edge of at least one of its nodes.  The workspace holds
+ * 8 N K bytes (one 64-bit key per node) and needs no clearing.  E == 0: nothing is launched. */
+int fslic_hip_merge_best_workspace_size(int N, int K, size_t* bytes);
+int fslic_hip_merge_best_edges(int device, void* stream, int N, int K, long long E, const int64_t* edge_index, const int64_t* offsets,
+                               const float* weight, int has_threshold, double threshold, uint8_t* join, void* workspace,
+                               size_t workspace_bytes);
+/* Components.  A node is present if members is NULL or members[n][v] > 0 (members_type FSLIC_LABEL_I32 or FSLIC_LABEL_I64).  Groups
+ * are the connected components of a frame's present nodes under the edges with join[e] != 0 whose two nodes are present; a group's
+ * leader is its smallest node; groups are numbered 0, 1, ... in ascending leader order.  mapping[n][v] (int32 [N][K]) = the number of
+ * v's group, -1 for an absent node; counts[n] (int32 [N]) = the groups of frame n.  The workspace holds two uint32 planes of N K words
+ * and 4 bytes per 256 nodes of a frame (each part rounded up to 16 bytes) and needs no clearing.  Six launches whatever the graph. */
+int fslic_hip_merge_components_workspace_size(int N, int K, size_t* bytes);
+int fslic_hip_merge_components(int device, void* stream, int N, int K, long long E, const int64_t* edge_index, const int64_t* offsets,
+                               const uint8_t* join, const void* members, int members_type, int32_t* mapping, int32_t* counts,
+                               void* workspace, size_t workspace_bytes);
+/* Labels.  out[n][p] (int32 [N][H][W], 4-byte aligned, overlapping nothing) = mapping[n][labels[n][p]] for a label in [0, K), -1 for
+ * any other.  labels : [N][H][W] of label_type (FSLIC_LABEL_*), N * H * W < 2^31, at any alignment of its type. */
+int fslic_hip_merge_labels(int device, void* stream, int N, int H, int W, int K, const void* labels, int label_type,
+                           const int32_t* mapping, int32_t* out);
+/* Contraction.  Clears the workspace of a label pair table (the graph's: fslic_hip_rag_workspace_size(N, K2, C, capacity)), then for
+ * every edge (a, b) of frame n with a' = mapping[n][a] and b' = mapping[n][b] both in [0, K2) and different adds boundary[e] (int32)
+ * and the row contrast[e][C] (int64; NULL with C == 0) to the pair (min(a', b'), max(a', b')).  The header is the graph's, and so is
+ * the way out: fslic_hip_rag_compact on the same stream, and a larger capacity after an overflow (2 * min(K2 (K2 - 1) / 2, E) pairs
+ * rounded up to a power of two always suffice for the load). */
+int fslic_hip_merge_contract_accumulate(int device, void* stream, int N, int K, int K2, long long E, const int64_t* edge_index,
+                                        const int64_t* offsets, const int32_t* boundary, const int64_t* contrast, int C,
+                                        const int32_t* mapping, long long capacity, void* workspace, size_t workspace_bytes);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
