@@ -74,6 +74,8 @@ EXPORTS = [
     # merging on the region adjacency graph (fast_slic_amd/merge.py)
     "fslic_hip_merge_best_workspace_size", "fslic_hip_merge_best_edges", "fslic_hip_merge_components_workspace_size",
     "fslic_hip_merge_components", "fslic_hip_merge_labels", "fslic_hip_merge_contract_accumulate",
+    # the features of merged regions (fast_slic_amd/regions.py)
+    "fslic_hip_region_sums_workspace_size", "fslic_hip_region_sums", "fslic_hip_region_edge_weights",
 ]
 
 _lib = None
@@ -234,6 +236,8 @@ def load_library():
             _declare_connect(lib)
         if hasattr(lib, "fslic_hip_merge_components"):
             _declare_merge(lib)
+        if hasattr(lib, "fslic_hip_region_sums"):
+            _declare_region(lib)
         _lib = lib
         return lib
 
@@ -261,6 +265,16 @@ def _declare_merge(lib):
     lib.fslic_hip_merge_contract_accumulate.argtypes = [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, sz]
     for name in ("best_workspace_size", "best_edges", "components_workspace_size", "components", "labels", "contract_accumulate"):
         getattr(lib, "fslic_hip_merge_" + name).restype = i32
+
+
+def _declare_region(lib):
+    """Signatures of the entry points of the features of merged regions (include/fslic_hip.h)."""
+    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
+    lib.fslic_hip_region_sums_workspace_size.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.fslic_hip_region_sums.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz]
+    lib.fslic_hip_region_edge_weights.argtypes = [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp]
+    for name in ("sums_workspace_size", "sums", "edge_weights"):
+        getattr(lib, "fslic_hip_region_" + name).restype = i32
 
 
 def _declare_crf(lib):

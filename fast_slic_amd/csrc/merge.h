@@ -19,6 +19,18 @@ namespace fslic {
 constexpr int kMergeChunk = 256;                     // nodes of one block of the rank passes
 constexpr uint32_t kMergeAbsent = 0xFFFFFFFFu;       // the parent word of a node that is in no group
 
+// (kernels of merge.hip and region.hip) The frame of edge e: how many of offsets[1 .. N] are <= e
+// (torch.searchsorted(offsets[1:], e, right=True)), at most N - 1.
+static __device__ __forceinline__ int frame_of(const long long* __restrict__ offsets, int N, long long e) {
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid + 1] <= e) lo = mid + 1;
+        else hi = mid;
+    }
+    return min(lo, N - 1);
+}
+
 inline size_t merge_align(size_t b) { return (b + 15) & ~(size_t)15; }
 inline size_t merge_chunks_per_frame(int K) { return ((size_t)K + kMergeChunk - 1) / kMergeChunk; }
 inline size_t merge_best_workspace_bytes(int N, int K) { return (size_t)N * (size_t)K * 8; }

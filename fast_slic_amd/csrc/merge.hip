@@ -32,17 +32,6 @@ static_assert((65534 + kMergeChunk - 1) / kMergeChunk <= 256, "k_merge_scan: the
 static __device__ __forceinline__ uint32_t ld_now(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 static __device__ __forceinline__ void st_now(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// The frame of edge e: how many of offsets[1 .. N] are <= e (torch.searchsorted(offsets[1:], e, right=True)), at most N - 1.
-static __device__ __forceinline__ int frame_of(const long long* __restrict__ offsets, int N, long long e) {
-    int lo = 0, hi = N;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid + 1] <= e) lo = mid + 1;
-        else hi = mid;
-    }
-    return min(lo, N - 1);
-}
-
 static inline dim3 merge_grid(unsigned long long items, unsigned long long per_block) {
     const int g = tile_grid(items, per_block);
     assert(g >= 1 && (unsigned long long)g < (1ull << 24));

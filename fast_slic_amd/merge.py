@@ -25,8 +25,9 @@
    field for field (edge_index, boundary, contrast, offsets).  K2 is the caller's bound on n, passed on without reading n back.
 
 Out of scope: the sequential priority-queue order of skimage's merge_hierarchical (the parallel round above is the semantics);
-float sums of group features (re-pool from the pixels for reproducible bits); gradients; 8- versus 4-connectivity, which is the
-graph's business.
+gradients; 8- versus 4-connectivity, which is the graph's business.  Reproducible float sums of group features, the weights from
+them and the whole loop are regions.py's (group_sums, edge_weights, merge_hierarchical); equality of those sums with a re-pool from
+the pixels holds for counts and exactly representable sums only, since pooled node sums are already rounded.
 
 The work runs on torch's current stream of the graph's (the map's) device and scratch memory comes from torch's caching allocator;
 results live on that GPU.  best_neighbour_edges, merge_components, merge_labels and compose_mappings do not synchronise the host;

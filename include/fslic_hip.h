@@ -520,6 +520,29 @@ int fslic_hip_merge_contract_accumulate(int device, void* stream, int N, int K, 
                                         const int64_t* offsets, const int32_t* boundary, const int64_t* contrast, int C,
                                         const int32_t* mapping, long long capacity, void* workspace, size_t workspace_bytes);
 
+/* ---- The features of merged regions (NEW surface; Python: fast_slic_amd/regions.py, which states the rules) ----
+ * Entries as for merging: a device index and a stream, no synchronisation, no allocation, no copy to the host, the caller's device
+ * restored, every argument checked before the first HIP call (FSLIC_E_INVALID); what the device arrays hold is checked by the kernels
+ * before it becomes an index.  N frames, C >= 1 channels, K and K2 in [1, 65534], N * C * K and N * C * K2 below 2^31.
+ *
+ * Group sums.  sums[n][c][g] (float [N][C][K2]) = the sum of values[n][c][v] (float [N][C][K]) over the nodes v with
+ * mapping[n][v] == g (int32 [N][K]); a mapping word outside [0, K2) adds nothing.  Each value is truncated towards zero to a multiple
+ * of 2^-96, the values are added exactly (the fixed-point accumulator of fslic_hip_pool, integer atomics), and the total is rounded
+ * once to float, ties to even: the same bits whatever the order.  No value, or a zero total: +0.0.  A NaN or Inf value leaves its
+ * group's entry unspecified.  counts (NULL, or [N][K] of counts_type FSLIC_LABEL_I32 or FSLIC_LABEL_I64) is added likewise into
+ * counts_out ([N][K2] of the same type; NULL exactly when counts is), with wrapping integer atomics.  The workspace holds
+ * 56 N C K2 bytes (seven 64-bit words per sum); the entry clears it, and counts_out, itself.  Two launches. */
+int fslic_hip_region_sums_workspace_size(int N, int C, int K2, size_t* bytes);
+int fslic_hip_region_sums(int device, void* stream, int N, int C, int K, int K2, const float* values, const int32_t* mapping,
+                          const void* counts, int counts_type, float* sums, void* counts_out, void* workspace, size_t workspace_bytes);
+/* Edge weights of a graph (edge_index, offsets, E as for merging) from sums (float [N][C][K]) and counts ([N][K] of counts_type).
+ * For the edge (a, b) of frame n: na = (float)counts[n][a], d_c = sums[n][c][a] / na - sums[n][c][b] / nb, s = the d_c * d_c added in
+ * ascending c; mode 0 (mean): weight = sqrt(s); mode 1 (ward): weight = ((na * nb) / (na + nb)) * s.  Every operation is one IEEE
+ * float operation rounded on its own, nothing fused, division and square root correctly rounded.  +inf where a or b is outside
+ * [0, K) or a count is <= 0.  One launch, no workspace; E == 0: nothing is launched. */
+int fslic_hip_region_edge_weights(int device, void* stream, int N, int C, int K, long long E, const int64_t* edge_index,
+                                  const int64_t* offsets, const float* sums, const void* counts, int counts_type, int mode, float* weight);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
