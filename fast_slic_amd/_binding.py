@@ -37,7 +37,7 @@ class Params(C.Structure):
 
 
 EXPORTS = [
-    "fslic_hip_device_count", "fslic_hip_create", "fslic_hip_destroy", "fslic_hip_initialize_clusters",
+    "fslic_hip_device_count", "fslic_hip_create", "fslic_hip_destroy", "fslic_hip_initialize_clusters", "fslic_hip_seed_positions",
     "fslic_hip_iterate", "fslic_hip_iterate_device", "fslic_hip_iterate_batch", "fslic_hip_submit_group",
     "fslic_hip_wait_group", "fslic_hip_rgb_to_lab",
     "fslic_hip_enforce_connectivity", "fslic_hip_enforce_connectivity_nodes", "fslic_hip_last_prelabels", "fslic_hip_last_timing_report",
@@ -76,6 +76,8 @@ EXPORTS = [
     "fslic_hip_merge_components", "fslic_hip_merge_labels", "fslic_hip_merge_contract_accumulate",
     # the features of merged regions (fast_slic_amd/regions.py)
     "fslic_hip_region_sums_workspace_size", "fslic_hip_region_sums", "fslic_hip_region_edge_weights",
+    # frames of any tensor layout into the engine's form (fast_slic_amd/frames.py)
+    "fslic_hip_pack_rgb",
 ]
 
 _lib = None
@@ -238,8 +240,19 @@ def load_library():
             _declare_merge(lib)
         if hasattr(lib, "fslic_hip_region_sums"):
             _declare_region(lib)
+        if hasattr(lib, "fslic_hip_pack_rgb"):
+            _declare_frames(lib)
         _lib = lib
         return lib
+
+
+def _declare_frames(lib):
+    """Signatures of the entry points of Slic on torch tensors (include/fslic_hip.h)."""
+    vp, i32 = C.c_void_p, C.c_int
+    lib.fslic_hip_seed_positions.argtypes = [i32, i32, i32, vp]
+    lib.fslic_hip_pack_rgb.argtypes = [i32, vp, i32, i32, i32, vp, i32, C.POINTER(C.c_longlong), C.c_float, vp, C.c_size_t]
+    for name in ("seed_positions", "pack_rgb"):
+        getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _declare_connect(lib):
@@ -803,18 +816,22 @@ class SlicModel(object):
         H, W = a.shape
         return self._engine.cluster_density_to_mask(a.view(np.uint16), d, H, W)
 
-    def iterate(self, image, max_iter, compactness, min_size_factor, subsample_stride):   # pyx:150-260
-        if not self.initialized:
-            raise RuntimeError("Slic model is not initialized")                    # pyx:151-152
-        image = self._check_image(image)
+    def iterate_params(self, max_iter, compactness, min_size_factor, subsample_stride):
+        """The fslic_params of an iterate() call with this model's options and variant (iterate below; frames.slic_tensor)."""
         variant = VARIANT_SLIC
         if self.real_dist:                                                         # pyx:198-235
             if self.real_dist_type not in _REAL_DIST_VARIANTS:
                 raise RuntimeError("No such real_dist_type " + repr(self.real_dist_type))      # pyx:236
             variant = _REAL_DIST_VARIANTS[self.real_dist_type]
-        p = make_params(max_iter, compactness, min_size_factor, subsample_stride, self.convert_to_lab,
-                        self.manhattan_spatial_dist, self.preemptive, self.preemptive_thres,
-                        self.num_threads, self.debug_mode, variant)
+        return make_params(max_iter, compactness, min_size_factor, subsample_stride, self.convert_to_lab,
+                           self.manhattan_spatial_dist, self.preemptive, self.preemptive_thres,
+                           self.num_threads, self.debug_mode, variant)
+
+    def iterate(self, image, max_iter, compactness, min_size_factor, subsample_stride):   # pyx:150-260
+        if not self.initialized:
+            raise RuntimeError("Slic model is not initialized")                    # pyx:151-152
+        image = self._check_image(image)
+        p = self.iterate_params(max_iter, compactness, min_size_factor, subsample_stride)
         labels = self._engine.iterate(image, self._clusters, p)
         self.last_timing_report = self._engine.last_timing_report()
         self.last_recorder_report = self._engine.last_recorder_report()     # bytes, after every call (pyx:196, :256)

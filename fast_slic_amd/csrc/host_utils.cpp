@@ -13,9 +13,11 @@ using namespace fslic;
 
 extern "C" {
 
-// BaseContext::initialize_clusters, src/context.cpp:42-97 (host, serial, O(K)).
-int fslic_hip_initialize_clusters(int H, int W, int K, const uint8_t* rgb, fslic_cluster* cl) {
-    if (!rgb || !cl) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+// The image-free part of BaseContext::initialize_clusters, src/context.cpp:42-97 (host, serial, O(K)): the seed grid, `number`, the
+// flags and num_members = 0; r, g, b are set to 0.  A caller whose frame lives in device memory reads the K seed pixels there
+// (fast_slic_amd/frames.py).
+int fslic_hip_seed_positions(int H, int W, int K, fslic_cluster* cl) {
+    if (!cl) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (H <= 0 || W <= 0 || K <= 0) return FSLIC_OK;   // the reference returns silently (:43)
     const int n_y = (int)sqrt((double)K);
     std::vector<int> n_xs(n_y, K / n_y);
@@ -45,12 +47,23 @@ int fslic_hip_initialize_clusters(int H, int W, int K, const uint8_t* rgb, fslic
         cl[acc].x = (float)(W / 2);
     }
     for (int k = 0; k < K; k++) {
+        cl[k].r = cl[k].g = cl[k].b = 0.0f;
+        cl[k].number = (uint16_t)k;
+        cl[k].num_members = 0;
+    }
+    return FSLIC_OK;
+}
+
+// BaseContext::initialize_clusters, src/context.cpp:42-97: the seeds above, each with the colour of its pixel.
+int fslic_hip_initialize_clusters(int H, int W, int K, const uint8_t* rgb, fslic_cluster* cl) {
+    if (!rgb || !cl) return fail(FSLIC_E_INVALID, "NULL pointer argument");
+    const int rc = fslic_hip_seed_positions(H, W, K, cl);
+    if (rc || H <= 0 || W <= 0 || K <= 0) return rc;
+    for (int k = 0; k < K; k++) {
         const size_t base = (size_t)W * (int)cl[k].y + (int)cl[k].x;
         cl[k].r = rgb[3 * base];
         cl[k].g = rgb[3 * base + 1];
         cl[k].b = rgb[3 * base + 2];
-        cl[k].number = (uint16_t)k;
-        cl[k].num_members = 0;
     }
     return FSLIC_OK;
 }

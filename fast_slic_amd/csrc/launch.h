@@ -47,23 +47,35 @@ static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsig
     add_kernel_node(*r, reinterpret_cast<void*>(kernel), grid, block, shmem, a, std::index_sequence_for<KArgs...>{});
 }
 
+// One 256-thread block per item for item counts the runtime cannot launch at once (soft.h has the rule and why; ingest.h follows it): the
+// launch goes out in slices of at most kMaxLaunchBlocks blocks, in order on the stream, each with the flat index of its first block as the
+// kernel's last argument.  Below that count there is one launch.
+constexpr unsigned long long kMaxLaunchBlocks = (1ull << 24) - 1ull;     // 2^32 - 256 threads: the largest launch the runtime supports
+template <typename... KArgs, typename... Args>
+static inline void launch_sliced(void (*kernel)(KArgs...), unsigned long long blocks, hipStream_t st, Args... args) {
+    for (unsigned long long first = 0; first < blocks; first += kMaxLaunchBlocks) {
+        const unsigned long long nb = blocks - first < kMaxLaunchBlocks ? blocks - first : kMaxLaunchBlocks;
+        launch(kernel, dim3((uint32_t)nb), dim3(256), 0, st, args..., (uint32_t)first);
+    }
+}
+
 // Blocks of a grid-stride kernel over `items` of which a block takes `per_block` a round: enough for one round, at most 32 a CU.
 static inline int tile_grid(unsigned long long items, unsigned long long per_block) {
     const unsigned long long want = (items + per_block - 1) / per_block;
     return (int)(want < 1ull ? 1ull : want > 256ull * 32ull ? 256ull * 32ull : want);
 }
 
-// Row-wise clear (hipMemset2DAsync on the stream, a memset node in the graph).
+// Row-wise clear of `rows` rows of `width_bytes` at `pitch` (both multiples of 4, dst 4-byte aligned; the LSC accumulators): a kernel, on
+// the stream and as a node of the graph alike.  It was hipMemset2DAsync / a memset node until a one-frame LSC group over device pointers,
+// replayed by one slot, came back from its third replay with the result of accumulators that had not been cleared (measured on the
+// MI355X, every time, 61 x 83 K = 20; groups of several frames and the direct path never did): tests/test_gpu_frames.py.
+static __global__ void k_clear_rows(uint32_t* dst, size_t pitch_words, uint32_t width_words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < width_words) dst[(size_t)blockIdx.y * pitch_words + i] = 0u;
+}
 static inline hipError_t clear_rows(void* dst, size_t pitch, size_t width_bytes, size_t rows, hipStream_t st) {
-    GraphRecorder* r = current_recorder();
-    if (!r) return hipMemset2DAsync(dst, pitch, 0, width_bytes, rows, st);
-    if (r->err != hipSuccess) return hipSuccess;
-    hipMemsetParams m{};
-    m.dst = dst; m.pitch = pitch; m.value = 0; m.elementSize = 1; m.width = width_bytes; m.height = rows;
-    hipGraphNode_t node = nullptr;
-    const hipError_t e = hipGraphAddMemsetNode(&node, r->graph, r->last ? &r->last : nullptr, r->last ? 1 : 0, &m);
-    if (e != hipSuccess) { r->err = e; return hipSuccess; }
-    r->chain(node);
+    const uint32_t words = (uint32_t)(width_bytes / 4);
+    launch(k_clear_rows, dim3((words + 255u) / 256u, (uint32_t)rows), dim3(256), 0, st, static_cast<uint32_t*>(dst), pitch / 4, words);
     return hipSuccess;
 }
 

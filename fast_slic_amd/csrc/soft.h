@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include "launch.h"
 
 namespace fslic {
 
@@ -23,7 +24,7 @@ constexpr int kSoftMaxK = 65534;
 // returns hipSuccess and runs b mod 2^24 of them, so the rest of the output stays unwritten.  The launches of soft.hip therefore go
 // out in slices of at most kSoftMaxBlocks blocks, in order on the stream, each with the flat index of its first block as the kernel's
 // last argument: a block computes what it would in one launch, bit for bit, and below 2^24 blocks there is one launch as before.
-constexpr unsigned long long kSoftMaxBlocks = (1ull << 24) - 1ull;     // 2^32 - 256 threads: the largest launch the runtime supports
+constexpr unsigned long long kSoftMaxBlocks = kMaxLaunchBlocks;        // 2^32 - 256 threads: the largest launch the runtime supports (launch.h)
 
 // d_j = sum_c (F[c][p] - S[c][k_j])^2 in ascending c; Q_j = exp(-(d_j - min d)) / sum over the valid slots
 void launch_soft_assign(const float* feat, const float* centres, float* q, int N, int C, int H, int W, int gh, int gw, hipStream_t st);

@@ -238,15 +238,8 @@ __global__ __launch_bounds__(256) void k_soft_pool(const float* __restrict__ fea
 }
 
 // ---- launches (the entries of softapi.cpp have checked every argument: N * ceil(H W / 256) and the pool items are below 2^31) ----
-// One block per item, issued in slices of at most kSoftMaxBlocks blocks (soft.h has the rule and why).  A kernel's last argument is
-// the flat index of its slice's first block, so every block computes exactly what it would in a single launch.
-template <typename... KArgs, typename... Args>
-static void launch_sliced(void (*kernel)(KArgs...), unsigned long long blocks, hipStream_t st, Args... args) {
-    for (unsigned long long first = 0; first < blocks; first += kSoftMaxBlocks) {
-        const unsigned long long nb = blocks - first < kSoftMaxBlocks ? blocks - first : kSoftMaxBlocks;
-        launch(kernel, dim3((uint32_t)nb), dim3(256), 0, st, args..., (uint32_t)first);
-    }
-}
+// One block per item, issued through launch_sliced (launch.h; soft.h has the rule and why): a kernel's last argument is the flat index of
+// its slice's first block, so every block computes exactly what it would in a single launch.
 
 #define SOFT_PIXEL_GRID()                                                  \
     const uint32_t HW = (uint32_t)H * (uint32_t)W, bpf = (HW + 255u) / 256u; \

@@ -94,6 +94,10 @@ void fslic_hip_destroy(fslic_engine* e);
  * SlicModel.initialize (cfast_slic.pyx:124-147).  Pure host code, O(K); `rgb` is a host pointer
  * to C-contiguous uint8[H][W][3]. */
 int fslic_hip_initialize_clusters(int H, int W, int K, const uint8_t* rgb, fslic_cluster* clusters);
+/* The part of it that needs no image (NEW surface): the seed grid, `number`, the flags and num_members = 0, with r, g, b set to 0.
+ * fslic_hip_initialize_clusters is this call plus the colours of the K seed pixels; a caller whose frames live in device memory
+ * reads those pixels there, at byte 3 * (W * (int)y + (int)x) + c of a frame (fast_slic_amd/frames.py). */
+int fslic_hip_seed_positions(int H, int W, int K, fslic_cluster* clusters);
 
 /* Replaces Context construction + initialize_state() + iterate() + delete for the integer SLIC path
  * (cfast_slic.pyx:171-197 -> src/context.cpp:108-197).
@@ -406,6 +410,21 @@ int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int r
  * out[n][c][p] = values[n][c][l] where argmax[n][c][l] == p, `fill` everywhere else. */
 int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
                      int label_type, const int32_t* argmax, float fill, float* out);
+
+/* ---- Frames of any tensor layout into the engine's form (NEW surface, no counterpart in the reference; Python: fast_slic_amd/frames.py) ----
+ * N frames of 3 channels -> uint8 [H][W][3] interleaved, what fslic_hip_iterate_batch and the other device entries read.  Entry as for
+ * pooling: a device index and a stream, no synchronisation, no allocation, the caller's device restored, every argument checked before
+ * the first HIP call (FSLIC_E_INVALID).
+ *   src     : element (n, c, y, x) at src + n * strides[0] + c * strides[1] + y * strides[2] + x * strides[3], strides in ELEMENTS of
+ *             src_type (FSLIC_PACK_*), any value, 0 included; src is aligned to its element type; H * W < 2^31
+ *   out     : frame n at out + n * pitch; pitch >= 3 H W, a multiple of 16 and at most 2^33; out is 4-byte aligned.  The bytes
+ *             [3 H W, pitch) of every frame are written as 0; nothing outside [out, out + N * pitch) is touched.
+ * A float source, per element, in float32 (float16 and bfloat16 widen exactly): v = x * scale, one rounding; NaN -> 0; clamp to
+ * [0, 255]; round to nearest, ties to even.  scale is finite.  A uint8 source is copied and scale ignored.  One launch (in slices
+ * past 2^24 - 1 blocks of 1024 pixels: N * ceil(ceil(pitch / 12) / 256) is admitted up to 2^31 - 1). */
+enum { FSLIC_PACK_U8 = 0, FSLIC_PACK_F16 = 1, FSLIC_PACK_BF16 = 2, FSLIC_PACK_F32 = 3 };
+int fslic_hip_pack_rgb(int device, void* stream, int N, int H, int W, const void* src, int src_type, const long long strides[4],
+                       float scale, uint8_t* out, size_t pitch);
 
 /* ---- Region adjacency graph of a label map (NEW surface, no counterpart in the reference; Python: fast_slic_amd/rag.py) ----
  * Every unordered pair of labels that touch, with the number of neighbouring pixel pairs across their boundary and, with an image, per
