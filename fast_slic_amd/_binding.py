@@ -36,49 +36,157 @@ class Params(C.Structure):
     ]
 
 
-EXPORTS = [
-    "fslic_hip_device_count", "fslic_hip_create", "fslic_hip_destroy", "fslic_hip_initialize_clusters", "fslic_hip_seed_positions",
-    "fslic_hip_iterate", "fslic_hip_iterate_device", "fslic_hip_iterate_batch", "fslic_hip_submit_group",
-    "fslic_hip_wait_group", "fslic_hip_rgb_to_lab",
-    "fslic_hip_enforce_connectivity", "fslic_hip_enforce_connectivity_nodes", "fslic_hip_last_prelabels", "fslic_hip_last_timing_report",
-    "fslic_hip_last_device_times", "fslic_hip_set_launch_timing", "fslic_hip_last_assign_loop", "fslic_hip_last_group_frames", "fslic_hip_last_path", "fslic_hip_last_launch_mode", "fslic_hip_group_done", "fslic_hip_last_error", "fslic_hip_version",
-    "fslic_hip_get_connectivity", "fslic_hip_knn_connectivity", "fslic_hip_get_mask_density", "fslic_hip_cluster_density_to_mask",
-    "fslic_hip_pipeline_submit", "fslic_hip_pipeline_drain", "fslic_hip_pipeline_batching", "fslic_hip_last_host_topk_frames",
-    "fslic_hip_separate_pass_redos", "fslic_hip_uncovered_redos", "fslic_hip_overlapped_groups", "fslic_hip_pipeline_overlap", "fslic_hip_copy_bandwidth", "fslic_hip_last_recorder_report",
-    "fslic_hip_debug_lsc_state", "fslic_hip_debug_forms_seen", "fslic_hip_debug_forms_all",
-    # SimpleCRF (fast_slic_amd/crf.py)
-    "fslic_hip_crf_new", "fslic_hip_crf_free", "fslic_hip_crf_copy", "fslic_hip_crf_get_params", "fslic_hip_crf_set_params",
-    "fslic_hip_crf_set_compat", "fslic_hip_crf_get_compat", "fslic_hip_crf_num_classes", "fslic_hip_crf_first_time",
-    "fslic_hip_crf_last_time", "fslic_hip_crf_num_frames", "fslic_hip_crf_pop_frame", "fslic_hip_crf_push_frame", "fslic_hip_crf_frame",
-    "fslic_hip_crf_frame_time", "fslic_hip_crf_frame_set_clusters", "fslic_hip_crf_frame_get_clusters",
-    "fslic_hip_crf_frame_set_connectivity", "fslic_hip_crf_frame_set_connectivity_csr", "fslic_hip_crf_frame_get_connectivity",
-    "fslic_hip_crf_frame_set_mask", "fslic_hip_crf_frame_set_proba", "fslic_hip_crf_frame_set_unbiased", "fslic_hip_crf_frame_set_unary",
-    "fslic_hip_crf_frame_get_unary", "fslic_hip_crf_frame_spatial_energy", "fslic_hip_crf_frame_temporal_energy",
-    "fslic_hip_crf_frame_get_inferred", "fslic_hip_crf_frame_reset_inferred", "fslic_hip_crf_initialize", "fslic_hip_crf_inference",
-    "fslic_hip_crf_expf_host", "fslic_hip_crf_expf_device",
-    # superpixel pooling (fast_slic_amd/pool.py)
-    "fslic_hip_pool_workspace_size", "fslic_hip_pool", "fslic_hip_pool_finalize", "fslic_hip_unpool",
-    # region adjacency graph (fast_slic_amd/rag.py)
-    "fslic_hip_rag_workspace_size", "fslic_hip_rag_accumulate", "fslic_hip_rag_compact",
-    # two label maps against each other (fast_slic_amd/compare.py)
-    "fslic_hip_overlap_workspace_size", "fslic_hip_overlap_accumulate", "fslic_hip_overlap_compact", "fslic_hip_boundary_match",
+def _signatures():
+    """(name, restype, argtypes) of every entry point of include/fslic_hip.h, once (tests/test_capi_cpu.py holds it against the header)."""
+    vp, i32, i64, sz, f32, f64, text = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double, C.c_char_p
+    P = C.POINTER
+    params = P(Params)
+    frames = [i32, i32, i32, i32, vp, vp, vp]      # H, W, K, n_frames, rgb, clusters, labels: one pointer array each
+    table = [
+        ("fslic_hip_device_count", i32, []),
+        ("fslic_hip_create", i32, [i32, i32, P(vp)]),
+        ("fslic_hip_destroy", None, [vp]),
+        ("fslic_hip_initialize_clusters", i32, [i32, i32, i32, vp, vp]),
+        ("fslic_hip_seed_positions", i32, [i32, i32, i32, vp]),
+        ("fslic_hip_iterate", i32, [vp, params, i32, i32, i32, vp, vp, vp]),
+        ("fslic_hip_iterate_device", i32, [vp, i32, params, i32, i32, i32, vp, vp, vp]),
+        ("fslic_hip_iterate_batch", i32, [vp, params] + frames + [i32]),
+        ("fslic_hip_submit_group", i32, [vp, i32, params] + frames),
+        ("fslic_hip_wait_group", i32, [vp, i32]),
+        ("fslic_hip_rgb_to_lab", i32, [vp, i32, i32, vp, i32, vp]),
+        ("fslic_hip_enforce_connectivity", i32, [vp, vp, i32, i32, i32, i32]),
+        ("fslic_hip_enforce_connectivity_nodes", i32, [vp, vp, i32, i32, i32, i32, P(C.c_uint32)]),
+        ("fslic_hip_last_prelabels", i32, [vp, i32, vp]),
+        ("fslic_hip_last_timing_report", text, [vp]),
+        ("fslic_hip_last_device_times", i32, [vp, i32, P(f32), P(f32)]),
+        ("fslic_hip_set_launch_timing", i32, [vp, i32]),
+        ("fslic_hip_last_assign_loop", i32, [vp, i32, P(f32), P(f64), P(i32)]),
+        ("fslic_hip_last_group_frames", i32, [vp, i32]),
+        ("fslic_hip_last_path", i32, [vp, i32]),
+        ("fslic_hip_last_launch_mode", i32, [vp, i32]),
+        ("fslic_hip_group_done", i32, [vp, i32]),
+        ("fslic_hip_last_error", text, []),
+        ("fslic_hip_version", text, []),
+        ("fslic_hip_get_connectivity", i32, [vp, i32, i32, i32, vp, vp, vp]),
+        ("fslic_hip_knn_connectivity", i32, [i32, i32, i32, vp, sz, vp, vp]),
+        ("fslic_hip_get_mask_density", i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+        ("fslic_hip_cluster_density_to_mask", i32, [vp, i32, i32, i32, vp, vp, vp]),
+        ("fslic_hip_pipeline_submit", i32, [vp, params] + frames),
+        ("fslic_hip_pipeline_drain", i32, [vp, P(f64), P(i64), P(i64), P(i64)]),
+        ("fslic_hip_pipeline_batching", i32, [vp, i32]),
+        ("fslic_hip_last_host_topk_frames", i32, [vp, i32]),
+        ("fslic_hip_separate_pass_redos", i32, [vp, i32]),
+        ("fslic_hip_uncovered_redos", i32, [vp, i32]),
+        ("fslic_hip_overlapped_groups", i64, [vp]),
+        ("fslic_hip_pipeline_overlap", i32, [vp, i32]),
+        ("fslic_hip_copy_bandwidth", i32, [vp, sz, i32, P(f64)]),
+        ("fslic_hip_last_recorder_report", i32, [vp, P(text), P(sz)]),
+        ("fslic_hip_debug_lsc_state", i32, [vp, i32, i32, i32, vp, vp]),
+        ("fslic_hip_debug_forms_seen", i32, [vp, i32, i32]),
+        ("fslic_hip_debug_forms_all", i32, [vp, i32]),
+        # SimpleCRF (fast_slic_amd/crf.py)
+        ("fslic_hip_crf_new", i32, [sz, sz, P(vp)]),
+        ("fslic_hip_crf_free", None, [vp]),
+        ("fslic_hip_crf_copy", i32, [vp, P(vp)]),
+        ("fslic_hip_crf_get_params", i32, [vp, vp]),
+        ("fslic_hip_crf_set_params", i32, [vp, vp]),
+        ("fslic_hip_crf_set_compat", i32, [vp, i32, f32]),
+        ("fslic_hip_crf_get_compat", i32, [vp, i32, P(f32)]),
+        ("fslic_hip_crf_num_classes", i32, [vp, P(sz), P(sz)]),
+        ("fslic_hip_crf_first_time", i32, [vp]),
+        ("fslic_hip_crf_last_time", i32, [vp]),
+        ("fslic_hip_crf_num_frames", sz, [vp]),
+        ("fslic_hip_crf_pop_frame", i32, [vp]),
+        ("fslic_hip_crf_push_frame", i32, [vp, P(vp)]),
+        ("fslic_hip_crf_frame", i32, [vp, i32, P(vp)]),
+        ("fslic_hip_crf_frame_time", i32, [vp]),
+        ("fslic_hip_crf_frame_set_clusters", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_get_clusters", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_set_connectivity", i32, [vp, i32, vp, vp, sz]),
+        ("fslic_hip_crf_frame_set_connectivity_csr", i32, [vp, i32, vp, vp]),
+        ("fslic_hip_crf_frame_get_connectivity", i32, [vp, vp, vp]),
+        ("fslic_hip_crf_frame_set_mask", i32, [vp, vp, f32]),
+        ("fslic_hip_crf_frame_set_proba", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_set_unbiased", i32, [vp]),
+        ("fslic_hip_crf_frame_set_unary", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_get_unary", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_spatial_energy", i32, [vp, i32, i32, P(f32)]),
+        ("fslic_hip_crf_frame_temporal_energy", i32, [vp, vp, i32, P(f32)]),
+        ("fslic_hip_crf_frame_get_inferred", i32, [vp, vp]),
+        ("fslic_hip_crf_frame_reset_inferred", i32, [vp]),
+        ("fslic_hip_crf_initialize", i32, [vp]),
+        ("fslic_hip_crf_inference", i32, [vp, vp, sz]),
+        ("fslic_hip_crf_expf_host", i32, [vp, vp, sz, i32]),
+        ("fslic_hip_crf_expf_device", i32, [vp, vp, vp, sz]),
+        # superpixel pooling (fast_slic_amd/pool.py)
+        ("fslic_hip_pool_workspace_size", i32, [i32, i32, i32, i32, P(sz)]),
+        ("fslic_hip_pool", i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, sz]),
+        ("fslic_hip_pool_finalize", i32, [i32, vp, i32, i32, i32, i32, vp, sz, vp, vp, vp]),
+        ("fslic_hip_unpool", i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, f32, vp]),
+        # region adjacency graph (fast_slic_amd/rag.py)
+        ("fslic_hip_rag_workspace_size", i32, [i32, i32, i32, i64, P(sz)]),
+        ("fslic_hip_rag_accumulate", i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]),
+        ("fslic_hip_rag_compact", i32, [i32, vp, i32, i32, i64, vp, sz, vp, vp, vp, i64]),
+        # two label maps against each other (fast_slic_amd/compare.py)
+        ("fslic_hip_overlap_workspace_size", i32, [i32, i64, P(sz)]),
+        ("fslic_hip_overlap_accumulate", i32, [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]),
+        ("fslic_hip_overlap_compact", i32, [i32, vp, i32, i64, vp, sz, vp, vp, i64]),
+        ("fslic_hip_boundary_match", i32, [i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]),
+    ]
     # SimpleCRF inference on torch tensors (fast_slic_amd/crf_torch.py)
-    "fslic_hip_crf_tensor_workspace_size", "fslic_hip_crf_tensor_inference",
-    "fslic_hip_crf_tensor_grad_workspace_size", "fslic_hip_crf_tensor_inference_saved", "fslic_hip_crf_tensor_backward",
-    "fslic_hip_crf_tensor_energies", "fslic_hip_crf_tensor_energies_backward_workspace_size", "fslic_hip_crf_tensor_energies_backward",
-    "fslic_hip_crf_tensor_inference_energies", "fslic_hip_crf_tensor_inference_saved_energies", "fslic_hip_crf_tensor_backward_energies",
+    sweep = [i32, vp, i32, i32, i32, i32, i32]      # device, stream, N, C, K, temporal, max_iter
+    inference = sweep + [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
+    inference_energies = sweep + [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, sz]
+    table += [
+        ("fslic_hip_crf_tensor_workspace_size", i32, [i32, i32, i32, i64, P(sz)]),
+        ("fslic_hip_crf_tensor_inference", i32, inference),
+        ("fslic_hip_crf_tensor_grad_workspace_size", i32, [i32, i32, i32, i64, i32, i32, P(sz)]),
+        ("fslic_hip_crf_tensor_inference_saved", i32, inference),
+        ("fslic_hip_crf_tensor_backward", i32, sweep + [vp, vp, vp, vp, vp, vp, i64] + [vp] * 10 + [sz]),
+        ("fslic_hip_crf_tensor_energies", i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]),
+        ("fslic_hip_crf_tensor_energies_backward_workspace_size", i32, [i32, i32, P(sz)]),
+        ("fslic_hip_crf_tensor_energies_backward", i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]),
+        ("fslic_hip_crf_tensor_inference_energies", i32, inference_energies),
+        ("fslic_hip_crf_tensor_inference_saved_energies", i32, inference_energies),
+        ("fslic_hip_crf_tensor_backward_energies", i32, sweep + [vp, vp, vp, vp, i64] + [vp] * 14 + [sz]),
+    ]
     # soft superpixel assignment on feature tensors (fast_slic_amd/soft.py)
-    "fslic_hip_soft_assign", "fslic_hip_soft_assign_backward", "fslic_hip_soft_pool", "fslic_hip_soft_unpool", "fslic_hip_soft_dot",
+    geom = [i32, vp, i32, i32, i32, i32, i32, i32]      # device, stream, N, C, H, W, gh, gw
+    table += [
+        ("fslic_hip_soft_assign", i32, geom + [vp, vp, vp]),
+        ("fslic_hip_soft_assign_backward", i32, geom + [vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_soft_pool", i32, geom + [vp, vp, vp, vp, vp]),
+        ("fslic_hip_soft_unpool", i32, geom + [vp, vp, vp]),
+        ("fslic_hip_soft_dot", i32, geom + [vp, vp, vp, vp]),
+    ]
     # connectivity on label tensors (fast_slic_amd/connect.py)
-    "fslic_hip_connect_workspace_size", "fslic_hip_connected_components", "fslic_hip_connect_enforce",
+    head = [i32, vp, i32, i32, i32, vp, i32]      # device, stream, N, H, W, labels, label_type
+    table += [
+        ("fslic_hip_connect_workspace_size", i32, [i32, i32, i32, P(sz)]),
+        ("fslic_hip_connected_components", i32, head + [vp, vp, vp, sz]),
+        ("fslic_hip_connect_enforce", i32, head + [i64, vp, vp, vp, sz]),
+    ]
     # merging on the region adjacency graph (fast_slic_amd/merge.py)
-    "fslic_hip_merge_best_workspace_size", "fslic_hip_merge_best_edges", "fslic_hip_merge_components_workspace_size",
-    "fslic_hip_merge_components", "fslic_hip_merge_labels", "fslic_hip_merge_contract_accumulate",
-    # the features of merged regions (fast_slic_amd/regions.py)
-    "fslic_hip_region_sums_workspace_size", "fslic_hip_region_sums", "fslic_hip_region_edge_weights",
-    # frames of any tensor layout into the engine's form (fast_slic_amd/frames.py)
-    "fslic_hip_pack_rgb",
-]
+    graph = [i32, vp, i32, i32, i64, vp, vp]      # device, stream, N, K, E, edge_index, offsets
+    table += [
+        ("fslic_hip_merge_best_workspace_size", i32, [i32, i32, P(sz)]),
+        ("fslic_hip_merge_best_edges", i32, graph + [vp, i32, f64, vp, vp, sz]),
+        ("fslic_hip_merge_components_workspace_size", i32, [i32, i32, P(sz)]),
+        ("fslic_hip_merge_components", i32, graph + [vp, vp, i32, vp, vp, vp, sz]),
+        ("fslic_hip_merge_labels", i32, [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp]),
+        ("fslic_hip_merge_contract_accumulate", i32, [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, sz]),
+        # the features of merged regions (fast_slic_amd/regions.py)
+        ("fslic_hip_region_sums_workspace_size", i32, [i32, i32, i32, P(sz)]),
+        ("fslic_hip_region_sums", i32, [i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz]),
+        ("fslic_hip_region_edge_weights", i32, [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp]),
+        # frames of any tensor layout into the engine's form (fast_slic_amd/frames.py)
+        ("fslic_hip_pack_rgb", i32, [i32, vp, i32, i32, i32, vp, i32, P(i64), f32, vp, sz]),
+    ]
+    return table
+
+
+SIGNATURES = _signatures()
+EXPORTS = [name for name, _, _ in SIGNATURES]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -169,221 +277,14 @@ def load_library():
                 "fast_slic_amd: %s is missing; build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C fast_slic_amd/csrc` (there is no CPU fallback)" % _LIB_PATH)
         lib = C.CDLL(os.environ.get("FSLIC_LIB") or _LIB_PATH)      # FSLIC_LIB: A/B a second build of the same ABI (scripts/gpu_ab.sh)
-        vp, i32 = C.c_void_p, C.c_int
-        lib.fslic_hip_device_count.restype = i32
-        lib.fslic_hip_create.argtypes = [i32, i32, C.POINTER(vp)]
-        lib.fslic_hip_destroy.argtypes = [vp]
-        lib.fslic_hip_destroy.restype = None
-        lib.fslic_hip_initialize_clusters.argtypes = [i32, i32, i32, vp, vp]
-        lib.fslic_hip_iterate.argtypes = [vp, C.POINTER(Params), i32, i32, i32, vp, vp, vp]
-        lib.fslic_hip_iterate_device.argtypes = [vp, i32, C.POINTER(Params), i32, i32, i32, vp, vp, vp]
-        lib.fslic_hip_iterate_batch.argtypes = [vp, C.POINTER(Params), i32, i32, i32, i32, vp, vp, vp, i32]
-        lib.fslic_hip_submit_group.argtypes = [vp, i32, C.POINTER(Params), i32, i32, i32, i32, vp, vp, vp]
-        lib.fslic_hip_wait_group.argtypes = [vp, i32]
-        lib.fslic_hip_pipeline_submit.argtypes = [vp, C.POINTER(Params), i32, i32, i32, i32, vp, vp, vp]
-        lib.fslic_hip_pipeline_drain.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
-        lib.fslic_hip_pipeline_batching.argtypes = [vp, i32]
-        lib.fslic_hip_last_host_topk_frames.argtypes = [vp, i32]
-        lib.fslic_hip_separate_pass_redos.argtypes = [vp, i32]
-        if hasattr(lib, "fslic_hip_uncovered_redos"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it: it has no label-free passes)
-            lib.fslic_hip_uncovered_redos.argtypes = [vp, i32]
-        if hasattr(lib, "fslic_hip_overlapped_groups"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it: its slot threads finish every group before the next)
-            lib.fslic_hip_overlapped_groups.argtypes = [vp]
-            lib.fslic_hip_overlapped_groups.restype = C.c_longlong
-            lib.fslic_hip_pipeline_overlap.argtypes = [vp, i32]
-        if hasattr(lib, "fslic_hip_copy_bandwidth"):      # (an A/B build of an earlier round, FSLIC_LIB, may lack it)
-            lib.fslic_hip_copy_bandwidth.argtypes = [vp, C.c_size_t, i32, C.POINTER(C.c_double)]
-        lib.fslic_hip_group_done.argtypes = [vp, i32]
-        lib.fslic_hip_rgb_to_lab.argtypes = [vp, i32, i32, vp, i32, vp]
-        lib.fslic_hip_enforce_connectivity.argtypes = [vp, vp, i32, i32, i32, i32]
-        if hasattr(lib, "fslic_hip_enforce_connectivity_nodes"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
-            lib.fslic_hip_enforce_connectivity_nodes.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(C.c_uint32)]
-        lib.fslic_hip_last_prelabels.argtypes = [vp, i32, vp]
-        if hasattr(lib, "fslic_hip_debug_lsc_state"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks it)
-            lib.fslic_hip_debug_lsc_state.argtypes = [vp, i32, i32, i32, vp, vp]
-        if hasattr(lib, "fslic_hip_debug_forms_seen"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks the form record)
-            lib.fslic_hip_debug_forms_seen.argtypes = [vp, i32, i32]
-            lib.fslic_hip_debug_forms_all.argtypes = [vp, i32]
-        lib.fslic_hip_last_timing_report.argtypes = [vp]
-        lib.fslic_hip_last_timing_report.restype = C.c_char_p
-        if hasattr(lib, "fslic_hip_last_recorder_report"):
-            lib.fslic_hip_last_recorder_report.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-        lib.fslic_hip_last_device_times.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        lib.fslic_hip_set_launch_timing.argtypes = [vp, i32]
-        lib.fslic_hip_last_assign_loop.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)]
-        lib.fslic_hip_last_group_frames.argtypes = [vp, i32]
-        lib.fslic_hip_last_path.argtypes = [vp, i32]
-        lib.fslic_hip_last_launch_mode.argtypes = [vp, i32]
-        if hasattr(lib, "fslic_hip_lab_force_generic"):           # testing aid, not in include/fslic_hip.h: a library given through
-            lib.fslic_hip_lab_force_generic.argtypes = [vp, i32]  # FSLIC_LIB may lack it (only the tests that use it then fail)
-        lib.fslic_hip_last_error.restype = C.c_char_p
-        lib.fslic_hip_version.restype = C.c_char_p
-        lib.fslic_hip_get_connectivity.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-        lib.fslic_hip_knn_connectivity.argtypes = [i32, i32, i32, vp, C.c_size_t, vp, vp]
-        lib.fslic_hip_get_mask_density.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
-        lib.fslic_hip_cluster_density_to_mask.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-        if hasattr(lib, "fslic_hip_crf_new"):
-            _declare_crf(lib)
-        if hasattr(lib, "fslic_hip_pool"):
-            _declare_pool(lib)
-        if hasattr(lib, "fslic_hip_rag_accumulate"):
-            _declare_rag(lib)
-        if hasattr(lib, "fslic_hip_overlap_accumulate"):
-            _declare_compare(lib)
-        if hasattr(lib, "fslic_hip_crf_tensor_inference"):
-            _declare_crf_tensor(lib)
-        if hasattr(lib, "fslic_hip_soft_assign"):
-            _declare_soft(lib)
-        if hasattr(lib, "fslic_hip_connect_enforce"):
-            _declare_connect(lib)
-        if hasattr(lib, "fslic_hip_merge_components"):
-            _declare_merge(lib)
-        if hasattr(lib, "fslic_hip_region_sums"):
-            _declare_region(lib)
-        if hasattr(lib, "fslic_hip_pack_rgb"):
-            _declare_frames(lib)
+        # A library given through FSLIC_LIB may be an older build of this ABI, without the entries added since: a name it lacks is
+        # skipped, and only the features that need it then fail.  The last row is a testing aid that is not in include/fslic_hip.h.
+        for name, restype, argtypes in SIGNATURES + [("fslic_hip_lab_force_generic", C.c_int, [C.c_void_p, C.c_int])]:
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
         return lib
-
-
-def _declare_frames(lib):
-    """Signatures of the entry points of Slic on torch tensors (include/fslic_hip.h)."""
-    vp, i32 = C.c_void_p, C.c_int
-    lib.fslic_hip_seed_positions.argtypes = [i32, i32, i32, vp]
-    lib.fslic_hip_pack_rgb.argtypes = [i32, vp, i32, i32, i32, vp, i32, C.POINTER(C.c_longlong), C.c_float, vp, C.c_size_t]
-    for name in ("seed_positions", "pack_rgb"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-
-
-def _declare_connect(lib):
-    """Signatures of the entry points of the connectivity pass on label tensors (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    head = [i32, vp, i32, i32, i32, vp, i32]      # device, stream, N, H, W, labels, label_type
-    lib.fslic_hip_connect_workspace_size.argtypes = [i32, i32, i32, C.POINTER(sz)]
-    lib.fslic_hip_connected_components.argtypes = head + [vp, vp, vp, sz]
-    lib.fslic_hip_connect_enforce.argtypes = head + [i64, vp, vp, vp, sz]
-    for name in ("connect_workspace_size", "connected_components", "connect_enforce"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-
-
-def _declare_merge(lib):
-    """Signatures of the entry points of merging on the region adjacency graph (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    graph = [i32, vp, i32, i32, i64, vp, vp]      # device, stream, N, K, E, edge_index, offsets
-    lib.fslic_hip_merge_best_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
-    lib.fslic_hip_merge_best_edges.argtypes = graph + [vp, i32, C.c_double, vp, vp, sz]
-    lib.fslic_hip_merge_components_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
-    lib.fslic_hip_merge_components.argtypes = graph + [vp, vp, i32, vp, vp, vp, sz]
-    lib.fslic_hip_merge_labels.argtypes = [i32, vp, i32, i32, i32, i32, vp, i32, vp, vp]
-    lib.fslic_hip_merge_contract_accumulate.argtypes = [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, i64, vp, sz]
-    for name in ("best_workspace_size", "best_edges", "components_workspace_size", "components", "labels", "contract_accumulate"):
-        getattr(lib, "fslic_hip_merge_" + name).restype = i32
-
-
-def _declare_region(lib):
-    """Signatures of the entry points of the features of merged regions (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    lib.fslic_hip_region_sums_workspace_size.argtypes = [i32, i32, i32, C.POINTER(sz)]
-    lib.fslic_hip_region_sums.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, sz]
-    lib.fslic_hip_region_edge_weights.argtypes = [i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp]
-    for name in ("sums_workspace_size", "sums", "edge_weights"):
-        getattr(lib, "fslic_hip_region_" + name).restype = i32
-
-
-def _declare_crf(lib):
-    """Signatures of the SimpleCRF entry points (include/fslic_hip.h)."""
-    vp, i32, sz, f32 = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-    for name, args in [
-        ("new", [sz, sz, C.POINTER(vp)]), ("copy", [vp, C.POINTER(vp)]), ("get_params", [vp, vp]), ("set_params", [vp, vp]),
-        ("set_compat", [vp, i32, f32]), ("get_compat", [vp, i32, C.POINTER(f32)]), ("num_classes", [vp, C.POINTER(sz), C.POINTER(sz)]),
-        ("first_time", [vp]), ("last_time", [vp]), ("pop_frame", [vp]), ("push_frame", [vp, C.POINTER(vp)]),
-        ("frame", [vp, i32, C.POINTER(vp)]), ("frame_time", [vp]), ("frame_set_clusters", [vp, vp]), ("frame_get_clusters", [vp, vp]),
-        ("frame_set_connectivity", [vp, i32, vp, vp, sz]), ("frame_set_connectivity_csr", [vp, i32, vp, vp]),
-        ("frame_get_connectivity", [vp, vp, vp]), ("frame_set_mask", [vp, vp, f32]), ("frame_set_proba", [vp, vp]),
-        ("frame_set_unbiased", [vp]), ("frame_set_unary", [vp, vp]), ("frame_get_unary", [vp, vp]),
-        ("frame_spatial_energy", [vp, i32, i32, C.POINTER(f32)]), ("frame_temporal_energy", [vp, vp, i32, C.POINTER(f32)]),
-        ("frame_get_inferred", [vp, vp]), ("frame_reset_inferred", [vp]), ("initialize", [vp]), ("inference", [vp, vp, sz]),
-        ("expf_host", [vp, vp, sz, i32]), ("expf_device", [vp, vp, vp, sz]),
-    ]:
-        f = getattr(lib, "fslic_hip_crf_" + name)
-        f.argtypes = args
-        f.restype = i32
-    lib.fslic_hip_crf_free.argtypes = [vp]
-    lib.fslic_hip_crf_free.restype = None
-    lib.fslic_hip_crf_num_frames.argtypes = [vp]
-    lib.fslic_hip_crf_num_frames.restype = sz
-
-
-def _declare_pool(lib):
-    """Signatures of the superpixel pooling entry points (include/fslic_hip.h)."""
-    vp, i32 = C.c_void_p, C.c_int
-    lib.fslic_hip_pool_workspace_size.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]
-    lib.fslic_hip_pool.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, C.c_size_t]
-    lib.fslic_hip_pool_finalize.argtypes = [i32, vp, i32, i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
-    lib.fslic_hip_unpool.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, C.c_float, vp]
-    for name in ("pool_workspace_size", "pool", "pool_finalize", "unpool"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-
-
-def _declare_rag(lib):
-    """Signatures of the region adjacency graph entry points (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    lib.fslic_hip_rag_workspace_size.argtypes = [i32, i32, i32, i64, C.POINTER(sz)]
-    lib.fslic_hip_rag_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
-    lib.fslic_hip_rag_compact.argtypes = [i32, vp, i32, i32, i64, vp, sz, vp, vp, vp, i64]
-    for name in ("rag_workspace_size", "rag_accumulate", "rag_compact"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-
-
-def _declare_compare(lib):
-    """Signatures of the entry points that compare two label maps (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    lib.fslic_hip_overlap_workspace_size.argtypes = [i32, i64, C.POINTER(sz)]
-    lib.fslic_hip_overlap_accumulate.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, i64, vp, sz]
-    lib.fslic_hip_overlap_compact.argtypes = [i32, vp, i32, i64, vp, sz, vp, vp, i64]
-    lib.fslic_hip_boundary_match.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
-    for name in ("overlap_workspace_size", "overlap_accumulate", "overlap_compact", "boundary_match"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-
-
-def _declare_crf_tensor(lib):
-    """Signatures of the entry points of SimpleCRF inference on device tensors (include/fslic_hip.h)."""
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t
-    lib.fslic_hip_crf_tensor_workspace_size.argtypes = [i32, i32, i32, i64, C.POINTER(sz)]
-    lib.fslic_hip_crf_tensor_inference.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
-    for name in ("crf_tensor_workspace_size", "crf_tensor_inference"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
-    if hasattr(lib, "fslic_hip_crf_tensor_backward"):      # (an A/B build of an earlier round, FSLIC_LIB, lacks the differentiable path)
-        lib.fslic_hip_crf_tensor_grad_workspace_size.argtypes = [i32, i32, i32, i64, i32, i32, C.POINTER(sz)]
-        lib.fslic_hip_crf_tensor_inference_saved.argtypes = lib.fslic_hip_crf_tensor_inference.argtypes
-        lib.fslic_hip_crf_tensor_backward.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
-                                                      vp, vp, vp, sz]
-        for name in ("crf_tensor_grad_workspace_size", "crf_tensor_inference_saved", "crf_tensor_backward"):
-            getattr(lib, "fslic_hip_" + name).restype = i32
-    if hasattr(lib, "fslic_hip_crf_tensor_energies"):      # (likewise: the energies as tensors)
-        lib.fslic_hip_crf_tensor_energies.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp]
-        lib.fslic_hip_crf_tensor_energies_backward_workspace_size.argtypes = [i32, i32, C.POINTER(sz)]
-        lib.fslic_hip_crf_tensor_energies_backward.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, sz]
-        lib.fslic_hip_crf_tensor_inference_energies.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, sz]
-        lib.fslic_hip_crf_tensor_inference_saved_energies.argtypes = lib.fslic_hip_crf_tensor_inference_energies.argtypes
-        lib.fslic_hip_crf_tensor_backward_energies.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
-                                                               vp, vp, vp, vp, vp, vp, vp, sz]
-        for name in ("energies", "energies_backward_workspace_size", "energies_backward", "inference_energies", "inference_saved_energies",
-                     "backward_energies"):
-            getattr(lib, "fslic_hip_crf_tensor_" + name).restype = i32
-
-
-def _declare_soft(lib):
-    """Signatures of the soft superpixel assignment entry points (include/fslic_hip.h)."""
-    vp, i32 = C.c_void_p, C.c_int
-    geom = [i32, vp, i32, i32, i32, i32, i32, i32]      # device, stream, N, C, H, W, gh, gw
-    lib.fslic_hip_soft_assign.argtypes = geom + [vp, vp, vp]
-    lib.fslic_hip_soft_assign_backward.argtypes = geom + [vp, vp, vp, vp, vp, vp]
-    lib.fslic_hip_soft_pool.argtypes = geom + [vp, vp, vp, vp, vp]
-    lib.fslic_hip_soft_unpool.argtypes = geom + [vp, vp, vp]
-    lib.fslic_hip_soft_dot.argtypes = geom + [vp, vp, vp, vp]
-    for name in ("soft_assign", "soft_assign_backward", "soft_pool", "soft_unpool", "soft_dot"):
-        getattr(lib, "fslic_hip_" + name).restype = i32
 
 
 def _raise(rc):

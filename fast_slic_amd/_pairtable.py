@@ -1,49 +1,15 @@
-"""What superpixel_graph (rag.py) and label_overlap (compare.py) share: the checks of a label map, the choice of the GPU, and the
-driver of the per-frame label pair table (csrc/pairtable.h) -- grow until it holds the map, read the header, compact, sort.  This
-module imports torch; the package itself does not import it."""
+"""The driver of the per-frame label pair table (csrc/pairtable.h) that superpixel_graph (rag.py), label_overlap (compare.py) and
+contract_graph (merge.py) share -- grow until it holds the map, read the header, compact, sort -- and the limits of its capacity.
+This module imports torch; the package itself does not import it."""
 import numpy as np
 import torch
 
-from .pool import _LABEL_TYPE, _NUMPY_LABELS, _check_device
-
 _HEADER_FIXED = 16          # bytes of the workspace header before the per-frame pair counts (csrc/pairtable.h)
-_MIN_CAPACITY, _MAX_CAPACITY = 64, 1 << 31
+MIN_CAPACITY, MAX_CAPACITY = 64, 1 << 31
 
 
-def _pow2_at_least(v):
+def pow2_at_least(v):
     return 1 << max(0, int(v) - 1).bit_length()
-
-
-def check_label_map(t, what):
-    if not isinstance(t, (np.ndarray, torch.Tensor)):
-        raise ValueError("%s must be a numpy array or a torch tensor" % what)
-    if t.ndim not in (2, 3):
-        raise ValueError("%s must be [H, W] or [N, H, W], got shape %s" % (what, tuple(t.shape)))
-    if 0 in t.shape:
-        raise ValueError("%s must not be empty, got shape %s" % (what, tuple(t.shape)))
-    ok = t.dtype.type in _NUMPY_LABELS if isinstance(t, np.ndarray) else t.dtype in _LABEL_TYPE
-    if not ok:
-        raise ValueError("%s must be int16 (Slic.iterate's map), int32 or int64, got %s" % (what, t.dtype))
-
-
-def pick_device(tensors, device):
-    """The GPU of the result; tensors: ((labels, "labels"), (image or None, "image")).  Torch tensors must already be there (and on
-    the same one); numpy arrays are uploaded."""
-    given = [(t, what) for t, what in tensors if isinstance(t, torch.Tensor)]
-    devs = {t.device for t, _ in given if t.device.type == "cuda"}
-    if device is not None:
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is not None:
-            devs.add(device)
-    if len(devs) > 1:
-        raise ValueError("%s and device must name one GPU, got %s" % (", ".join(what for _, what in tensors), sorted(str(d) for d in devs)))
-    for t, what in given:                          # (a CPU tensor is the last thing refused)
-        _check_device(t, what)
-    if device is not None and device.type != "cuda":
-        raise ValueError("device must be a ROCm GPU, got %s (there is no CPU fallback)" % device)
-    if devs:
-        return devs.pop()
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def start_capacity(first, limit, _start_capacity):
@@ -51,9 +17,9 @@ def start_capacity(first, limit, _start_capacity):
     if _start_capacity is None:
         return first, limit
     capacity = _start_capacity
-    if isinstance(capacity, bool) or not isinstance(capacity, int) or not _MIN_CAPACITY <= capacity <= _MAX_CAPACITY \
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not MIN_CAPACITY <= capacity <= MAX_CAPACITY \
             or capacity & (capacity - 1):
-        raise ValueError("_start_capacity must be a power of two in [%d, 2^31]" % _MIN_CAPACITY)
+        raise ValueError("_start_capacity must be a power of two in [%d, 2^31]" % MIN_CAPACITY)
     return capacity, max(limit, capacity)
 
 

@@ -18,36 +18,29 @@ other's boundary pixels is the boundary recall, the swapped call gives the preci
 the boundary IoU.  All of it is integer arithmetic: results are exact and bitwise reproducible.  Unbatched input drops the leading N
 of every result.  This module imports torch; the package itself does not import it.
 """
-import ctypes as C
 import numbers
 
 import torch
 
-from . import _binding as B, _pairtable as T
-from ._pairtable import _MAX_CAPACITY, _pow2_at_least
-from .pool import MAX_COMPONENTS, _labels_on, _stream
+from . import _binding as B, _pairtable as PT, _tensors as T
 
 __all__ = ["label_overlap", "boundary_match", "OverlapTable"]
 
 MAX_TOLERANCE = 15
 
 
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_overlap_accumulate"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no label map comparison entry points; rebuild it")
-    return lib
+_ENTRY = ("fslic_hip_overlap_accumulate", "label map comparison entry points")
 
 
 def first_capacity(K, M):
     """Slots per frame of the first pair table: a segment of one Slic-like map meets a handful of the other's, and the table stays
     under half load."""
-    return max(1024, _pow2_at_least(16 * max(K, M)))
+    return max(1024, PT.pow2_at_least(16 * max(K, M)))
 
 
 def capacity_limit(K, M, H, W):
     """Slots per frame that hold any two maps of this shape at half load: no more distinct pairs than label pairs or pixels."""
-    return min(_MAX_CAPACITY, max(first_capacity(K, M), _pow2_at_least(2 * min(K * M, H * W))))
+    return min(PT.MAX_CAPACITY, max(first_capacity(K, M), PT.pow2_at_least(2 * min(K * M, H * W))))
 
 
 class OverlapTable(object):
@@ -128,23 +121,6 @@ def _check_maps(labels, other):
     return H, W
 
 
-def _check_count(K, what):
-    if isinstance(K, bool) or not isinstance(K, numbers.Integral):
-        raise ValueError("%s must be an integer" % what)
-    K = int(K)
-    if not 1 <= K <= MAX_COMPONENTS:
-        raise ValueError("%s must be in [1, %d], got %d" % (what, MAX_COMPONENTS, K))
-    return K
-
-
-def _on(maps, dev, batched):
-    out = []
-    for m in maps:
-        t, code = _labels_on(m, dev)
-        out.append((t if batched else t.unsqueeze(0), code))
-    return out
-
-
 def label_overlap(labels, other, num_components, num_other, *, device=None, _start_capacity=None):
     """The overlap table of `labels` and `other` ([H, W] or [N, H, W] of one shape; int16, int32 or int64, not necessarily the same;
     numpy or torch) as an OverlapTable: every pair (a, b) with 0 <= a < num_components and 0 <= b < num_other that shares a pixel,
@@ -158,30 +134,28 @@ def label_overlap(labels, other, num_components, num_other, *, device=None, _sta
     min(K M, H W) pairs.  The result does not depend on the table's size.  `_start_capacity` (testing) sets the first table's slots
     per frame."""
     H, W = _check_maps(labels, other)
-    K = _check_count(num_components, "num_components")
-    M = _check_count(num_other, "num_other")
-    capacity, limit = T.start_capacity(first_capacity(K, M), capacity_limit(K, M, H, W), _start_capacity)
-    dev = T.pick_device(((labels, "labels"), (other, "other")), device)
+    K = T.check_count(num_components, "num_components")
+    M = T.check_count(num_other, "num_other")
+    capacity, limit = PT.start_capacity(first_capacity(K, M), capacity_limit(K, M, H, W), _start_capacity)
+    dev = T.one_device(((labels, "labels"), (other, "other")), device)
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     batched = labels.ndim == 3
-    (lab, ltype), (oth, otype) = _on((labels, other), dev, batched)
+    (lab, ltype), (oth, otype) = T.labels_on(labels, dev, batched), T.labels_on(other, dev, batched)
     N = lab.shape[0]
 
     def accumulate(capacity):
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_overlap_workspace_size(N, capacity, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        B._check(lib.fslic_hip_overlap_accumulate(dev.index, _stream(dev), N, H, W, K, M, lab.data_ptr(), ltype, oth.data_ptr(), otype,
-                                                  capacity, ws.data_ptr(), nbytes.value))
-        return ws, nbytes.value
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_overlap_workspace_size, N, capacity)
+        B._check(lib.fslic_hip_overlap_accumulate(dev.index, T.stream(dev), N, H, W, K, M, lab.data_ptr(), ltype, oth.data_ptr(), otype,
+                                                  capacity, ws.data_ptr(), nbytes))
+        return ws, nbytes
 
     def compact(ws, nbytes, capacity, P, keys, count):
-        B._check(lib.fslic_hip_overlap_compact(dev.index, _stream(dev), N, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
+        B._check(lib.fslic_hip_overlap_compact(dev.index, T.stream(dev), N, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
                                                count.data_ptr(), P))
 
     with torch.cuda.device(dev):
-        pairs, count, _, offsets, capacity = T.run(accumulate, compact, N, capacity, limit, dev)
+        pairs, count, _, offsets, capacity = PT.run(accumulate, compact, N, capacity, limit, dev)
     return OverlapTable(pairs, count, offsets, K, M, capacity, batched)
 
 
@@ -192,14 +166,14 @@ def boundary_match(labels, other, tolerance=0, *, device=None):
     H, W = _check_maps(labels, other)
     if isinstance(tolerance, bool) or not isinstance(tolerance, numbers.Integral) or not 0 <= int(tolerance) <= MAX_TOLERANCE:
         raise ValueError("tolerance must be an integer in [0, %d], got %r" % (MAX_TOLERANCE, tolerance))
-    dev = T.pick_device(((labels, "labels"), (other, "other")), device)
+    dev = T.one_device(((labels, "labels"), (other, "other")), device)
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     batched = labels.ndim == 3
-    (lab, ltype), (oth, otype) = _on((labels, other), dev, batched)
+    (lab, ltype), (oth, otype) = T.labels_on(labels, dev, batched), T.labels_on(other, dev, batched)
     N = lab.shape[0]
     with torch.cuda.device(dev):
         out = torch.empty((N, 3), dtype=torch.int64, device=dev)
-        B._check(lib.fslic_hip_boundary_match(dev.index, _stream(dev), N, H, W, lab.data_ptr(), ltype, oth.data_ptr(), otype,
+        B._check(lib.fslic_hip_boundary_match(dev.index, T.stream(dev), N, H, W, lab.data_ptr(), ltype, oth.data_ptr(), otype,
                                               int(tolerance), out.data_ptr()))
     return out if batched else out[0]

@@ -31,22 +31,13 @@ host path for any input; scratch memory (8 bytes per pixel) comes from torch's c
 it is integer arithmetic: results are exact and identical from run to run.  Unbatched input drops the leading N of every result.
 This module imports torch; the package itself does not import it.
 """
-import ctypes as C
 import numbers
 
 import torch
 
-from . import _binding as B, _pairtable as T
-from .pool import _labels_on, _stream
+from . import _binding as B, _tensors as T
 
 __all__ = ["connected_components", "enforce_connectivity"]
-
-
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_connect_enforce"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no connectivity entry points for label tensors; rebuild it")
-    return lib
 
 
 # ---- argument checks: all of them run before any device work ----
@@ -72,25 +63,21 @@ def _run(labels, device, min_size):
     _check_map(labels)
     if min_size is not None:
         min_size = _check_min_size(min_size)
-    dev = T.pick_device(((labels, "labels"),), device)
+    dev = T.one_device(((labels, "labels"),), device)
 
-    lib = _lib()
+    lib = T.library("fslic_hip_connect_enforce", "connectivity entry points for label tensors")
     batched = labels.ndim == 3
-    lab, ltype = _labels_on(labels, dev)
-    if not batched:
-        lab = lab.unsqueeze(0)
+    lab, ltype = T.labels_on(labels, dev, batched)
     N, H, W = (int(v) for v in lab.shape)
-    nbytes = C.c_size_t()
-    B._check(lib.fslic_hip_connect_workspace_size(N, H, W, C.byref(nbytes)))
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_connect_workspace_size, N, H, W)
         out = torch.empty((N, H, W), dtype=torch.int32, device=dev)
         n = torch.empty((N,), dtype=torch.int32, device=dev)
-        head = (dev.index, _stream(dev), N, H, W, lab.data_ptr(), ltype)
+        head = (dev.index, T.stream(dev), N, H, W, lab.data_ptr(), ltype)
         if min_size is None:
-            B._check(lib.fslic_hip_connected_components(*head, out.data_ptr(), n.data_ptr(), ws.data_ptr(), nbytes.value))
+            B._check(lib.fslic_hip_connected_components(*head, out.data_ptr(), n.data_ptr(), ws.data_ptr(), nbytes))
         else:
-            B._check(lib.fslic_hip_connect_enforce(*head, min_size, out.data_ptr(), n.data_ptr(), ws.data_ptr(), nbytes.value))
+            B._check(lib.fslic_hip_connect_enforce(*head, min_size, out.data_ptr(), n.data_ptr(), ws.data_ptr(), nbytes))
     return (out, n) if batched else (out[0], n[0])
 
 

@@ -29,9 +29,8 @@ import numbers
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _binding as B
+from . import _binding as B, _tensors as T
 from .crf import _PARAMS, _Params
-from .pool import _check_device, _check_float_map, _stream
 from .rag import SuperpixelGraph
 
 __all__ = ["superpixel_crf", "crf_edge_energies", "transpose_batch_csr", "DEFAULT_PARAMS", "PARAM_NAMES"]
@@ -44,41 +43,23 @@ DEFAULT_PARAMS = dict(spatial_w=10.0, temporal_w=10.0, spatial_srgb=13.0, tempor
 _LIMIT = 1 << 31
 
 
-def _lib(entry="fslic_hip_crf_tensor_inference", what="entry points"):
-    lib = B.load_library()
-    if not hasattr(lib, entry):
-        raise RuntimeError("fast_slic_amd: the loaded library has no CRF tensor %s; rebuild it" % what)
-    return lib
+def _library(entry="fslic_hip_crf_tensor_inference", what="entry points"):
+    return T.library(entry, "CRF tensor " + what)
 
 
-def _lib_energies():
-    _lib()
-    return _lib("fslic_hip_crf_tensor_backward_energies", "energies entry points")
-
-
-def _ptr(t, cond=True):
-    """The device pointer of `t`; None (NULL) without a tensor or where `cond` does not hold."""
-    return t.data_ptr() if t is not None and cond else None
-
-
-def _scratch(dev, size_entry, *sizes):
-    """Scratch memory from torch's caching allocator, as many bytes as the library's `size_entry` asks for `sizes`."""
-    nbytes = C.c_size_t()
-    B._check(size_entry(*sizes, C.byref(nbytes)))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+def _energies_library():
+    _library()
+    return _library("fslic_hip_crf_tensor_backward_energies", "energies entry points")
 
 
 # ---- argument checks: all of them run before any device work ----
 def _check_tensor(t, dtype, shape, what, shape_text):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a torch tensor" % what)
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (what, str(dtype).replace("torch.", ""), t.dtype))
+    T.check_tensor(t, what, (dtype,), shape_text, lambda s: True)
     if tuple(t.shape) != tuple(shape):
         raise ValueError("%s must have shape %s (%s) to match the unaries, got %s" % (what, tuple(shape), shape_text, tuple(t.shape)))
 
 
-def _check_graph(graph, N, K):
+def _check_neighbours(graph, N, K):
     """-> the number of neighbour entries, known without looking at device memory."""
     if isinstance(graph, SuperpixelGraph):
         if graph.num_components != K or graph.num_frames != N:
@@ -191,29 +172,29 @@ class _Call(object):
         self.nnz = int(indices.shape[0])
 
     def _head(self):
-        return (self.dev.index, _stream(self.dev), self.N, self.Cn, self.K, int(self.temporal), self.max_iter)
+        return (self.dev.index, T.stream(self.dev), self.N, self.Cn, self.K, int(self.temporal), self.max_iter)
 
     def _graph(self):
-        return (_ptr(self.mem), _ptr(self.offsets), _ptr(self.indices, self.nnz), self.nnz)
+        return (T.ptr(self.mem), T.ptr(self.offsets), T.ptr(self.indices, self.nnz), self.nnz)
 
     def from_params(self, p, yx):
         """The arguments up to nnz of an entry that computes the energies from host params and yxrgb."""
-        return self._head() + (C.byref(p), _ptr(self.comp), _ptr(yx)) + self._graph()
+        return self._head() + (C.byref(p), T.ptr(self.comp), T.ptr(yx)) + self._graph()
 
     def from_energies(self, edge, links):
         """The arguments up to links of an _energies entry."""
-        return self._head() + (_ptr(self.comp),) + self._graph() + (_ptr(edge, self.nnz), _ptr(links))
+        return self._head() + (T.ptr(self.comp),) + self._graph() + (T.ptr(edge, self.nnz), T.ptr(links))
 
     def run(self, entry, lead, own, size_entry, *flags):
         """entry(*lead, *own, workspace, bytes) with as much workspace as size_entry(N, C, K, nnz, *flags) asks for."""
-        ws = _scratch(self.dev, size_entry, self.N, self.Cn, self.K, self.nnz, *flags)
-        B._check(entry(*lead, *own, ws.data_ptr(), ws.numel()))
+        ws, nbytes = T.scratch(self.dev, size_entry, self.N, self.Cn, self.K, self.nnz, *flags)
+        B._check(entry(*lead, *own, ws.data_ptr(), nbytes))
 
 
 def _plain(lib, entry, call, lead, start):
     """The call outside autograd -> q."""
     q = torch.empty_like(call.un)
-    call.run(entry, lead, (_ptr(call.un), _ptr(start), _ptr(q)), lib.fslic_hip_crf_tensor_workspace_size)
+    call.run(entry, lead, (T.ptr(call.un), T.ptr(start), T.ptr(q)), lib.fslic_hip_crf_tensor_workspace_size)
     return q
 
 
@@ -221,7 +202,7 @@ def _saved_forward(ctx, lib, entry, call, lead, start, kept):
     """The sweeps with every iterate kept -> q, a view of them.  `kept`: the energy source's tensors, saved behind the call's."""
     with torch.cuda.device(call.dev):
         q_all = torch.empty((call.max_iter + 1,) + tuple(call.un.shape), dtype=torch.float32, device=call.dev)
-        call.run(entry, lead, (_ptr(call.un), _ptr(start), _ptr(q_all)), lib.fslic_hip_crf_tensor_grad_workspace_size, 0, 0)
+        call.run(entry, lead, (T.ptr(call.un), T.ptr(start), T.ptr(q_all)), lib.fslic_hip_crf_tensor_grad_workspace_size, 0, 0)
     ctx.save_for_backward(call.un, call.comp, call.mem, call.offsets, call.indices, q_all, *kept)
     ctx.call = (call.N, call.max_iter, call.temporal, start is not None)
     return q_all[call.max_iter]
@@ -242,8 +223,8 @@ def _saved_backward(lib, entry, call, lead, q_all, has_q0, with_compat, g, energ
         du = torch.empty_like(un)
         dq0 = torch.empty_like(un) if has_q0 else None
         dcompat = torch.empty_like(call.comp) if with_compat else None
-        own = (_ptr(t_offsets), _ptr(t_entries, nnz), _ptr(t_rows, nnz), _ptr(un), _ptr(q_all), _ptr(g), _ptr(du), _ptr(dq0),
-               _ptr(dcompat)) + tuple(energy_grads)
+        own = (T.ptr(t_offsets), T.ptr(t_entries, nnz), T.ptr(t_rows, nnz), T.ptr(un), T.ptr(q_all), T.ptr(g), T.ptr(du), T.ptr(dq0),
+               T.ptr(dcompat)) + tuple(energy_grads)
         call.run(entry, lead, own, lib.fslic_hip_crf_tensor_grad_workspace_size, 1, int(with_compat))
     return du, dq0, dcompat
 
@@ -253,7 +234,7 @@ class _SuperpixelCRF(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, un, start, comp, yx, mem, offsets, indices, N, max_iter, temporal, p):
-        lib = _lib("fslic_hip_crf_tensor_backward", "backward")
+        lib = _library("fslic_hip_crf_tensor_backward", "backward")
         call = _Call(un, comp, mem, offsets, indices, N, max_iter, temporal)
         ctx.p = p
         return _saved_forward(ctx, lib, lib.fslic_hip_crf_tensor_inference_saved, call, call.from_params(p, yx), start, (yx,))
@@ -261,7 +242,7 @@ class _SuperpixelCRF(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        lib = _lib()
+        lib = _library()
         call, q_all, has_q0, (yx,) = _saved_call(ctx)
         return _saved_backward(lib, lib.fslic_hip_crf_tensor_backward, call, call.from_params(ctx.p, yx), q_all, has_q0,
                                ctx.needs_input_grad[2], g) + (None,) * 8
@@ -272,7 +253,7 @@ class _SuperpixelCRFEnergies(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal):
-        lib = _lib_energies()
+        lib = _energies_library()
         call = _Call(un, comp, mem, offsets, indices, N, max_iter, temporal)
         return _saved_forward(ctx, lib, lib.fslic_hip_crf_tensor_inference_saved_energies, call, call.from_energies(edge, links), start,
                               (edge,) if links is None else (edge, links))
@@ -280,25 +261,25 @@ class _SuperpixelCRFEnergies(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        lib = _lib_energies()
+        lib = _energies_library()
         call, q_all, has_q0, kept = _saved_call(ctx)
         edge, links = (kept + (None,))[:2]
         dedge = torch.empty_like(edge) if ctx.needs_input_grad[3] else None
         dlinks = torch.empty_like(links) if links is not None and ctx.needs_input_grad[4] else None
         grads = _saved_backward(lib, lib.fslic_hip_crf_tensor_backward_energies, call, call.from_energies(edge, links), q_all, has_q0,
-                                ctx.needs_input_grad[2], g, (_ptr(dedge, call.nnz), _ptr(dlinks)))
+                                ctx.needs_input_grad[2], g, (T.ptr(dedge, call.nnz), T.ptr(dlinks)))
         return grads + (dedge, dlinks) + (None,) * 6
 
 
 def _energies_raw(theta, yx, mem, offsets, indices, N, K, temporal):
     """edge [nnz] and links [N, 2, K] from contiguous tensors on one GPU."""
-    lib, dev = _lib_energies(), yx.device
+    lib, dev = _energies_library(), yx.device
     nnz = int(indices.shape[0])
     with torch.cuda.device(dev):
         edge = torch.empty(nnz, dtype=torch.float32, device=dev)
         links = torch.empty((N, 2, K), dtype=torch.float32, device=dev)
-        B._check(lib.fslic_hip_crf_tensor_energies(dev.index, _stream(dev), N, K, int(temporal), _ptr(theta), _ptr(yx), _ptr(mem),
-                                                   _ptr(offsets), _ptr(indices, nnz), nnz, _ptr(edge, nnz), _ptr(links)))
+        B._check(lib.fslic_hip_crf_tensor_energies(dev.index, T.stream(dev), N, K, int(temporal), T.ptr(theta), T.ptr(yx), T.ptr(mem),
+                                                   T.ptr(offsets), T.ptr(indices, nnz), nnz, T.ptr(edge, nnz), T.ptr(links)))
     return edge, links
 
 
@@ -317,16 +298,16 @@ class _EdgeEnergies(torch.autograd.Function):
     def backward(ctx, g_edge, g_links):
         theta, yx, offsets, indices = ctx.saved_tensors
         N, K, temporal = ctx.call
-        lib, dev = _lib_energies(), yx.device
+        lib, dev = _energies_library(), yx.device
         nnz = int(indices.shape[0])
         with torch.cuda.device(dev):
             g_edge = g_edge.contiguous() if g_edge is not None and nnz else None
             g_links = g_links.contiguous() if g_links is not None else None
-            ws = _scratch(dev, lib.fslic_hip_crf_tensor_energies_backward_workspace_size, N, K)
+            ws, nbytes = T.scratch(dev, lib.fslic_hip_crf_tensor_energies_backward_workspace_size, N, K)
             dtheta = torch.empty_like(theta)
             B._check(lib.fslic_hip_crf_tensor_energies_backward(
-                dev.index, _stream(dev), N, K, int(temporal), _ptr(theta), _ptr(yx), _ptr(offsets), _ptr(indices, nnz), nnz, _ptr(g_edge),
-                _ptr(g_links), _ptr(dtheta), ws.data_ptr(), ws.numel()))
+                dev.index, T.stream(dev), N, K, int(temporal), T.ptr(theta), T.ptr(yx), T.ptr(offsets), T.ptr(indices, nnz), nnz, T.ptr(g_edge),
+                T.ptr(g_links), T.ptr(dtheta), ws.data_ptr(), nbytes))
         return dtheta, None, None, None, None, None, None, None
 
 
@@ -354,7 +335,7 @@ def _check_same_device(dev, owner, graph, named):
         else (("graph offsets", graph[0]), ("graph indices", graph[1]))
     for what, t in named + on_graph:
         if isinstance(t, torch.Tensor):
-            _check_device(t, what)
+            T.check_device(t, what)
             if t.device != dev:
                 raise ValueError("%s must be on %s GPU %s, got %s" % (what, owner, dev, t.device))
 
@@ -370,7 +351,7 @@ def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
     params: None, a dict, or a float32 [7] tensor on the clusters' GPU in PARAM_NAMES order, read on the device.  With a tensor that
     requires a gradient the result is differentiable with respect to it (terms and sums in double, a fixed order, no atomics); it is
     not differentiable with respect to yxrgb.  Runs on the current stream without host synchronisation."""
-    _check_float_map(yxrgb, (2, 3), "yxrgb", "[5, K] or [N, 5, K]")
+    T.check_float_map(yxrgb, (2, 3), "yxrgb", "[5, K] or [N, 5, K]")
     batched = yxrgb.dim() == 3
     N = yxrgb.shape[0] if batched else 1
     if yxrgb.shape[-2] != 5:
@@ -378,7 +359,7 @@ def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
     K = int(yxrgb.shape[-1])
     lead = (N,) if batched else ()
     _check_tensor(members, torch.int32, lead + (K,), "members", "[K] or [N, K]")
-    nnz = _check_graph(graph, N, K)
+    nnz = _check_neighbours(graph, N, K)
     if isinstance(params, torch.Tensor):
         _check_params_tensor(params)
     else:
@@ -387,7 +368,7 @@ def crf_edge_energies(graph, yxrgb, members, params=None, temporal=False):
         raise ValueError("temporal must be True or False, got %r" % (temporal,))
     if N * K + 1 >= _LIMIT or nnz >= _LIMIT:
         raise ValueError("N * K + 1 and the number of neighbour entries must be below 2^31")
-    _check_device(yxrgb, "yxrgb")
+    T.check_device(yxrgb, "yxrgb")
     dev = yxrgb.device
     _check_same_device(dev, "yxrgb's", graph, (("members", members), ("params", params)))
     with torch.cuda.device(dev):
@@ -424,7 +405,7 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     the sweep's part of the energy gradients, one owner thread per cell, and a params tensor receives the energies' backward of them.
     An entry whose index is outside [0, K), the link cells at the window's ends and all of links with temporal false get 0.0.
     `yxrgb`, `members` and the graph get no gradient.  Otherwise q has no grad_fn."""
-    _check_float_map(unaries, (2, 3), "unaries", "[C, K] or [N, C, K]")
+    T.check_float_map(unaries, (2, 3), "unaries", "[C, K] or [N, C, K]")
     batched = unaries.dim() == 3
     N = unaries.shape[0] if batched else 1
     Cn, K = (int(v) for v in unaries.shape[-2:])
@@ -436,7 +417,7 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
     _check_tensor(members, torch.int32, lead + (K,), "members", "[K] or [N, K]")
     if q0 is not None:
         _check_tensor(q0, torch.float32, tuple(unaries.shape), "q0", "the unaries' shape")
-    nnz = _check_graph(graph, N, K)
+    nnz = _check_neighbours(graph, N, K)
     if isinstance(max_iter, bool) or not isinstance(max_iter, numbers.Integral) or max_iter < 0:
         raise ValueError("max_iter must be a non-negative integer, got %r" % (max_iter,))
     max_iter = int(max_iter)
@@ -456,12 +437,12 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
         edge, links = _check_energies(energies, nnz, lead, K, temporal)
     if N * Cn * K >= _LIMIT or N * K + 1 >= _LIMIT or nnz >= _LIMIT:
         raise ValueError("N * C * K, N * K + 1 and the number of neighbour entries must be below 2^31")
-    _check_device(unaries, "unaries")
+    T.check_device(unaries, "unaries")
     dev = unaries.device
     _check_same_device(dev, "the unaries'", graph, (("yxrgb", yxrgb), ("members", members), ("q0", q0), ("compat", compat),
                                                     ("params", params), ("energies: edge", edge), ("energies: links", links)))
 
-    lib = _lib()
+    lib = _library()
     with torch.cuda.device(dev):
         offsets, indices = _batch_csr(graph)
         if compat is None:
@@ -486,5 +467,5 @@ def superpixel_crf(unaries, graph, yxrgb, members, max_iter=10, params=None, com
         links = links.contiguous().view(N, 2, K) if links is not None else None
         if wants_grad(unaries, q0, compat, edge, links):
             return _SuperpixelCRFEnergies.apply(un, start, comp, edge, links, mem, offsets, indices, N, max_iter, temporal)
-        lib = _lib_energies()
+        lib = _energies_library()
         return _plain(lib, lib.fslic_hip_crf_tensor_inference_energies, call, call.from_energies(edge, links), start)

@@ -23,21 +23,14 @@ import numbers
 import numpy as np
 import torch
 
-from . import _binding as B
+from . import _binding as B, _tensors as T
 from .base_slic import BaseSlic
-from .pool import _stream
 
 __all__ = ["slic_tensor", "pack_rgb", "SlicFrames"]
 
 _SRC_TYPE = {torch.uint8: 0, torch.float16: 1, torch.bfloat16: 2, torch.float32: 3}      # FSLIC_PACK_*
 MAX_COMPONENTS = 65533                                                                    # (SlicModel: num_components < 65534)
-
-
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_pack_rgb"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no frame ingest entry points; rebuild it")
-    return lib
+_ENTRY = ("fslic_hip_pack_rgb", "frame ingest entry points")
 
 
 def frame_pitch(H, W):
@@ -77,11 +70,6 @@ def _check_scale(scale):
     return float(scale)
 
 
-def _check_device(images):      # (a CPU tensor is the last thing refused)
-    if images.device.type != "cuda":
-        raise ValueError("images must be on a ROCm GPU, got device %s (there is no CPU fallback)" % images.device)
-
-
 def _check_out(out, N, need):
     if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != N or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 tensor [N, pitch]")
@@ -95,8 +83,8 @@ def _pack(x, scale, out):
     """x: the [N, 3, H, W] view.  One launch on torch's current stream of x's device."""
     N, _, H, W = x.shape
     strides = (C.c_longlong * 4)(*x.stride())
-    B._check(_lib().fslic_hip_pack_rgb(x.device.index, _stream(x.device), N, H, W, x.data_ptr(), _SRC_TYPE[x.dtype], strides,
-                                       C.c_float(scale), out.data_ptr(), out.shape[1]))
+    B._check(T.library(*_ENTRY).fslic_hip_pack_rgb(x.device.index, T.stream(x.device), N, H, W, x.data_ptr(), _SRC_TYPE[x.dtype], strides,
+                                                   C.c_float(scale), out.data_ptr(), out.shape[1]))
     return out
 
 
@@ -110,7 +98,7 @@ def pack_rgb(images, scale=255.0, channels_first=None, out=None):
     N, _, H, W = (int(v) for v in x.shape)
     if out is not None:
         _check_out(out, N, 3 * H * W)
-    _check_device(images)
+    T.check_device(images, "images")      # (a CPU tensor is the last thing refused)
     if out is not None and out.device != images.device:
         raise ValueError("out must be on the images' device %s, got %s" % (images.device, out.device))
     if out is None:
@@ -166,7 +154,7 @@ def _seed_clusters(frames, N, H, W, K):
     """The clusters Slic.iterate starts a fresh model with, for every frame: the seed grid once, then the K seed pixels of all frames
     by one gather on the device and one copy of N K 3 bytes to the host.  frames: uint8 [N, >= 3 H W]."""
     seed = np.zeros(K, B.CLUSTER_DTYPE)
-    B._check(_lib().fslic_hip_seed_positions(H, W, K, seed.ctypes.data))
+    B._check(T.library(*_ENTRY).fslic_hip_seed_positions(H, W, K, seed.ctypes.data))
     base = 3 * (W * seed["y"].astype(np.int64) + seed["x"].astype(np.int64))
     index = torch.from_numpy((base[:, None] + np.arange(3)).reshape(-1)).to(frames.device)
     rgb = frames.index_select(1, index).cpu().numpy().reshape(N, K, 3)
@@ -204,7 +192,7 @@ def slic_tensor(images, slic, max_iter=10, clusters=None, scale=255.0, channels_
         raise ValueError("max_iter must be a non-negative integer")
     K = _check_num_components(slic.num_components) if clusters is None else _check_clusters(clusters, N)
     params = model.iterate_params(int(max_iter), slic.compactness, slic.min_size_factor, slic.subsample_stride)
-    _check_device(images)
+    T.check_device(images, "images")      # (a CPU tensor is the last thing refused)
 
     dev = x.device
     if x.dtype == torch.uint8 and not channels_first and x.permute(0, 2, 3, 1).is_contiguous():

@@ -35,105 +35,44 @@ contract_graph synchronises once for the number of edges, and again only when it
 There is no CPU fallback.  All of it is integer arithmetic or comparison: results are exact and identical from run to run.
 This module imports torch; the package itself does not import it.
 """
-import ctypes as C
 import numbers
 
 import torch
 
-from . import _binding as B, _pairtable as T
-from ._pairtable import _MAX_CAPACITY, _pow2_at_least
-from .pool import _check_device, _check_num_components, _labels_on, _stream
-from .rag import MAX_CHANNELS, SuperpixelGraph, first_capacity
+from . import _binding as B, _pairtable as PT, _tensors as T
+from .rag import SuperpixelGraph, check_graph, first_capacity, graph_device, graph_edges
 
 __all__ = ["best_neighbour_edges", "merge_components", "merge_labels", "contract_graph", "compose_mappings"]
 
-_MEMBER_TYPE = {torch.int32: 1, torch.int64: 2}                            # FSLIC_LABEL_I32, FSLIC_LABEL_I64
-
-
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_merge_components"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no graph merging entry points; rebuild it")
-    return lib
+_ENTRY = ("fslic_hip_merge_components", "graph merging entry points")
 
 
 # ---- argument checks: all of them run before any device work ----
-def _check_tensor(t, what, dtypes, shape_text, ok_shape):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("%s must be a torch tensor" % what)
-    if t.dtype not in dtypes:
-        raise ValueError("%s must be %s, got %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), t.dtype))
-    if not ok_shape(tuple(t.shape)):
-        raise ValueError("%s must be %s, got shape %s" % (what, shape_text, tuple(t.shape)))
-
-
-def _check_graph(graph):
-    """-> (N, K, E, C) of a SuperpixelGraph whose fields have the types and shapes superpixel_graph gives them."""
-    if not isinstance(graph, SuperpixelGraph):
-        raise ValueError("graph must be a SuperpixelGraph")
-    K = _check_num_components(graph.num_components)
-    _check_tensor(graph.edge_index, "graph.edge_index", (torch.int64,), "[2, E]", lambda s: len(s) == 2 and s[0] == 2)
-    E = int(graph.edge_index.shape[1])
-    _check_tensor(graph.offsets, "graph.offsets", (torch.int64,), "[N + 1]", lambda s: len(s) == 1 and s[0] >= 2)
-    N = int(graph.offsets.shape[0]) - 1
-    if E >= 1 << 31:
-        raise ValueError("the graph must have fewer than 2^31 edges")
-    if N * K >= 1 << 31:
-        raise ValueError("N * num_components must be below 2^31")
-    _check_tensor(graph.boundary, "graph.boundary", (torch.int32,), "[E]", lambda s: s == (E,))
-    Cc = 0
-    if graph.contrast is not None:
-        _check_tensor(graph.contrast, "graph.contrast", (torch.int64,), "[E, C] with C in 1 .. %d" % MAX_CHANNELS,
-                      lambda s: len(s) == 2 and s[0] == E and 1 <= s[1] <= MAX_CHANNELS)
-        Cc = int(graph.contrast.shape[1])
-    return N, K, E, Cc
-
-
-def _graph_device(graph, others):
-    """The GPU of the graph; others: ((tensor or None, name), ...) must be there too.  A CPU tensor is the last thing refused."""
-    fields = [(graph.edge_index, "graph.edge_index"), (graph.offsets, "graph.offsets"), (graph.boundary, "graph.boundary"),
-              (graph.contrast, "graph.contrast")] + list(others)
-    given = [(t, what) for t, what in fields if t is not None]
-    devs = {t.device for t, _ in given if t.device.type == "cuda"}
-    if len(devs) > 1:
-        raise ValueError("%s must be on one GPU, got %s" % (", ".join(what for _, what in given), sorted(str(d) for d in devs)))
-    for t, what in given:
-        _check_device(t, what)
-    return devs.pop()
-
-
 def _check_mapping(mapping, N, K=None, what="mapping"):
-    _check_tensor(mapping, what, (torch.int32,), "[N, K] with N = %d%s" % (N, "" if K is None else " and K = %d" % K),
-                  lambda s: len(s) == 2 and s[0] == N and s[1] >= 1 and (K is None or s[1] == K))
-
-
-def _edges(graph):
-    ei = graph.edge_index.contiguous()
-    return ei, graph.offsets.contiguous()
+    T.check_tensor(mapping, what, (torch.int32,), "[N, K] with N = %d%s" % (N, "" if K is None else " and K = %d" % K),
+                   lambda s: len(s) == 2 and s[0] == N and s[1] >= 1 and (K is None or s[1] == K))
 
 
 def best_neighbour_edges(graph, weight, threshold=None):
     """join bool [E]: true where the edge is the best edge of at least one of its endpoints (rule 1 of the module's text).  `weight`
     float32 [E] on the graph's GPU; `threshold` None or a Python number: only edges with weight < threshold are eligible."""
-    N, K, E, _ = _check_graph(graph)
-    _check_tensor(weight, "weight", (torch.float32,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
+    N, K, E, _ = check_graph(graph)
+    T.check_tensor(weight, "weight", (torch.float32,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
     if threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, numbers.Real)):
         raise ValueError("threshold must be None or a number, got %r" % (threshold,))
-    dev = _graph_device(graph, ((weight, "weight"),))
+    dev = graph_device(graph, ((weight, "weight"),))
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
         join = torch.empty(E, dtype=torch.bool, device=dev)
         if E == 0:
             return join
-        ei, offsets = _edges(graph)
+        ei, offsets = graph_edges(graph)
         w = weight.contiguous()
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_merge_best_workspace_size(N, K, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        B._check(lib.fslic_hip_merge_best_edges(dev.index, _stream(dev), N, K, E, ei.data_ptr(), offsets.data_ptr(), w.data_ptr(),
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_merge_best_workspace_size, N, K)
+        B._check(lib.fslic_hip_merge_best_edges(dev.index, T.stream(dev), N, K, E, ei.data_ptr(), offsets.data_ptr(), w.data_ptr(),
                                                 0 if threshold is None else 1, 0.0 if threshold is None else float(threshold),
-                                                join.data_ptr(), ws.data_ptr(), nbytes.value))
+                                                join.data_ptr(), ws.data_ptr(), nbytes))
     return join
 
 
@@ -141,27 +80,24 @@ def merge_components(graph, join, members=None):
     """(mapping int32 [N, K], n int32 [N]): the groups of the present nodes under the edges with `join` true, numbered by their
     smallest node (rule 2 of the module's text).  `join` bool [E]; `members` None or int32 / int64 [N, K] ([K] allowed when N = 1),
     superpixel_pool's counts: a node without members is absent.  The same six launches whatever the graph, no host synchronisation."""
-    N, K, E, _ = _check_graph(graph)
-    _check_tensor(join, "join", (torch.bool,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
+    N, K, E, _ = check_graph(graph)
+    T.check_tensor(join, "join", (torch.bool,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
     if members is not None:
-        _check_tensor(members, "members", tuple(_MEMBER_TYPE), "[N, K] = [%d, %d]%s" % (N, K, " or [K]" if N == 1 else ""),
-                      lambda s: s == (N, K) or (N == 1 and s == (K,)))
-    dev = _graph_device(graph, ((join, "join"), (members, "members")))
+        T.check_tensor(members, "members", tuple(T.MEMBER_TYPE), "[N, K] = [%d, %d]%s" % (N, K, " or [K]" if N == 1 else ""),
+                       lambda s: s == (N, K) or (N == 1 and s == (K,)))
+    dev = graph_device(graph, ((join, "join"), (members, "members")))
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
-        ei, offsets = _edges(graph)
+        ei, offsets = graph_edges(graph)
         jn = join.contiguous()
         mem = members.contiguous() if members is not None else None
         mapping = torch.empty((N, K), dtype=torch.int32, device=dev)
         n = torch.empty((N,), dtype=torch.int32, device=dev)
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_merge_components_workspace_size(N, K, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        B._check(lib.fslic_hip_merge_components(dev.index, _stream(dev), N, K, E, ei.data_ptr() if E else None, offsets.data_ptr(),
-                                                jn.data_ptr() if E else None, mem.data_ptr() if mem is not None else None,
-                                                _MEMBER_TYPE[mem.dtype] if mem is not None else 0, mapping.data_ptr(), n.data_ptr(),
-                                                ws.data_ptr(), nbytes.value))
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_merge_components_workspace_size, N, K)
+        B._check(lib.fslic_hip_merge_components(dev.index, T.stream(dev), N, K, E, T.ptr(ei, E), offsets.data_ptr(), T.ptr(jn, E),
+                                                T.ptr(mem), T.MEMBER_TYPE[mem.dtype] if mem is not None else 0, mapping.data_ptr(),
+                                                n.data_ptr(), ws.data_ptr(), nbytes))
     return mapping, n
 
 
@@ -175,22 +111,22 @@ def merge_labels(labels, mapping, *, device=None):
     if N * H * W >= 1 << 31:
         raise ValueError("N * H * W must be below 2^31, got shape %s" % (tuple(labels.shape),))
     _check_mapping(mapping, N)
-    K = _check_num_components(int(mapping.shape[1]))
-    dev = T.pick_device(((labels, "labels"), (mapping, "mapping")), device)
+    K = T.check_count(int(mapping.shape[1]), "num_components")
+    dev = T.one_device(((labels, "labels"), (mapping, "mapping")), device)
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
-        lab, ltype = _labels_on(labels, dev)
+        lab, ltype = T.labels_on(labels, dev)
         mp = mapping.contiguous()
         out = torch.empty(tuple(labels.shape), dtype=torch.int32, device=dev)
-        B._check(lib.fslic_hip_merge_labels(dev.index, _stream(dev), N, H, W, K, lab.data_ptr(), ltype, mp.data_ptr(), out.data_ptr()))
+        B._check(lib.fslic_hip_merge_labels(dev.index, T.stream(dev), N, H, W, K, lab.data_ptr(), ltype, mp.data_ptr(), out.data_ptr()))
     return out
 
 
 def contract_capacity_limit(K2, E):
     """Slots per frame that hold any contraction at half load: no more distinct pairs than label pairs or edges."""
     pairs = min(K2 * (K2 - 1) // 2, E)
-    return min(_MAX_CAPACITY, max(first_capacity(K2), _pow2_at_least(2 * pairs)))
+    return min(PT.MAX_CAPACITY, max(first_capacity(K2), PT.pow2_at_least(2 * pairs)))
 
 
 def contract_graph(graph, mapping, num_components, *, _start_capacity=None):
@@ -199,47 +135,45 @@ def contract_graph(graph, mapping, num_components, *, _start_capacity=None):
     holds the sums, and the graph's compact pass reads them out: one host synchronisation for the number of edges, more only when
     the table has to grow (the first has a power of two >= 8 K2 slots per frame).  `_start_capacity` (testing) sets the first
     table's slots per frame."""
-    N, K, E, Cc = _check_graph(graph)
+    N, K, E, Cc = check_graph(graph)
     _check_mapping(mapping, N, K)
-    K2 = _check_num_components(num_components)
-    capacity, limit = T.start_capacity(first_capacity(K2), contract_capacity_limit(K2, E), _start_capacity)
-    dev = _graph_device(graph, ((mapping, "mapping"),))
+    K2 = T.check_count(num_components, "num_components")
+    capacity, limit = PT.start_capacity(first_capacity(K2), contract_capacity_limit(K2, E), _start_capacity)
+    dev = graph_device(graph, ((mapping, "mapping"),))
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
         if E == 0:
             return SuperpixelGraph(torch.zeros((2, 0), dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
                                    torch.zeros((0, Cc), dtype=torch.int64, device=dev) if Cc else None,
                                    torch.zeros(N + 1, dtype=torch.int64, device=dev), K2, capacity)
-        ei, offsets = _edges(graph)
+        ei, offsets = graph_edges(graph)
         boundary, mp = graph.boundary.contiguous(), mapping.contiguous()
         contrast = graph.contrast.contiguous() if Cc else None
 
         def accumulate(capacity):
-            nbytes = C.c_size_t()
-            B._check(lib.fslic_hip_rag_workspace_size(N, K2, Cc, capacity, C.byref(nbytes)))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            B._check(lib.fslic_hip_merge_contract_accumulate(dev.index, _stream(dev), N, K, K2, E, ei.data_ptr(), offsets.data_ptr(),
-                                                             boundary.data_ptr(), contrast.data_ptr() if Cc else None, Cc, mp.data_ptr(),
-                                                             capacity, ws.data_ptr(), nbytes.value))
-            return ws, nbytes.value
+            ws, nbytes = T.scratch(dev, lib.fslic_hip_rag_workspace_size, N, K2, Cc, capacity)
+            B._check(lib.fslic_hip_merge_contract_accumulate(dev.index, T.stream(dev), N, K, K2, E, ei.data_ptr(), offsets.data_ptr(),
+                                                             boundary.data_ptr(), T.ptr(contrast), Cc, mp.data_ptr(), capacity,
+                                                             ws.data_ptr(), nbytes))
+            return ws, nbytes
 
         def compact(ws, nbytes, capacity, R, keys, count, sums=None):
-            B._check(lib.fslic_hip_rag_compact(dev.index, _stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
-                                               count.data_ptr(), sums.data_ptr() if sums is not None else None, R))
+            B._check(lib.fslic_hip_rag_compact(dev.index, T.stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
+                                               count.data_ptr(), T.ptr(sums), R))
 
-        edge_index, count, extra, out_offsets, capacity = T.run(accumulate, compact, N, capacity, limit, dev,
-                                                                [((Cc,), torch.int64)] if Cc else [])
+        edge_index, count, extra, out_offsets, capacity = PT.run(accumulate, compact, N, capacity, limit, dev,
+                                                                 [((Cc,), torch.int64)] if Cc else [])
     return SuperpixelGraph(edge_index, count, extra[0] if extra else None, out_offsets, K2, capacity)
 
 
 def compose_mappings(first, then):
     """int32 [N, K]: then[f, first[f, v]], and -1 where first is -1 (or names no node of `then`): the total mapping of two rounds.
     `first` int32 [N, K], `then` int32 [N, K'], on one GPU.  Plain torch, no host synchronisation."""
-    _check_tensor(first, "first", (torch.int32,), "[N, K]", lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)
+    T.check_tensor(first, "first", (torch.int32,), "[N, K]", lambda s: len(s) == 2 and s[0] >= 1 and s[1] >= 1)
     _check_mapping(then, int(first.shape[0]), what="then")
     for t, what in ((first, "first"), (then, "then")):
-        _check_device(t, what)
+        T.check_device(t, what)
     if first.device != then.device:
         raise ValueError("first and then must be on one GPU, got %s and %s" % (first.device, then.device))
     ok = (first >= 0) & (first < then.shape[1])

@@ -13,36 +13,25 @@ at down-right and down-left: every unordered pixel pair of the whole plane exact
 SlicModel.get_connectivity, which reproduces the reference's scan and its cap of 12 neighbours).  All of it is integer arithmetic:
 results are exact and bitwise reproducible.  This module imports torch; the package itself does not import it.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _binding as B, _pairtable as T
-from ._pairtable import _MAX_CAPACITY, _pow2_at_least
-from .pool import _check_num_components, _labels_on, _stream
+from . import _binding as B, _pairtable as PT, _tensors as T
 
 __all__ = ["superpixel_graph", "SuperpixelGraph"]
 
 MAX_CHANNELS = 4
 
 
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_rag_accumulate"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no region adjacency graph entry points; rebuild it")
-    return lib
-
-
 def first_capacity(K):
     """Slots per frame of the first pair table: sized for a planar map (a Slic map has about 2.9 K edges), under half load."""
-    return max(1024, _pow2_at_least(8 * K))
+    return max(1024, PT.pow2_at_least(8 * K))
 
 
 def capacity_limit(K, H, W, connectivity):
     """Slots per frame that hold any map of this shape at half load: no more distinct pairs than label pairs or pixel pairs."""
     pairs = min(K * (K - 1) // 2, (connectivity // 2) * H * W)
-    return min(_MAX_CAPACITY, max(first_capacity(K), _pow2_at_least(2 * pairs)))
+    return min(PT.MAX_CAPACITY, max(first_capacity(K), PT.pow2_at_least(2 * pairs)))
 
 
 class SuperpixelGraph(object):
@@ -88,6 +77,40 @@ class SuperpixelGraph(object):
         return offsets, (flat - rows * K).to(torch.int32)
 
 
+# ---- a SuperpixelGraph as an argument (merge.py, regions.py): its checks run before any device work ----
+def check_graph(graph):
+    """-> (N, K, E, C) of a SuperpixelGraph whose fields have the types and shapes superpixel_graph gives them."""
+    if not isinstance(graph, SuperpixelGraph):
+        raise ValueError("graph must be a SuperpixelGraph")
+    K = T.check_count(graph.num_components, "num_components")
+    T.check_tensor(graph.edge_index, "graph.edge_index", (torch.int64,), "[2, E]", lambda s: len(s) == 2 and s[0] == 2)
+    E = int(graph.edge_index.shape[1])
+    T.check_tensor(graph.offsets, "graph.offsets", (torch.int64,), "[N + 1]", lambda s: len(s) == 1 and s[0] >= 2)
+    N = int(graph.offsets.shape[0]) - 1
+    if E >= 1 << 31:
+        raise ValueError("the graph must have fewer than 2^31 edges")
+    if N * K >= 1 << 31:
+        raise ValueError("N * num_components must be below 2^31")
+    T.check_tensor(graph.boundary, "graph.boundary", (torch.int32,), "[E]", lambda s: s == (E,))
+    Cc = 0
+    if graph.contrast is not None:
+        T.check_tensor(graph.contrast, "graph.contrast", (torch.int64,), "[E, C] with C in 1 .. %d" % MAX_CHANNELS,
+                       lambda s: len(s) == 2 and s[0] == E and 1 <= s[1] <= MAX_CHANNELS)
+        Cc = int(graph.contrast.shape[1])
+    return N, K, E, Cc
+
+
+def graph_device(graph, others):
+    """The GPU of the graph; others: ((tensor or None, name), ...) must be there too.  A CPU tensor is the last thing refused."""
+    return T.one_device([(graph.edge_index, "graph.edge_index"), (graph.offsets, "graph.offsets"), (graph.boundary, "graph.boundary"),
+                         (graph.contrast, "graph.contrast")] + list(others))
+
+
+def graph_edges(graph):
+    """-> (edge_index, offsets), contiguous: what every entry that takes a graph is given."""
+    return graph.edge_index.contiguous(), graph.offsets.contiguous()
+
+
 # ---- argument checks: all of them run before any device work ----
 def _check_image(image, shape):
     if isinstance(image, np.ndarray):
@@ -120,41 +143,36 @@ def superpixel_graph(labels, num_components, connectivity=4, image=None, *, devi
     H, W = (int(v) for v in labels.shape[-2:])
     if H * W >= 1 << 29:
         raise ValueError("H * W must be below 2^29")
-    K = _check_num_components(num_components)
+    K = T.check_count(num_components, "num_components")
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8, got %r" % (connectivity,))
     connectivity = int(connectivity)
     if image is not None:
         _check_image(image, labels.shape)
-    capacity, limit = T.start_capacity(first_capacity(K), capacity_limit(K, H, W, connectivity), _start_capacity)
-    dev = T.pick_device(((labels, "labels"), (image, "image")), device)
+    capacity, limit = PT.start_capacity(first_capacity(K), capacity_limit(K, H, W, connectivity), _start_capacity)
+    dev = T.one_device(((labels, "labels"), (image, "image")), device)
 
-    lib = _lib()
+    lib = T.library("fslic_hip_rag_accumulate", "region adjacency graph entry points")
     batched = labels.ndim == 3
-    lab, ltype = _labels_on(labels, dev)
-    if not batched:
-        lab = lab.unsqueeze(0)
+    lab, ltype = T.labels_on(labels, dev, batched)
     img = None
     if image is not None:
-        img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(device=dev).contiguous()
-        if not batched:
-            img = img.unsqueeze(0)
+        img = (torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image).to(device=dev)
+        img = T.batch_of(img, batched)
     N, Cc = lab.shape[0], img.shape[-1] if img is not None else 0
 
     def accumulate(capacity):
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_rag_workspace_size(N, K, Cc, capacity, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        B._check(lib.fslic_hip_rag_accumulate(dev.index, _stream(dev), N, H, W, K, connectivity, lab.data_ptr(), ltype,
-                                              img.data_ptr() if img is not None else None, Cc, capacity, ws.data_ptr(), nbytes.value))
-        return ws, nbytes.value
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_rag_workspace_size, N, K, Cc, capacity)
+        B._check(lib.fslic_hip_rag_accumulate(dev.index, T.stream(dev), N, H, W, K, connectivity, lab.data_ptr(), ltype, T.ptr(img), Cc,
+                                              capacity, ws.data_ptr(), nbytes))
+        return ws, nbytes
 
     def compact(ws, nbytes, capacity, E, keys, boundary, contrast=None):
-        B._check(lib.fslic_hip_rag_compact(dev.index, _stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
-                                           boundary.data_ptr(), contrast.data_ptr() if contrast is not None else None, E))
+        B._check(lib.fslic_hip_rag_compact(dev.index, T.stream(dev), N, Cc, capacity, ws.data_ptr(), nbytes, keys.data_ptr(),
+                                           boundary.data_ptr(), T.ptr(contrast), E))
 
     with torch.cuda.device(dev):
-        edge_index, boundary, extra, offsets, capacity = T.run(accumulate, compact, N, capacity, limit, dev,
-                                                               [((Cc,), torch.int64)] if img is not None else [])
+        edge_index, boundary, extra, offsets, capacity = PT.run(accumulate, compact, N, capacity, limit, dev,
+                                                                [((Cc,), torch.int64)] if img is not None else [])
     contrast = extra[0] if extra else None
     return SuperpixelGraph(edge_index, boundary, contrast, offsets, K, capacity)

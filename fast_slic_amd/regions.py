@@ -48,26 +48,20 @@ synchronise the host (limit_joins is plain torch: a stable sort of the 64-bit ke
 synchronisation to contract_graph's, whose edge count is all its stopping rules read.  There is no CPU fallback.
 This module imports torch; the package itself does not import it.
 """
-import ctypes as C
 import numbers
 
 import torch
 
-from . import _binding as B
-from .merge import (_MEMBER_TYPE, _check_graph, _check_tensor, _edges, _graph_device, best_neighbour_edges, compose_mappings,
-                    contract_graph, merge_components)
-from .pool import MAX_COMPONENTS, _check_device, _stream
+from . import _binding as B, _tensors as T
+from .merge import best_neighbour_edges, compose_mappings, contract_graph, merge_components
+from .rag import check_graph, graph_device, graph_edges
 
 __all__ = ["group_sums", "edge_weights", "limit_joins", "merge_hierarchical", "MergeResult"]
 
 _MODES = {"mean": 0, "ward": 1}                                            # kRegionMean, kRegionWard
 
 
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_region_sums"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no region feature entry points; rebuild it")
-    return lib
+_ENTRY = ("fslic_hip_region_sums", "region feature entry points")
 
 
 class MergeResult(object):
@@ -81,8 +75,8 @@ class MergeResult(object):
 # ---- argument checks: all of them run before any device work ----
 def _check_values(values, what, N, K):
     """-> C of a float32 [N, C, K] tensor ([C, K] allowed when N = 1)."""
-    _check_tensor(values, what, (torch.float32,), "[N, C, K] = [%d, C, %d]%s with C >= 1" % (N, K, " or [C, K]" if N == 1 else ""),
-                  lambda s: (len(s) == 3 and s[0] == N and s[1] >= 1 and s[2] == K) or (N == 1 and len(s) == 2 and s[0] >= 1 and s[1] == K))
+    T.check_tensor(values, what, (torch.float32,), "[N, C, K] = [%d, C, %d]%s with C >= 1" % (N, K, " or [C, K]" if N == 1 else ""),
+                   lambda s: (len(s) == 3 and s[0] == N and s[1] >= 1 and s[2] == K) or (N == 1 and len(s) == 2 and s[0] >= 1 and s[1] == K))
     Cc = int(values.shape[-2])
     if N * Cc * K >= 1 << 31:
         raise ValueError("N * C * K must be below 2^31, got %s of shape %s" % (what, tuple(values.shape)))
@@ -90,8 +84,8 @@ def _check_values(values, what, N, K):
 
 
 def _check_counts(counts, N, K, what="counts"):
-    _check_tensor(counts, what, tuple(_MEMBER_TYPE), "[N, K] = [%d, %d]%s" % (N, K, " or [K]" if N == 1 else ""),
-                  lambda s: s == (N, K) or (N == 1 and s == (K,)))
+    T.check_tensor(counts, what, tuple(T.MEMBER_TYPE), "[N, K] = [%d, %d]%s" % (N, K, " or [K]" if N == 1 else ""),
+                   lambda s: s == (N, K) or (N == 1 and s == (K,)))
 
 
 def _check_mode(mode):
@@ -100,66 +94,53 @@ def _check_mode(mode):
     return _MODES[mode]
 
 
-def _one_device(given):
-    """The GPU of the tensors ((tensor or None, name), ...).  A CPU tensor is the last thing refused."""
-    given = [(t, what) for t, what in given if t is not None]
-    devs = {t.device for t, _ in given if t.device.type == "cuda"}
-    if len(devs) > 1:
-        raise ValueError("%s must be on one GPU, got %s" % (", ".join(what for _, what in given), sorted(str(d) for d in devs)))
-    for t, what in given:
-        _check_device(t, what)
-    return devs.pop()
-
-
 def group_sums(values, mapping, num_groups, counts=None):
     """float32 [N, C, K2], and with `counts` (that, counts' dtype [N, K2]): the sums of `values` float32 [N, C, K] ([C, K] when N = 1)
     and of `counts` int32 / int64 [N, K] over the groups of `mapping` int32 [N, K], K2 = num_groups (rule 1 of the module's text).
     Exact and reproducible; two launches behind two clears, no host synchronisation, no gradients."""
-    _check_tensor(mapping, "mapping", (torch.int32,), "[N, K]", lambda s: len(s) == 2 and s[0] >= 1 and 1 <= s[1] <= MAX_COMPONENTS)
+    T.check_tensor(mapping, "mapping", (torch.int32,), "[N, K]", lambda s: len(s) == 2 and s[0] >= 1 and 1 <= s[1] <= T.MAX_COMPONENTS)
     N, K = (int(v) for v in mapping.shape)
     Cc = _check_values(values, "values", N, K)
-    if isinstance(num_groups, bool) or not isinstance(num_groups, numbers.Integral) or not 1 <= int(num_groups) <= MAX_COMPONENTS:
-        raise ValueError("num_groups must be an integer in [1, %d], got %r" % (MAX_COMPONENTS, num_groups))
+    if isinstance(num_groups, bool) or not isinstance(num_groups, numbers.Integral) or not 1 <= int(num_groups) <= T.MAX_COMPONENTS:
+        raise ValueError("num_groups must be an integer in [1, %d], got %r" % (T.MAX_COMPONENTS, num_groups))
     K2 = int(num_groups)
     if N * Cc * K2 >= 1 << 31:
         raise ValueError("N * C * num_groups must be below 2^31")
     if counts is not None:
         _check_counts(counts, N, K)
-    dev = _one_device(((values, "values"), (mapping, "mapping"), (counts, "counts")))
+    dev = T.one_device(((values, "values"), (mapping, "mapping"), (counts, "counts")))
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
         val, mp = values.detach().contiguous(), mapping.contiguous()
         cnt = counts.contiguous() if counts is not None else None
         sums = torch.empty((N, Cc, K2), dtype=torch.float32, device=dev)
         out_counts = torch.empty((N, K2), dtype=cnt.dtype, device=dev) if cnt is not None else None
-        nbytes = C.c_size_t()
-        B._check(lib.fslic_hip_region_sums_workspace_size(N, Cc, K2, C.byref(nbytes)))
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        B._check(lib.fslic_hip_region_sums(dev.index, _stream(dev), N, Cc, K, K2, val.data_ptr(), mp.data_ptr(),
-                                           cnt.data_ptr() if cnt is not None else None, _MEMBER_TYPE[cnt.dtype] if cnt is not None else 0,
-                                           sums.data_ptr(), out_counts.data_ptr() if cnt is not None else None, ws.data_ptr(), nbytes.value))
+        ws, nbytes = T.scratch(dev, lib.fslic_hip_region_sums_workspace_size, N, Cc, K2)
+        B._check(lib.fslic_hip_region_sums(dev.index, T.stream(dev), N, Cc, K, K2, val.data_ptr(), mp.data_ptr(), T.ptr(cnt),
+                                           T.MEMBER_TYPE[cnt.dtype] if cnt is not None else 0, sums.data_ptr(), T.ptr(out_counts),
+                                           ws.data_ptr(), nbytes))
     return sums if counts is None else (sums, out_counts)
 
 
 def edge_weights(graph, sums, counts, mode="mean"):
     """float32 [E]: the weight of every edge from the means of its two regions (rule 2 of the module's text).  `sums` float32
     [N, C, K], `counts` int32 / int64 [N, K] on the graph's GPU; mode "mean" or "ward".  One launch, no host synchronisation."""
-    N, K, E, _ = _check_graph(graph)
+    N, K, E, _ = check_graph(graph)
     Cc = _check_values(sums, "sums", N, K)
     _check_counts(counts, N, K)
     m = _check_mode(mode)
-    dev = _graph_device(graph, ((sums, "sums"), (counts, "counts")))
+    dev = graph_device(graph, ((sums, "sums"), (counts, "counts")))
 
-    lib = _lib()
+    lib = T.library(*_ENTRY)
     with torch.cuda.device(dev):
         weight = torch.empty(E, dtype=torch.float32, device=dev)
         if E == 0:
             return weight
-        ei, offsets = _edges(graph)
+        ei, offsets = graph_edges(graph)
         s, cnt = sums.detach().contiguous(), counts.contiguous()
-        B._check(lib.fslic_hip_region_edge_weights(dev.index, _stream(dev), N, Cc, K, E, ei.data_ptr(), offsets.data_ptr(), s.data_ptr(),
-                                                   cnt.data_ptr(), _MEMBER_TYPE[cnt.dtype], m, weight.data_ptr()))
+        B._check(lib.fslic_hip_region_edge_weights(dev.index, T.stream(dev), N, Cc, K, E, ei.data_ptr(), offsets.data_ptr(), s.data_ptr(),
+                                                   cnt.data_ptr(), T.MEMBER_TYPE[cnt.dtype], m, weight.data_ptr()))
     return weight
 
 
@@ -167,11 +148,11 @@ def limit_joins(graph, weight, join, quota):
     """bool [E]: of frame f's edges with `join` true and a finite weight, the quota[f] with the smallest (weight, position) stay true
     (rule 3 of the module's text).  `weight` float32 [E], `join` bool [E], `quota` int32 / int64 [N].  Plain torch: a stable sort of
     the 64-bit keys, then of the frames; no host synchronisation."""
-    N, K, E, _ = _check_graph(graph)
-    _check_tensor(weight, "weight", (torch.float32,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
-    _check_tensor(join, "join", (torch.bool,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
-    _check_tensor(quota, "quota", tuple(_MEMBER_TYPE), "[N] with N = %d, one per frame" % N, lambda s: s == (N,))
-    dev = _graph_device(graph, ((weight, "weight"), (join, "join"), (quota, "quota")))
+    N, K, E, _ = check_graph(graph)
+    T.check_tensor(weight, "weight", (torch.float32,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
+    T.check_tensor(join, "join", (torch.bool,), "[E] with E = %d, one per edge of the graph" % E, lambda s: s == (E,))
+    T.check_tensor(quota, "quota", tuple(T.MEMBER_TYPE), "[N] with N = %d, one per frame" % N, lambda s: s == (N,))
+    dev = graph_device(graph, ((weight, "weight"), (join, "join"), (quota, "quota")))
 
     with torch.cuda.device(dev):
         if E == 0:
@@ -194,7 +175,7 @@ def merge_hierarchical(graph, sums, counts, threshold=None, target=None, max_rou
     """A MergeResult (mapping, n, graph, sums, counts): the rounds of rule 4 of the module's text.  `threshold` None or a number: only
     edges with a weight below it join; `target` None or an integer >= 1: no frame goes below that many regions; at most `max_rounds`
     rounds.  One host synchronisation a round, contract_graph's."""
-    N, K, E, _ = _check_graph(graph)
+    N, K, E, _ = check_graph(graph)
     Cc = _check_values(sums, "sums", N, K)
     _check_counts(counts, N, K)
     if threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, numbers.Real)):
@@ -204,7 +185,7 @@ def merge_hierarchical(graph, sums, counts, threshold=None, target=None, max_rou
     if isinstance(max_rounds, bool) or not isinstance(max_rounds, numbers.Integral) or max_rounds < 1:
         raise ValueError("max_rounds must be an integer >= 1, got %r" % (max_rounds,))
     _check_mode(mode)
-    dev = _graph_device(graph, ((sums, "sums"), (counts, "counts")))
+    dev = graph_device(graph, ((sums, "sums"), (counts, "counts")))
 
     with torch.cuda.device(dev):
         sums0, counts0 = sums.detach().reshape(N, Cc, K).contiguous(), counts.reshape(N, K).contiguous()

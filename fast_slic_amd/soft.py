@@ -18,23 +18,17 @@ superpixel gathers from its own window in a fixed order, so results are bitwise 
 of the other channels.  Every function is differentiable once (features, centres, values, Q).  This module imports torch; the package
 itself does not import it.
 """
-import ctypes as C
 import numbers
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _binding as B
-from .pool import MAX_COMPONENTS, _check_device, _check_float_map, _stream
+from . import _binding as B, _tensors as T
 
 __all__ = ["soft_assign", "soft_pool", "soft_unpool", "soft_labels", "soft_slic", "with_coords"]
 
 
-def _lib():
-    lib = B.load_library()
-    if not hasattr(lib, "fslic_hip_soft_assign"):
-        raise RuntimeError("fast_slic_amd: the loaded library has no soft assignment entry points; rebuild it")
-    return lib
+_ENTRY = ("fslic_hip_soft_assign", "soft assignment entry points")
 
 
 # ---- argument checks: all of them run before any device work ----
@@ -46,8 +40,8 @@ def _check_grid(grid, H, W):
     gh, gw = int(grid[0]), int(grid[1])
     if not (1 <= gh <= H and 1 <= gw <= W):
         raise ValueError("grid must satisfy 1 <= gh <= H and 1 <= gw <= W, got %s for %d x %d pixels" % ((gh, gw), H, W))
-    if gh * gw > MAX_COMPONENTS:
-        raise ValueError("grid must have at most %d cells, got %d" % (MAX_COMPONENTS, gh * gw))
+    if gh * gw > T.MAX_COMPONENTS:
+        raise ValueError("grid must have at most %d cells, got %d" % (T.MAX_COMPONENTS, gh * gw))
     if H * W >= 1 << 31:
         raise ValueError("H * W must be below 2^31")
     return gh, gw
@@ -55,19 +49,19 @@ def _check_grid(grid, H, W):
 
 def _check_map(t, what):
     """features-like: [C, H, W] or [N, C, H, W] -> batched?"""
-    _check_float_map(t, (3, 4), what, "[C, H, W] or [N, C, H, W]")
+    T.check_float_map(t, (3, 4), what, "[C, H, W] or [N, C, H, W]")
     return t.dim() == 4
 
 
 def _check_table(t, what, batched, lead, K):
     """centres / values: [C, K] or [N, C, K] matching the batch and the grid; lead: the expected (N,) or ()"""
-    _check_float_map(t, (3,) if batched else (2,), what, "[N, C, K]" if batched else "[C, K]")
+    T.check_float_map(t, (3,) if batched else (2,), what, "[N, C, K]" if batched else "[C, K]")
     if tuple(t.shape[:len(lead)]) != tuple(lead) or t.shape[-1] != K:
         raise ValueError("%s must have shape %s to match the batch and the grid, got %s" % (what, tuple(lead) + ("C", K), tuple(t.shape)))
 
 
 def _check_q(q, batched, lead, H, W):
-    _check_float_map(q, (4,) if batched else (3,), "Q", "[N, 9, H, W]" if batched else "[9, H, W]")
+    T.check_float_map(q, (4,) if batched else (3,), "Q", "[N, 9, H, W]" if batched else "[9, H, W]")
     want = tuple(lead) + (9, H, W)
     if tuple(q.shape) != want:
         raise ValueError("Q must have shape %s, got %s" % (want, tuple(q.shape)))
@@ -78,19 +72,15 @@ def _same_device(a, b, what):
         raise ValueError("%s must be on the device of the other tensors (%s), got %s" % (what, a.device, b.device))
 
 
-def _b(t, batched):
-    return (t if batched else t.unsqueeze(0)).contiguous()
-
-
 # ---- the raw calls: contiguous [N, ...] tensors on one device ----
 def _geom(t, N, Cc, H, W, grid):
-    return (t.device.index, _stream(t.device), N, Cc, H, W, grid[0], grid[1])
+    return (t.device.index, T.stream(t.device), N, Cc, H, W, grid[0], grid[1])
 
 
 def _assign_raw(feat, cen, grid):
     N, Cc, H, W = feat.shape
     q = torch.empty((N, 9, H, W), dtype=torch.float32, device=feat.device)
-    B._check(_lib().fslic_hip_soft_assign(*_geom(feat, N, Cc, H, W, grid), feat.data_ptr(), cen.data_ptr(), q.data_ptr()))
+    B._check(T.library(*_ENTRY).fslic_hip_soft_assign(*_geom(feat, N, Cc, H, W, grid), feat.data_ptr(), cen.data_ptr(), q.data_ptr()))
     return q
 
 
@@ -99,9 +89,8 @@ def _pool_raw(feat, q, grid, centres=None, weights=True):
     K = grid[0] * grid[1]
     sums = torch.empty((N, Cc, K), dtype=torch.float32, device=feat.device)
     wts = torch.empty((N, K), dtype=torch.float32, device=feat.device) if weights else None
-    B._check(_lib().fslic_hip_soft_pool(*_geom(feat, N, Cc, H, W, grid), feat.data_ptr(), q.data_ptr(),
-                                        centres.data_ptr() if centres is not None else None, sums.data_ptr(),
-                                        wts.data_ptr() if wts is not None else None))
+    B._check(T.library(*_ENTRY).fslic_hip_soft_pool(*_geom(feat, N, Cc, H, W, grid), feat.data_ptr(), q.data_ptr(),
+                                                    T.ptr(centres), sums.data_ptr(), T.ptr(wts)))
     return sums, wts
 
 
@@ -109,15 +98,14 @@ def _unpool_raw(values, q, grid):
     N, Cc, _ = values.shape
     H, W = q.shape[-2:]
     out = torch.empty((N, Cc, H, W), dtype=torch.float32, device=values.device)
-    B._check(_lib().fslic_hip_soft_unpool(*_geom(values, N, Cc, H, W, grid), values.data_ptr(), q.data_ptr(), out.data_ptr()))
+    B._check(T.library(*_ENTRY).fslic_hip_soft_unpool(*_geom(values, N, Cc, H, W, grid), values.data_ptr(), q.data_ptr(), out.data_ptr()))
     return out
 
 
 def _dot_raw(a, b, bias, grid):
     N, Cc, H, W = a.shape
     out = torch.empty((N, 9, H, W), dtype=torch.float32, device=a.device)
-    B._check(_lib().fslic_hip_soft_dot(*_geom(a, N, Cc, H, W, grid), a.data_ptr(), b.data_ptr(),
-                                       bias.data_ptr() if bias is not None else None, out.data_ptr()))
+    B._check(T.library(*_ENTRY).fslic_hip_soft_dot(*_geom(a, N, Cc, H, W, grid), a.data_ptr(), b.data_ptr(), T.ptr(bias), out.data_ptr()))
     return out
 
 
@@ -136,8 +124,8 @@ class _Assign(torch.autograd.Function):
         N, Cc, H, W = feat.shape
         gq = gq.contiguous()
         gd, gf = torch.empty_like(q), torch.empty_like(feat)
-        B._check(_lib().fslic_hip_soft_assign_backward(*_geom(feat, N, Cc, H, W, ctx.grid), feat.data_ptr(), cen.data_ptr(), q.data_ptr(),
-                                                       gq.data_ptr(), gd.data_ptr(), gf.data_ptr()))
+        B._check(T.library(*_ENTRY).fslic_hip_soft_assign_backward(*_geom(feat, N, Cc, H, W, ctx.grid), feat.data_ptr(), cen.data_ptr(),
+                                                                   q.data_ptr(), gq.data_ptr(), gd.data_ptr(), gf.data_ptr()))
         gs = None
         if ctx.needs_input_grad[1]:          # -2 sum_p gd (F - S[k]), accumulated as written: no difference of two pooled sums
             gs = _pool_raw(feat, gd, ctx.grid, centres=cen, weights=False)[0].mul_(-2.0)
@@ -191,9 +179,9 @@ def soft_assign(features, centres, grid):
     _check_table(centres, "centres", batched, lead, gh * gw)
     if centres.shape[-2] != features.shape[-3]:
         raise ValueError("centres must have the features' %d channels, got %d" % (features.shape[-3], centres.shape[-2]))
-    _check_device(features, "features")
+    T.check_device(features, "features")
     _same_device(features, centres, "centres")
-    q = _Assign.apply(_b(features, batched), _b(centres, batched), (gh, gw))
+    q = _Assign.apply(T.batch_of(features, batched), T.batch_of(centres, batched), (gh, gw))
     return q if batched else q.squeeze(0)
 
 
@@ -205,9 +193,9 @@ def soft_pool(features, Q, grid, normalize=True, return_weights=False):
     H, W = features.shape[-2:]
     gh, gw = _check_grid(grid, H, W)
     _check_q(Q, batched, tuple(features.shape[:1]) if batched else (), H, W)
-    _check_device(features, "features")
+    T.check_device(features, "features")
     _same_device(features, Q, "Q")
-    sums, weights = _Pool.apply(_b(features, batched), _b(Q, batched), (gh, gw))
+    sums, weights = _Pool.apply(T.batch_of(features, batched), T.batch_of(Q, batched), (gh, gw))
     out = sums
     if normalize:
         w = weights.unsqueeze(1)
@@ -229,9 +217,9 @@ def soft_unpool(values, Q, grid):
     _check_q(Q, batched, lead, H, W)
     gh, gw = _check_grid(grid, H, W)
     _check_table(values, "values", batched, lead, gh * gw)
-    _check_device(values, "values")
+    T.check_device(values, "values")
     _same_device(values, Q, "Q")
-    out = _Unpool.apply(_b(values, batched), _b(Q, batched), (gh, gw))
+    out = _Unpool.apply(T.batch_of(values, batched), T.batch_of(Q, batched), (gh, gw))
     return out if batched else out.squeeze(0)
 
 
@@ -275,8 +263,8 @@ def soft_slic(features, grid, max_iter=10):
     gh, gw = _check_grid(grid, H, W)
     if isinstance(max_iter, bool) or not isinstance(max_iter, numbers.Integral) or max_iter < 0:
         raise ValueError("max_iter must be a non-negative integer")
-    _check_device(features, "features")
-    feat = _b(features, batched)
+    T.check_device(features, "features")
+    feat = T.batch_of(features, batched)
     q0 = torch.zeros((feat.shape[0], 9, H, W), dtype=torch.float32, device=feat.device)
     q0[:, 4] = 1.0
     centres = soft_pool(feat, q0, (gh, gw))

@@ -85,7 +85,7 @@ def main():
         Q = S.soft_assign(F, cen, grid)
         gQ, gS, gW, gO = torch.randn_like(Q), torch.randn(N, Cc, K, device=dev), torch.randn(N, K, device=dev), torch.randn_like(F)
         gd, gF = torch.empty_like(Q), torch.empty_like(F)
-        lib = S._lib()
+        lib = S.T.library(*S._ENTRY)
         geom = S._geom(F, N, Cc, H, W, grid)
         res = {}
         # the kernels, one launch each

@@ -30,6 +30,57 @@ def test_library_exports_every_declared_symbol():
     assert sorted(names) == sorted(B.EXPORTS)
 
 
+def declared_prototypes():
+    """name -> (return class, [parameter classes]) of every prototype of include/fslic_hip.h.  A class is "pointer" (any T*, T* const*
+    or T name[n]), "int", "long long", "size_t", "float" or "double"; a return may also be "void" or "const char*"."""
+    src = open(os.path.join(ROOT, "include", "fslic_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    values = {"int", "long long", "size_t", "float", "double"}
+
+    def parameter(text):
+        if "*" in text or "[" in text:
+            return "pointer"
+        kind = " ".join(w for w in text.split()[:-1] if w != "const")      # the words before the parameter's name
+        assert kind in values, "a parameter %r that is no pointer and none of %s" % (text, sorted(values))
+        return kind
+
+    out = {}
+    for ret, name, args in re.findall(r"^([A-Za-z_][\w \*]*?)\s*\b(fslic_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+        ret = " ".join(ret.replace("*", " * ").split()).replace(" *", "*")
+        assert ret in values - {"float", "double"} | {"void", "const char*"}, (name, ret)
+        args = " ".join(args.split())
+        assert name not in out, name
+        out[name] = (ret, [] if args == "void" else [parameter(a.strip()) for a in args.split(",")])
+    return out
+
+
+def test_signature_table_matches_the_header():
+    """Every prototype of the header against _binding.SIGNATURES: as many parameters, each of the same class, and the same class of
+    return.  A wrong width in a hand-written argtypes list would otherwise pass every CPU test."""
+    import ctypes as C
+    by_type = {C.c_int: "int", C.c_longlong: "long long", C.c_size_t: "size_t", C.c_float: "float", C.c_double: "double"}
+    assert len(by_type) == 5      # (c_size_t and c_longlong are different ctypes types here, so the table can tell them apart)
+
+    def of(ctype):
+        if ctype in (C.c_void_p, C.c_char_p) or isinstance(ctype, type(C.POINTER(C.c_int))):
+            return "pointer"
+        return by_type[ctype]
+
+    header = declared_prototypes()
+    assert sorted(header) == declared_symbols()
+    table = {name: (restype, argtypes) for name, restype, argtypes in B.SIGNATURES}
+    assert len(table) == len(B.SIGNATURES) and sorted(table) == sorted(header)
+    for name, (ret, args) in header.items():
+        restype, argtypes = table[name]
+        got = "void" if restype is None else "const char*" if restype is C.c_char_p else by_type[restype]
+        assert got == ret, "%s returns %s in the header and %s in the table" % (name, ret, got)
+        assert [of(t) for t in argtypes] == args, "%s: the header has %s, the table %s" % (name, args, [of(t) for t in argtypes])
+    lib = B.load_library()
+    for name, restype, argtypes in B.SIGNATURES:      # and the loaded library carries what the table says
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
 def test_cluster_abi_is_32_bytes_with_reference_offsets():
     d = B.CLUSTER_DTYPE
     assert d.itemsize == 32

@@ -309,8 +309,8 @@ def test_cpu_tensors_are_refused_after_every_other_check():
 
 def test_mismatched_devices_are_named_before_a_cpu_tensor():
     """No GPU here, let alone two: the device check is exercised through the helpers with stand-ins that have a device and nothing else."""
-    from fast_slic_amd.merge import _graph_device
-    from fast_slic_amd.regions import _one_device
+    from fast_slic_amd._tensors import one_device as _one_device
+    from fast_slic_amd.rag import graph_device as _graph_device
 
     class On(object):
         def __init__(self, device):
