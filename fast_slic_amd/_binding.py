@@ -182,6 +182,13 @@ def _signatures():
         # frames of any tensor layout into the engine's form (fast_slic_amd/frames.py)
         ("fslic_hip_pack_rgb", i32, [i32, vp, i32, i32, i32, vp, i32, P(i64), f32, vp, sz]),
     ]
+    # aggregation over neighbour lists (fast_slic_amd/propagate.py)
+    lists = [i32, vp, i32, i32, i32, i64]      # device, stream, N, C, K, nnz
+    table += [
+        ("fslic_hip_aggregate_forward", i32, lists + [i32, vp, vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_aggregate_backward_values", i32, lists + [i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_aggregate_backward_weight", i32, lists + [vp, vp, vp, vp, vp]),
+    ]
     return table
 
 

@@ -562,6 +562,36 @@ int fslic_hip_region_sums(int device, void* stream, int N, int C, int K, int K2,
 int fslic_hip_region_edge_weights(int device, void* stream, int N, int C, int K, long long E, const int64_t* edge_index,
                                   const int64_t* offsets, const float* sums, const void* counts, int counts_type, int mode, float* weight);
 
+/* ---- Aggregation over neighbour lists (NEW surface; Python: fast_slic_amd/propagate.py, which states the rules) ----
+ * Entries as for the regions: a device index and a stream, no synchronisation, no allocation, no workspace, no copy to the host, the
+ * caller's device restored, every argument checked before the first HIP call (FSLIC_E_INVALID).  N frames, C >= 1 channels, K in
+ * [1, 65534] nodes, N * C * K below 2^31, nnz in [0, 2^31) entries.  The lists are one CSR over the N * K rows (frame, node):
+ * offsets int64 [N * K + 1], indices int32 [nnz] (node numbers inside the frame), weight float [nnz] or NULL.  What the device arrays
+ * hold is checked by the kernels before it becomes an address: row bounds are clamped into [0, nnz], an end before its start is an
+ * empty row, and an entry whose index is outside [0, K) is not valid and contributes nothing.  Every float operation is one IEEE
+ * operation rounded on its own, nothing fused, the division correctly rounded; no atomics: the same bits from run to run.
+ *
+ * Forward.  reduce 0 (sum): out[n][c][i] = the left fold from +0.0 over the valid entries p of row (n, i), ascending, of
+ * weight[p] * values[n][c][indices[p]] (values[...] itself without a weight).  reduce 1 (mean): that sum without a weight, divided by
+ * (float)d, d = the row's valid entries, +0.0 for d = 0; degree (int32 [N * K], required) receives d.  reduce 2 (max): the largest
+ * value over the valid entries, +0.0 for d = 0; argmax (int32 [N][C][K], required) receives the smallest p that attains it, -1 for
+ * d = 0; NaN values leave the cell unspecified.  A weight goes with reduce 0 only.  One launch. */
+int fslic_hip_aggregate_forward(int device, void* stream, int N, int C, int K, long long nnz, int reduce, const int64_t* offsets,
+                                const int32_t* indices, const float* weight, const float* values, float* out, int32_t* argmax, int32_t* degree);
+/* Backward to the values over the transposed lists: the entries whose index is node j of frame n are t_entries[t_offsets[n * K + j] ..
+ * t_offsets[n * K + j + 1]) (int32 [nnz], ascending), t_rows (int32 [nnz]) the row over (frame, node) of each; an entry outside
+ * [0, nnz) or a row outside frame n contributes nothing.  grad_values[n][c][j] = the left fold from +0.0 over them of
+ * weight[p] * grad_out[n][c][row(p)] (sum; grad_out[...] itself without a weight), grad_out[n][c][row(p)] / (float)degree[row(p)]
+ * (mean; degree as the forward wrote it), or grad_out[n][c][row(p)] where argmax[n][c][row(p)] == p (max).  One launch. */
+int fslic_hip_aggregate_backward_values(int device, void* stream, int N, int C, int K, long long nnz, int reduce, const int64_t* t_offsets,
+                                        const int32_t* t_entries, const int32_t* t_rows, const float* weight, const int32_t* argmax,
+                                        const int32_t* degree, const float* grad_out, float* grad_values);
+/* Backward of the sum to the weights: grad_weight[p] = the left fold from +0.0 over c = 0 .. C - 1 of values[n][c][indices[p]] *
+ * grad_out[n][c][i], with (n, i) = rows[p] (int32 [nnz], the row over (frame, node) of each entry); +0.0 where rows[p] is outside
+ * [0, N * K) or indices[p] outside [0, K).  One thread an entry; one launch, none for nnz == 0. */
+int fslic_hip_aggregate_backward_weight(int device, void* stream, int N, int C, int K, long long nnz, const int32_t* rows, const int32_t* indices,
+                                        const float* values, const float* grad_out, float* grad_weight);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
