@@ -1,7 +1,5 @@
 // aggregateapi.cpp -- the C ABI of the aggregation over neighbour lists (include/fslic_hip.h, fslic_hip_aggregate*; kernels in
-// aggregate.hip).  No engine: the caller names the device and the stream and owns every buffer.  Every argument is checked before the
-// first HIP call; nothing here synchronises, allocates or copies to the host.
-#include "engine_internal.h"
+// aggregate.hip), on streamapi.h; nothing here synchronises, allocates or copies to the host.
 #include "aggregate.h"
 #include "streamapi.h"
 
@@ -11,13 +9,9 @@ namespace {
 
 // the device, the cells of a [N][C][K] array and the entries of the lists
 int check_call(int device, int N, int C, int K, long long nnz) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
-    if (N < 1) return fail(FSLIC_E_INVALID, "N must be positive");
-    if (C < 1) return fail(FSLIC_E_INVALID, "C must be positive");
-    if (K < 1 || K > 65534) return fail(FSLIC_E_INVALID, "K must be in [1, 65534]");
-    if ((long long)N * K >= (1ll << 31) || (long long)N * K * C >= (1ll << 31)) return fail(FSLIC_E_INVALID, "N * C * K must be below 2^31");
-    if (nnz < 0 || nnz >= (1ll << 31)) return fail(FSLIC_E_INVALID, "nnz must be in [0, 2^31)");
-    return FSLIC_OK;
+    int rc = check_device(device);
+    if (rc || (rc = check_cells(N, C, K, "K"))) return rc;
+    return check_entry_count(nnz, "nnz");
 }
 
 // the reduction and what goes with it: a weight only with the sum, the argmax with the max, the degree with the mean
@@ -38,11 +32,10 @@ int fslic_hip_aggregate_forward(int device, void* stream, int N, int C, int K, l
     int rc = check_call(device, N, C, K, nnz);
     if (rc || (rc = check_reduce(reduce, weight, argmax, degree))) return rc;
     if (!offsets || !values || !out || (nnz > 0 && !indices)) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_aggregate_forward(reduce, reinterpret_cast<const long long*>(offsets), indices, weight, values, out, argmax, degree, N, C, K, nnz,
-                             reinterpret_cast<hipStream_t>(stream));
-    return launched("aggregate launch");
+    return on_stream(device, stream, "aggregate launch", [&](hipStream_t st) -> int {
+        launch_aggregate_forward(reduce, i64(offsets), indices, weight, values, out, argmax, degree, N, C, K, nnz, st);
+        return FSLIC_OK;
+    });
 }
 
 int fslic_hip_aggregate_backward_values(int device, void* stream, int N, int C, int K, long long nnz, int reduce, const int64_t* t_offsets,
@@ -51,23 +44,22 @@ int fslic_hip_aggregate_backward_values(int device, void* stream, int N, int C, 
     int rc = check_call(device, N, C, K, nnz);
     if (rc || (rc = check_reduce(reduce, weight, argmax, degree))) return rc;
     if (!t_offsets || !grad_out || !grad_values || (nnz > 0 && (!t_entries || !t_rows))) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_aggregate_backward_values(reduce, reinterpret_cast<const long long*>(t_offsets), t_entries, t_rows, weight, argmax, degree, grad_out,
-                                     grad_values, N, C, K, nnz, reinterpret_cast<hipStream_t>(stream));
-    return launched("aggregate launch");
+    return on_stream(device, stream, "aggregate launch", [&](hipStream_t st) -> int {
+        launch_aggregate_backward_values(reduce, i64(t_offsets), t_entries, t_rows, weight, argmax, degree, grad_out, grad_values, N, C, K, nnz, st);
+        return FSLIC_OK;
+    });
 }
 
 int fslic_hip_aggregate_backward_weight(int device, void* stream, int N, int C, int K, long long nnz, const int32_t* rows, const int32_t* indices,
                                         const float* values, const float* grad_out, float* grad_weight) {
-    int rc = check_call(device, N, C, K, nnz);
+    const int rc = check_call(device, N, C, K, nnz);
     if (rc) return rc;
     if (!values || !grad_out || (nnz > 0 && (!rows || !indices || !grad_weight))) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (nnz == 0) return FSLIC_OK;
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_aggregate_backward_weight(rows, indices, values, grad_out, grad_weight, N, C, K, nnz, reinterpret_cast<hipStream_t>(stream));
-    return launched("aggregate launch");
+    return on_stream(device, stream, "aggregate launch", [&](hipStream_t st) -> int {
+        launch_aggregate_backward_weight(rows, indices, values, grad_out, grad_weight, N, C, K, nnz, st);
+        return FSLIC_OK;
+    });
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ namespace fslic {
 
 constexpr int kMatchMaxTolerance = 15;               // a tile of 32 rows and its halo of 15 on either side: one row per lane
 
-// labels, other: N x H x W of the given PoolLabel types (pool.h)
+// labels, other: N x H x W of the given LabelTypes (labels.h)
 void launch_overlap_accumulate(const void* labels, int label_type, const void* other, int other_type, void* workspace,
                                int N, int H, int W, int K, int M, uint32_t capacity, hipStream_t st);
 // out: uint64 [N][3] = (hits, boundary pixels of other, boundary pixels of labels), cleared by the caller

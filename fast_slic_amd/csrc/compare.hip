@@ -15,7 +15,7 @@
 //                       frame: its counts meet in LDS and go out as one 64-bit atomic per counter.
 // All integer work: neither the order in which tiles arrive nor the capacity of the table can change a bit of the result.
 #include "device_common.h"
-#include "pool.h"
+#include "labels.h"
 #include "compare.h"
 
 namespace fslic {
@@ -199,7 +199,7 @@ static inline unsigned long long compare_tiles(int N, int H, int W, int rows) {
     return (unsigned long long)N * (((unsigned long long)W + 63ull) / 64ull) * (unsigned long long)((H + rows - 1) / rows);
 }
 
-// (the two maps as their label types: with_label_type of pool.h, nested)
+// (the two maps as their label types: with_label_type of labels.h, nested)
 void launch_overlap_accumulate(const void* labels, int label_type, const void* other, int other_type, void* workspace,
                                int N, int H, int W, int K, int M, uint32_t capacity, hipStream_t st) {
     const PairTables t = pair_tables(workspace, N, capacity);

@@ -28,7 +28,7 @@ inline size_t connect_workspace_bytes(int N, int H, int W) {
     return 2 * connect_align(P * 4) + connect_align(connect_chunks(N, H, W) * 4);
 }
 
-// labels: N x H x W of the given PoolLabel type (pool.h), compared for equality only.  enforce == false: out = the component number of
+// labels: N x H x W of the given LabelType (labels.h), compared for equality only.  enforce == false: out = the component number of
 // every pixel, counts[n] = the components of frame n.  enforce == true: out = the labels of rules 2 to 4 with `min_size` (at most
 // H W + 1), counts[n] = the kept components, 1 when there are none.  Every launch goes to `st`; nothing waits on the host.
 void launch_connect(const void* labels, int label_type, int32_t* out, int32_t* counts, void* workspace, int N, int H, int W,

@@ -19,17 +19,14 @@
 //   k_connect_output  : out = the label at the pixel's leader.
 // No kernel waits for another block.  All integer work: the result is the same bits from run to run.
 #include "device_common.h"
-#include "pool.h"
+#include "labels.h"
 #include "connect.h"
-#include <cassert>
 
 namespace fslic {
 
 static_assert(kConnectTileRows == 16 && kConnectChunk == 1024, "256 threads: four rows of a tile and four pixels of a chunk each");
 
-// a word that another block may be changing: read past this CU's L1 (a stale value is still right, only further from the end)
-static __device__ __forceinline__ uint32_t ld_now(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-static __device__ __forceinline__ void st_now(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ld_now of device_common.h for a word in LDS
 static __device__ __forceinline__ uint32_t lds_now(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 static __device__ __forceinline__ uint32_t lds_find(const uint32_t* par, uint32_t a) {
@@ -349,14 +346,7 @@ __global__ __launch_bounds__(256) void k_connect_output(const uint32_t* __restri
 }
 
 // ---- launches ---------------------------------------------------------------------------------
-// Every kernel strides over its items with at most tile_grid's 8192 blocks: far below the 2^24 blocks past which the runtime runs
-// only a part of a grid (soft.h).
-static inline dim3 connect_grid(unsigned long long items, unsigned long long per_block) {
-    const int g = tile_grid(items, per_block);
-    assert(g >= 1 && (unsigned long long)g < (1ull << 24));
-    return dim3((unsigned)g);
-}
-
+// Every kernel strides over its items with at most tile_grid's 8192 blocks (launch.h).
 void launch_connect(const void* labels, int label_type, int32_t* out, int32_t* counts, void* workspace, int N, int H, int W,
                     bool enforce, uint32_t min_size, hipStream_t st) {
     const size_t HW = (size_t)H * (size_t)W, P = (size_t)N * HW;
@@ -367,16 +357,16 @@ void launch_connect(const void* labels, int label_type, int32_t* out, int32_t* c
     uint32_t* sums = reinterpret_cast<uint32_t*>(ws + 2 * connect_align(P * 4));
     const unsigned long long ntx = ((unsigned long long)W + 63ull) / 64ull, nty = (unsigned long long)((H + kConnectTileRows - 1) / kConnectTileRows);
     const unsigned long long seams = ((nty - 1ull) * (unsigned long long)W + (ntx - 1ull) * (unsigned long long)H) * (unsigned long long)N;
-    const dim3 block(256), pixels = connect_grid(chunks, 1);
+    const dim3 block(256), pixels = tile_grid_dim(chunks, 1);
     if (!enforce) min_size = 0;
     with_label_type(labels, label_type, [&](auto* la) {
         using L = std::decay_t<decltype(*la)>;
-        launch(k_connect_tiles<L>, connect_grid(ntx * nty * (unsigned long long)N, 1), block, 0, st, la, parent, area, N, H, W);
-        if (seams) launch(k_connect_seams<L>, connect_grid(seams, 256), block, 0, st, la, parent, N, H, W);
+        launch(k_connect_tiles<L>, tile_grid_dim(ntx * nty * (unsigned long long)N, 1), block, 0, st, la, parent, area, N, H, W);
+        if (seams) launch(k_connect_seams<L>, tile_grid_dim(seams, 256), block, 0, st, la, parent, N, H, W);
     });
     launch(k_connect_flatten, pixels, block, 0, st, parent, area, HW, nb, chunks);
     launch(k_connect_count, pixels, block, 0, st, parent, area, sums, HW, nb, chunks, min_size);
-    launch(k_connect_scan, connect_grid((unsigned long long)N, 1), block, 0, st, sums, counts, N, nb, enforce ? 1u : 0u);
+    launch(k_connect_scan, tile_grid_dim((unsigned long long)N, 1), block, 0, st, sums, counts, N, nb, enforce ? 1u : 0u);
     launch(k_connect_apply, pixels, block, 0, st, parent, area, sums, HW, W, nb, chunks, min_size);
     if (enforce) launch(k_connect_chain, pixels, block, 0, st, parent, area, HW, nb, chunks);
     launch(k_connect_output, pixels, block, 0, st, parent, area, out, HW, nb, chunks);

@@ -1,7 +1,5 @@
 // connectapi.cpp -- the C ABI of the connectivity pass on label tensors (include/fslic_hip.h, fslic_hip_connect*; kernels in
-// connect.hip).  No engine: the caller names the device and the stream and owns every buffer.  Every argument is checked before the
-// first HIP call; nothing here synchronises or copies to the host.
-#include "engine_internal.h"
+// connect.hip), on streamapi.h; nothing here synchronises or copies to the host.
 #include "connect.h"
 #include "streamapi.h"
 
@@ -18,19 +16,16 @@ int check_connect_map(int N, int H, int W, int label_type) {
 
 int run_connect(int device, void* stream, int N, int H, int W, const void* labels, int label_type, int32_t* out, int32_t* counts,
                 void* workspace, size_t workspace_bytes, bool enforce, long long min_size) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
-    int rc = check_connect_map(N, H, W, label_type);
-    if (rc) return rc;
+    int rc = check_device(device);
+    if (rc || (rc = check_connect_map(N, H, W, label_type))) return rc;
     if (min_size < 0) return fail(FSLIC_E_INVALID, "min_size must be >= 0");
     if (!labels || !out || !counts || !workspace) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const size_t need = connect_workspace_bytes(N, H, W);
-    if (workspace_bytes < need) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
+    if ((rc = check_workspace(workspace_bytes, connect_workspace_bytes(N, H, W)))) return rc;
     const long long HW = (long long)H * W;
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_connect(labels, label_type, out, counts, workspace, N, H, W, enforce, (uint32_t)(min_size > HW ? HW + 1 : min_size),
-                   reinterpret_cast<hipStream_t>(stream));
-    return launched("connect launch");
+    return on_stream(device, stream, "connect launch", [&](hipStream_t st) -> int {
+        launch_connect(labels, label_type, out, counts, workspace, N, H, W, enforce, (uint32_t)(min_size > HW ? HW + 1 : min_size), st);
+        return FSLIC_OK;
+    });
 }
 
 }  // namespace
@@ -38,11 +33,7 @@ int run_connect(int device, void* stream, int N, int H, int W, const void* label
 extern "C" {
 
 int fslic_hip_connect_workspace_size(int N, int H, int W, size_t* bytes) {
-    if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const int rc = check_connect_map(N, H, W, kLabelI32);
-    if (rc) return rc;
-    *bytes = connect_workspace_bytes(N, H, W);
-    return FSLIC_OK;
+    return workspace_size(bytes, [&] { return check_connect_map(N, H, W, kLabelI32); }, [&] { return connect_workspace_bytes(N, H, W); });
 }
 
 int fslic_hip_connected_components(int device, void* stream, int N, int H, int W, const void* labels, int label_type,

@@ -62,6 +62,11 @@ static __device__ __forceinline__ void st_stream(uint4* p, uint4 v) {
 }
 #endif
 
+// (merge.hip, connect.hip) a word that another block may be changing: read past this CU's L1 (a stale value is still right, only further
+// from the end)
+static __device__ __forceinline__ uint32_t ld_now(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+static __device__ __forceinline__ void st_now(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // Sum over the 64 lanes of a wavefront without the LDS crossbar: __shfl_xor is ds_bpermute, which occupies the CU's LDS
 // pipe (measured: 56 % LDS-busy in a kernel that reduces 17 values per wavefront with it).  Four DPP steps leave every
 // lane of a 16-lane row with its row's sum (fixed order: deterministic for floats), four readlanes combine the rows.

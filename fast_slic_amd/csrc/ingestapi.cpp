@@ -1,6 +1,4 @@
-// ingestapi.cpp -- the C ABI of the frame ingest (include/fslic_hip.h, fslic_hip_pack_rgb; kernel in ingest.hip).  No engine: the caller
-// names the device and the stream and owns every buffer.  Every argument is checked before the first HIP call.
-#include "engine_internal.h"
+// ingestapi.cpp -- the C ABI of the frame ingest (include/fslic_hip.h, fslic_hip_pack_rgb; kernel in ingest.hip), on streamapi.h.
 #include "ingest.h"
 #include "streamapi.h"
 
@@ -12,7 +10,8 @@ extern "C" {
 
 int fslic_hip_pack_rgb(int device, void* stream, int N, int H, int W, const void* src, int src_type, const long long strides[4],
                        float scale, uint8_t* out, size_t pitch) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
+    const int rc = check_device(device);
+    if (rc) return rc;
     if (!src || !strides || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (N < 1 || H < 1 || W < 1) return fail(FSLIC_E_INVALID, "N, H and W must be positive");
     if ((long long)H * W >= (1ll << 31)) return fail(FSLIC_E_INVALID, "H * W must be below 2^31");
@@ -25,11 +24,10 @@ int fslic_hip_pack_rgb(int device, void* stream, int N, int H, int W, const void
     const uintptr_t elem = src_type == kIngestU8 ? 1 : src_type == kIngestF32 ? 4 : 2;
     if (reinterpret_cast<uintptr_t>(src) & (elem - 1)) return fail(FSLIC_E_INVALID, "src is not aligned to its element type");
     if ((unsigned long long)N * ingest_blocks_per_frame(pitch) >= (1ull << 31)) return fail(FSLIC_E_INVALID, "too many frames");
-    DeviceScope scope;
-    const int rc = scope.enter(device);
-    if (rc) return rc;
-    launch_pack_rgb(src, src_type, strides, scale, out, pitch, N, H, W, reinterpret_cast<hipStream_t>(stream));
-    return launched("pack launch");
+    return on_stream(device, stream, "pack launch", [&](hipStream_t st) -> int {
+        launch_pack_rgb(src, src_type, strides, scale, out, pitch, N, H, W, st);
+        return FSLIC_OK;
+    });
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cassert>
 #include <tuple>
 #include <type_traits>
 #include <utility>
@@ -63,6 +64,13 @@ static inline void launch_sliced(void (*kernel)(KArgs...), unsigned long long bl
 static inline int tile_grid(unsigned long long items, unsigned long long per_block) {
     const unsigned long long want = (items + per_block - 1) / per_block;
     return (int)(want < 1ull ? 1ull : want > 256ull * 32ull ? 256ull * 32ull : want);
+}
+// The same as a dim3 (merge.hip, connect.hip): at most tile_grid's 8192 blocks, far below the 2^24 blocks past which the runtime runs
+// only a part of a grid (soft.h).
+static inline dim3 tile_grid_dim(unsigned long long items, unsigned long long per_block) {
+    const int g = tile_grid(items, per_block);
+    assert(g >= 1 && (unsigned long long)g < (1ull << 24));
+    return dim3((unsigned)g);
 }
 
 // Row-wise clear of `rows` rows of `width_bytes` at `pitch` (both multiples of 4, dst 4-byte aligned; the LSC accumulators): a kernel, on

@@ -19,26 +19,16 @@
 //                         pair table (pairtable.h), which the graph's compact pass reads out.
 // No kernel waits for another block.  All integer work: the result is the same bits from run to run.
 #include "device_common.h"
-#include "pool.h"
+#include "labels.h"
 #include "merge.h"
-#include <cassert>
 
 namespace fslic {
 
 static_assert(kMergeChunk == 256, "256 threads: one node of a chunk each");
 static_assert((65534 + kMergeChunk - 1) / kMergeChunk <= 256, "k_merge_scan: the chunks of a frame are one block's");
 
-// a word that another block may be changing: read past this CU's L1 (a stale value is still right, only further from the end)
-static __device__ __forceinline__ uint32_t ld_now(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-static __device__ __forceinline__ void st_now(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-static inline dim3 merge_grid(unsigned long long items, unsigned long long per_block) {
-    const int g = tile_grid(items, per_block);
-    assert(g >= 1 && (unsigned long long)g < (1ull << 24));
-    return dim3((unsigned)g);
-}
 // The edge kernels: one edge a thread and round, with at most the 2048 blocks of 256 threads the chip holds at once (8 a CU).
-static inline dim3 edge_grid(long long E) { return dim3(min(merge_grid((unsigned long long)E, 256).x, 2048u)); }
+static inline dim3 edge_grid(long long E) { return dim3(min(tile_grid_dim((unsigned long long)E, 256).x, 2048u)); }
 
 // ---- each node's best edge --------------------------------------------------------------------
 template <bool kMark>
@@ -204,12 +194,12 @@ void launch_merge_components(const long long* edge_index, const long long* offse
     uint32_t* parent = reinterpret_cast<uint32_t*>(ws);
     uint32_t* rank = reinterpret_cast<uint32_t*>(ws + merge_align((size_t)total * 4));
     uint32_t* sums = reinterpret_cast<uint32_t*>(ws + 2 * merge_align((size_t)total * 4));
-    const dim3 block(256), nodes = merge_grid(total, 256), per_chunk = merge_grid(chunks, 1);
+    const dim3 block(256), nodes = tile_grid_dim(total, 256), per_chunk = tile_grid_dim(chunks, 1);
     if (members_type == kLabelI64) launch(k_merge_init<int64_t>, nodes, block, 0, st, reinterpret_cast<const int64_t*>(members), parent, (uint32_t)K, total);
     else launch(k_merge_init<int32_t>, nodes, block, 0, st, reinterpret_cast<const int32_t*>(members), parent, (uint32_t)K, total);
     if (E > 0) launch(k_merge_hook, edge_grid(E), block, 0, st, edge_index, offsets, join, parent, N, (uint32_t)K, E);
     launch(k_merge_flatten, per_chunk, block, 0, st, parent, sums, (uint32_t)K, nb, chunks);
-    launch(k_merge_scan, merge_grid((unsigned long long)N, 1), block, 0, st, sums, counts, N, nb);
+    launch(k_merge_scan, tile_grid_dim((unsigned long long)N, 1), block, 0, st, sums, counts, N, nb);
     launch(k_merge_rank, per_chunk, block, 0, st, parent, sums, rank, (uint32_t)K, nb, chunks);
     launch(k_merge_output, nodes, block, 0, st, parent, rank, mapping, (uint32_t)K, total);
 }
@@ -269,7 +259,7 @@ void launch_merge_labels(const void* labels, int label_type, const int32_t* mapp
     uint32_t head = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / 4u;      // (out is an int32 pointer: 4-byte aligned)
     if (head > total) head = total;
     const uint32_t groups = (total - head) / 4u;
-    const dim3 grid = merge_grid(groups, 256), block(256);
+    const dim3 grid = tile_grid_dim(groups, 256), block(256);
     with_label_type(labels, label_type, [&](auto* la) {
         using L = std::decay_t<decltype(*la)>;
         const size_t align = sizeof(L) == 8 ? 16 : 4 * sizeof(L);

@@ -5,9 +5,8 @@
 //   max        : key[N][C][K] uint64             -- (order-preserving bits of x) << 32 | (0xFFFFFFFF - flat pixel index)
 //   then       : counts[N][K] uint32
 #pragma once
-#include <hip/hip_runtime.h>
+#include "labels.h"
 #include <cstddef>
-#include <cstdint>
 
 namespace fslic {
 
@@ -15,20 +14,6 @@ constexpr int kPoolLimbs = 7;          // 7 x 32 bits: the fixed point spans 2^-
 constexpr int kPoolLsb = -96;          // weight of bit 0 of limb 0
 
 enum PoolReduce { kPoolSum = 0, kPoolMean = 1, kPoolMax = 2 };
-enum PoolLabel { kLabelU16 = 0, kLabelI32 = 1, kLabelI64 = 2 };
-
-// (kernels of pool.hip and rag.hip) a label as an index: K when it is not in [0, K) (the int16 map's -1 is 0xFFFF >= K, K <= 65534)
-static __device__ __forceinline__ uint32_t canon(uint16_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
-static __device__ __forceinline__ uint32_t canon(int32_t v, uint32_t K) { return (uint32_t)v < K ? (uint32_t)v : K; }
-static __device__ __forceinline__ uint32_t canon(int64_t v, uint32_t K) { return (unsigned long long)v < (unsigned long long)K ? (uint32_t)v : K; }
-
-// (launches) calls f(const L* map) with the map as its label type L; compare.hip nests two of them for its two maps
-template <class F>
-static inline void with_label_type(const void* map, int label_type, F f) {
-    if (label_type == kLabelU16) f(reinterpret_cast<const uint16_t*>(map));
-    else if (label_type == kLabelI32) f(reinterpret_cast<const int32_t*>(map));
-    else f(reinterpret_cast<const int64_t*>(map));
-}
 
 inline size_t pool_acc_bytes(int N, int C, int K, int reduce) {
     const size_t cells = (size_t)N * (size_t)C * (size_t)K;
@@ -38,7 +23,7 @@ inline size_t pool_workspace_bytes(int N, int C, int K, int reduce) {
     return pool_acc_bytes(N, C, K, reduce) + (((size_t)N * (size_t)K * 4 + 7) & ~(size_t)7);
 }
 
-// labels: N x H x W of the given PoolLabel type; label values outside [0, K) are skipped everywhere
+// labels: N x H x W of the given LabelType (labels.h); label values outside [0, K) are skipped everywhere
 void launch_pool_tiles(const float* feat, const void* labels, int label_type, int reduce, void* workspace,
                        int N, int C, int H, int W, int K, hipStream_t st);
 void launch_pool_finalize(const void* workspace, int reduce, float* values, int32_t* counts, int32_t* argmax,

@@ -1,6 +1,4 @@
-// poolapi.cpp -- the C ABI of superpixel pooling (include/fslic_hip.h, fslic_hip_pool*; kernels in pool.hip).  No engine: the
-// caller names the device and the stream and owns every buffer.  Every argument is checked before the first HIP call.
-#include "engine_internal.h"
+// poolapi.cpp -- the C ABI of superpixel pooling (include/fslic_hip.h, fslic_hip_pool*; kernels in pool.hip), on streamapi.h.
 #include "pool.h"
 #include "streamapi.h"
 
@@ -9,9 +7,10 @@ using namespace fslic;
 namespace {
 
 int check_common(int device, int N, int C, int K, int reduce) {
-    if (device < 0) return fail(FSLIC_E_INVALID, "device must be >= 0");
+    int rc = check_device(device);
+    if (rc) return rc;
     if (N < 1 || C < 1) return fail(FSLIC_E_INVALID, "N and C must be positive");
-    if (K < 1 || K > 65534) return fail(FSLIC_E_INVALID, "K must be in [1, 65534]");
+    if ((rc = check_node_count(K, "K"))) return rc;
     if (reduce != kPoolSum && reduce != kPoolMean && reduce != kPoolMax) return fail(FSLIC_E_INVALID, "unknown reduce");
     if ((long long)N * C * K >= (1ll << 40)) return fail(FSLIC_E_INVALID, "N * C * K must be below 2^40");
     return FSLIC_OK;
@@ -22,11 +21,7 @@ int check_common(int device, int N, int C, int K, int reduce) {
 extern "C" {
 
 int fslic_hip_pool_workspace_size(int N, int C, int K, int reduce, size_t* bytes) {
-    if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const int rc = check_common(0, N, C, K, reduce);
-    if (rc) return rc;
-    *bytes = pool_workspace_bytes(N, C, K, reduce);
-    return FSLIC_OK;
+    return workspace_size(bytes, [&] { return check_common(0, N, C, K, reduce); }, [&] { return pool_workspace_bytes(N, C, K, reduce); });
 }
 
 int fslic_hip_pool(int device, void* stream, int N, int C, int H, int W, int K, int reduce, const float* features,
@@ -35,26 +30,25 @@ int fslic_hip_pool(int device, void* stream, int N, int C, int H, int W, int K, 
     if (rc || (rc = check_label_map(N, H, W, label_type))) return rc;
     if (!features || !labels || !workspace) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     const size_t need = pool_workspace_bytes(N, C, K, reduce);
-    if (workspace_bytes < need) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIPCHK(hipMemsetAsync(workspace, 0, need, st));
-    launch_pool_tiles(features, labels, label_type, reduce, workspace, N, C, H, W, K, st);
-    return launched("pool launch");
+    if ((rc = check_workspace(workspace_bytes, need))) return rc;
+    return on_stream(device, stream, "pool launch", [&](hipStream_t st) -> int {
+        HIPCHK(hipMemsetAsync(workspace, 0, need, st));
+        launch_pool_tiles(features, labels, label_type, reduce, workspace, N, C, H, W, K, st);
+        return FSLIC_OK;
+    });
 }
 
 int fslic_hip_pool_finalize(int device, void* stream, int N, int C, int K, int reduce, const void* workspace, size_t workspace_bytes,
                             float* values, int32_t* counts, int32_t* argmax) {
-    int rc = check_common(device, N, C, K, reduce);
+    const int rc = check_common(device, N, C, K, reduce);
     if (rc) return rc;
     if (!workspace || !values) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (argmax && reduce != kPoolMax) return fail(FSLIC_E_INVALID, "argmax needs reduce == FSLIC_POOL_MAX");
     if (workspace_bytes < pool_workspace_bytes(N, C, K, reduce)) return fail(FSLIC_E_INVALID, "workspace too small");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_pool_finalize(workspace, reduce, values, counts, argmax, N, C, K, reinterpret_cast<hipStream_t>(stream));
-    return launched("pool launch");
+    return on_stream(device, stream, "pool launch", [&](hipStream_t st) -> int {
+        launch_pool_finalize(workspace, reduce, values, counts, argmax, N, C, K, st);
+        return FSLIC_OK;
+    });
 }
 
 int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K, const float* values, const void* labels,
@@ -62,10 +56,10 @@ int fslic_hip_unpool(int device, void* stream, int N, int C, int H, int W, int K
     int rc = check_common(device, N, C, K, kPoolSum);
     if (rc || (rc = check_label_map(N, H, W, label_type))) return rc;
     if (!values || !labels || !out) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    launch_unpool(values, labels, label_type, argmax, fill, out, N, C, H, W, K, reinterpret_cast<hipStream_t>(stream));
-    return launched("pool launch");
+    return on_stream(device, stream, "pool launch", [&](hipStream_t st) -> int {
+        launch_unpool(values, labels, label_type, argmax, fill, out, N, C, H, W, K, st);
+        return FSLIC_OK;
+    });
 }
 
 }  // extern "C"

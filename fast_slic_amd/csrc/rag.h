@@ -9,7 +9,7 @@
 
 namespace fslic {
 
-// labels: N x H x W of the given PoolLabel type (pool.h); image: N x H x W x C uint8 or nullptr (then C == 0)
+// labels: N x H x W of the given LabelType (labels.h); image: N x H x W x C uint8 or nullptr (then C == 0)
 void launch_rag_accumulate(const void* labels, int label_type, const uint8_t* image, void* workspace,
                            int N, int C, int H, int W, int K, int connectivity, uint32_t capacity, hipStream_t st);
 

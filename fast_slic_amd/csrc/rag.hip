@@ -11,7 +11,7 @@
 // All integer work: counts are 32-bit integer adds, contrast sums 64-bit integer adds, so neither the order in which tiles arrive nor
 // the capacity of the table can change a bit of the result.  Labels are checked against K before they form a key.
 #include "device_common.h"
-#include "pool.h"
+#include "labels.h"
 #include "rag.h"
 
 namespace fslic {

@@ -1,6 +1,4 @@
-// ragapi.cpp -- the C ABI of the region adjacency graph (include/fslic_hip.h, fslic_hip_rag*; kernels in rag.hip).  No engine: the
-// caller names the device and the stream and owns every buffer.  Every argument is checked before the first HIP call.
-#include "engine_internal.h"
+// ragapi.cpp -- the C ABI of the region adjacency graph (include/fslic_hip.h, fslic_hip_rag*; kernels in rag.hip), on streamapi.h.
 #include "rag.h"
 #include "streamapi.h"
 
@@ -9,9 +7,8 @@ using namespace fslic;
 namespace {
 
 int check_tables(int device, int N, int K, int C, long long capacity) {
-    const int rc = check_pair_table(device, N, capacity);
-    if (rc) return rc;
-    if (K < 1 || K > 65534) return fail(FSLIC_E_INVALID, "K must be in [1, 65534]");
+    int rc = check_pair_table(device, N, capacity);
+    if (rc || (rc = check_node_count(K, "K"))) return rc;
     if (C < 0 || C > kPairMaxChannels) return fail(FSLIC_E_INVALID, "C must be in [0, 4] (0: no image)");
     return FSLIC_OK;
 }
@@ -21,11 +18,7 @@ int check_tables(int device, int N, int K, int C, long long capacity) {
 extern "C" {
 
 int fslic_hip_rag_workspace_size(int N, int K, int C, long long capacity, size_t* bytes) {
-    if (!bytes) return fail(FSLIC_E_INVALID, "NULL pointer argument");
-    const int rc = check_tables(0, N, K, C, capacity);
-    if (rc) return rc;
-    *bytes = pair_workspace_bytes(N, C, (uint32_t)capacity);
-    return FSLIC_OK;
+    return workspace_size(bytes, [&] { return check_tables(0, N, K, C, capacity); }, [&] { return pair_workspace_bytes(N, C, (uint32_t)capacity); });
 }
 
 int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int K, int connectivity, const void* labels, int label_type,
@@ -37,30 +30,27 @@ int fslic_hip_rag_accumulate(int device, void* stream, int N, int H, int W, int 
     if (!labels || !workspace) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if ((image != nullptr) != (C > 0)) return fail(FSLIC_E_INVALID, "an image needs C in [1, 4], no image needs C == 0");
     const size_t need = pair_workspace_bytes(N, C, (uint32_t)capacity);
-    if (workspace_bytes < need) return fail(FSLIC_E_INVALID, "workspace too small: " + std::to_string(need) + " bytes needed");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIPCHK(hipMemsetAsync(workspace, 0, need, st));
-    launch_rag_accumulate(labels, label_type, image, workspace, N, C, H, W, K, connectivity, (uint32_t)capacity, st);
-    return launched("rag launch");
+    if ((rc = check_workspace(workspace_bytes, need))) return rc;
+    return on_stream(device, stream, "rag launch", [&](hipStream_t st) -> int {
+        HIPCHK(hipMemsetAsync(workspace, 0, need, st));
+        launch_rag_accumulate(labels, label_type, image, workspace, N, C, H, W, K, connectivity, (uint32_t)capacity, st);
+        return FSLIC_OK;
+    });
 }
 
 int fslic_hip_rag_compact(int device, void* stream, int N, int C, long long capacity, void* workspace, size_t workspace_bytes,
                           int64_t* keys, int32_t* boundary, int64_t* contrast, long long max_edges) {
-    int rc = check_tables(device, N, 1, C, capacity);
+    const int rc = check_tables(device, N, 1, C, capacity);
     if (rc) return rc;
     if (!workspace || !keys || !boundary) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     if (contrast && C == 0) return fail(FSLIC_E_INVALID, "contrast needs C in [1, 4]");
     if (max_edges < 0) return fail(FSLIC_E_INVALID, "max_edges must be >= 0");
     if (workspace_bytes < pair_workspace_bytes(N, C, (uint32_t)capacity)) return fail(FSLIC_E_INVALID, "workspace too small");
-    DeviceScope scope;
-    if ((rc = scope.enter(device))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(workspace) + offsetof(PairHeader, cursor), 0, sizeof(unsigned long long), st));
-    launch_pair_compact(workspace, N, C, (uint32_t)capacity, 0u, true, reinterpret_cast<unsigned long long*>(keys), boundary,
-                        reinterpret_cast<unsigned long long*>(contrast), (unsigned long long)max_edges, st);
-    return launched("rag launch");
+    return on_stream(device, stream, "rag launch", [&](hipStream_t st) -> int {
+        HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(workspace) + offsetof(PairHeader, cursor), 0, sizeof(unsigned long long), st));
+        launch_pair_compact(workspace, N, C, (uint32_t)capacity, 0u, true, u64(keys), boundary, u64(contrast), (unsigned long long)max_edges, st);
+        return FSLIC_OK;
+    });
 }
 
 }  // extern "C"
