@@ -118,6 +118,12 @@ def _signatures():
         ("fslic_hip_crf_inference", i32, [vp, vp, sz]),
         ("fslic_hip_crf_expf_host", i32, [vp, vp, sz, i32]),
         ("fslic_hip_crf_expf_device", i32, [vp, vp, vp, sz]),
+        # attention over neighbour lists (fast_slic_amd/attention.py); device, stream, N, [C,] K, nnz, heads first.  (The stream entries
+        # from the pooling on are listed in the order of tests/test_stream_refusals_cpu.py; these have tests/test_attention_cpu.py.)
+        ("fslic_hip_attend_dot", i32, [i32, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp, vp]),
+        ("fslic_hip_attend_softmax", i32, [i32, vp, i32, i32, i64, i32, vp, vp, vp, vp]),
+        ("fslic_hip_attend_softmax_backward", i32, [i32, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp]),
+        ("fslic_hip_attend_apply", i32, [i32, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
         # superpixel pooling (fast_slic_amd/pool.py)
         ("fslic_hip_pool_workspace_size", i32, [i32, i32, i32, i32, P(sz)]),
         ("fslic_hip_pool", i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, sz]),

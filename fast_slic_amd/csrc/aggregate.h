@@ -25,6 +25,12 @@ constexpr int kAggWaveChannels = 8;        // channels a lane accumulates at onc
 constexpr int kAggBlockChannels = 32;      // channels of an item: 4 waves x 8
 constexpr int kAggStage = 1024;            // entries of the LDS window: 16 a row, a SLIC map has about 6
 
+// the clamped bound of a row: offsets are not trusted (aggregate.hip, attend.hip)
+__device__ __forceinline__ int row_bound(const long long* __restrict__ offsets, uint32_t r, int nnz) {
+    const long long o = offsets[r];
+    return o < 0 ? 0 : o > (long long)nnz ? nnz : (int)o;
+}
+
 // out[n][c][i] by rule 1, 2 or 3 of propagate.py; argmax int32 [N][C][K] (kAggMax), degree int32 [N * K] (kAggMean: the valid entries
 // of each row).  weight only with kAggSum.  One launch.
 void launch_aggregate_forward(int reduce, const long long* offsets, const int32_t* indices, const float* weight, const float* values, float* out,

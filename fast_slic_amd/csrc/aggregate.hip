@@ -18,12 +18,6 @@ namespace fslic {
 
 namespace {
 
-// the clamped bound of a row: offsets are not trusted
-__device__ __forceinline__ int row_bound(const long long* __restrict__ offsets, uint32_t r, int nnz) {
-    const long long o = offsets[r];
-    return o < 0 ? 0 : o > (long long)nnz ? nnz : (int)o;
-}
-
 // One position of the lists as the walk takes it: `node` is the neighbour (forward) or the row over (frame, node) of the entry
 // (backward; -1 for an entry or a row outside its range), `p` the entry, `w` the weight of p, or float(degree[row]) for the mean's
 // backward.  pos is inside [0, nnz).

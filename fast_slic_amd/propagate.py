@@ -39,8 +39,9 @@ graph_aggregate:
 Nothing of a raw pair is trusted on the device: a kernel clamps each row's bounds into [0, nnz], a row whose end lies before its start
 is empty, and no index outside [0, K) is ever dereferenced: garbage gives unspecified values, never an access out of bounds.
 
-Out of scope: self loops and normalisations as arguments (one elementwise torch line each: README), a softmax over a node's entries,
-float16 / bfloat16, several weight heads, torch sparse tensors, gradients to anything but `values` and `weight`.
+Out of scope: self loops and normalisations as arguments (one elementwise torch line each: README), float16 / bfloat16, torch sparse
+tensors, gradients to anything but `values` and `weight`.  A softmax over a node's entries, several weight heads and the score of an
+entry from its two ends are attention.py's (neighbour_softmax, head_aggregate, neighbour_dot), on these lists.
 
 Every argument is checked before any device work (ValueError; two GPUs are refused first and a CPU tensor last).  graph_aggregate
 runs on torch's current stream of the tensors' GPU, takes its results and what it keeps for the backward from torch's caching

@@ -592,6 +592,37 @@ int fslic_hip_aggregate_backward_values(int device, void* stream, int N, int C, 
 int fslic_hip_aggregate_backward_weight(int device, void* stream, int N, int C, int K, long long nnz, const int32_t* rows, const int32_t* indices,
                                         const float* values, const float* grad_out, float* grad_weight);
 
+/* ---- Attention over neighbour lists (NEW surface; Python: fast_slic_amd/attention.py, which states the rules) ----
+ * Entries, lists, limits and the treatment of what the device arrays hold as for the aggregation above.  heads >= 1 divides C; D =
+ * C / heads channels a head, head h owns the channels h D .. h D + D - 1; a per-entry array is float [heads][nnz], the entries
+ * innermost, heads * nnz below 2^31.  An entry p is valid when it lies inside the clamped bounds of a row and indices[p] is inside
+ * [0, K).  Every float operation is one IEEE operation rounded on its own, nothing fused, the division correctly rounded, the
+ * exponential the one of fslic_hip_crf_expf_host(.., use_libm = 0); no atomics: the same bits from run to run.  No output overlaps an
+ * input.
+ *
+ * Dot.  out[h][p] = the left fold from +0.0 over c = h D .. h D + D - 1 of a[n][c][i] * b[n][c][indices[p]], with (n, i) = rows[p]
+ * (int32 [nnz], the row over (frame, node) of each entry); +0.0 where rows[p] is outside [0, N * K) or indices[p] outside [0, K).
+ * One thread per (head, entry); one launch, none for nnz == 0. */
+int fslic_hip_attend_dot(int device, void* stream, int N, int C, int K, long long nnz, int heads, const int32_t* rows, const int32_t* indices,
+                         const float* a, const float* b, float* out);
+/* Softmax over the valid entries of each row, per head: m = their largest score, e = expf(scores[h][p] - m), Z = the left fold from
+ * +0.0 of e in ascending p, out[h][p] = e / Z; +0.0 for every entry that is not valid.  Defined for rows whose valid scores are
+ * finite or -inf with at least one finite; NaN and +inf leave the row unspecified.  One launch, none for nnz == 0. */
+int fslic_hip_attend_softmax(int device, void* stream, int N, int K, long long nnz, int heads, const int64_t* offsets, const int32_t* indices,
+                             const float* scores, float* out);
+/* Its backward from alpha (what the forward wrote): t = the left fold from +0.0 over the row's valid entries of alpha[h][p] *
+ * grad_out[h][p]; grad_scores[h][p] = alpha[h][p] * (grad_out[h][p] - t), +0.0 for an entry that is not valid.  One launch. */
+int fslic_hip_attend_softmax_backward(int device, void* stream, int N, int K, long long nnz, int heads, const int64_t* offsets,
+                                      const int32_t* indices, const float* alpha, const float* grad_out, float* grad_scores);
+/* The neighbour sum with one weight per head (weight float [heads][nnz]).  transposed 0: ia = indices, ib is not read; dst[n][c][i] =
+ * the left fold from +0.0 over the valid entries p of row (n, i), ascending, of weight[h(c)][p] * src[n][c][indices[p]], h(c) =
+ * c / D.  transposed 1: offsets, ia, ib = t_offsets, t_entries, t_rows of the transposed lists as in
+ * fslic_hip_aggregate_backward_values; dst[n][c][j] = the fold over them of weight[h(c)][p] * src[n][c][row(p)].  With heads == 1 the
+ * bits of fslic_hip_aggregate_forward / _backward_values with reduce 0 and this weight.  The two are the gradients of the dot (to a
+ * with src = b, to b with src = a, weight = grad_out) and the dot is the gradient of this sum to its weight.  One launch. */
+int fslic_hip_attend_apply(int device, void* stream, int N, int C, int K, long long nnz, int heads, int transposed, const int64_t* offsets,
+                           const int32_t* ia, const int32_t* ib, const float* weight, const float* src, float* dst);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
