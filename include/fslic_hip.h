@@ -623,6 +623,20 @@ int fslic_hip_attend_softmax_backward(int device, void* stream, int N, int K, lo
 int fslic_hip_attend_apply(int device, void* stream, int N, int C, int K, long long nnz, int heads, int transposed, const int64_t* offsets,
                            const int32_t* ia, const int32_t* ib, const float* weight, const float* src, float* dst);
 
+/* ---- exact k nearest neighbours in feature space (NEW surface; Python: fast_slic_amd/knn.py) ----
+ * For every node i of every frame f of `points` (float [N][D][K], the node innermost) the k nearest nodes j of the same frame of
+ * `other` (the same layout; NULL: of `points` itself, and then j != i unless `loop` is not 0) by the squared Euclidean distance
+ *     d(i, j) = the left fold from +0.0f over c = 0 .. D - 1 of  t = points[f][c][i] - other[f][c][j],  acc = acc + t * t
+ * three separately rounded float operations a channel, nothing fused.  `valid` (one byte per node, [N][K], 0 = invalid; NULL: all
+ * valid) describes the nodes of both arrays: an invalid node is no candidate and its own row is all padding.  A NaN distance is no
+ * candidate, +inf is an ordinary distance.  indices (int32) and dist (float), both [N * K][k], take the k smallest candidates of
+ * every row in the total order (d, j), ascending, and -1 / +inf behind the last one.  The result does not depend on the launch shape
+ * and is the same bits from run to run; no atomics, no workspace, one launch.  1 <= k <= 32, N * K * k < 2^31; `loop` together with
+ * `other` is refused.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, every argument checked
+ * before the first HIP call (FSLIC_E_INVALID).  No output overlaps an input. */
+int fslic_hip_knn_graph(int device, void* stream, int N, int D, int K, int k, int loop, const float* points, const float* other,
+                        const uint8_t* valid, int32_t* indices, float* dist);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
