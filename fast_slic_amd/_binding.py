@@ -126,6 +126,9 @@ def _signatures():
         ("fslic_hip_attend_apply", i32, [i32, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
         # nearest neighbours in feature space (fast_slic_amd/knn.py; tests/test_knn_cpu.py); device, stream, N, D, K, k, loop first
         ("fslic_hip_knn_graph", i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+        # messages over neighbour lists (fast_slic_amd/messages.py; tests/test_messages_cpu.py); device, stream, N, C, K, nnz first
+        ("fslic_hip_message_gather", i32, [i32, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_message_reduce", i32, [i32, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         # superpixel pooling (fast_slic_amd/pool.py)
         ("fslic_hip_pool_workspace_size", i32, [i32, i32, i32, i32, P(sz)]),
         ("fslic_hip_pool", i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, sz]),

@@ -637,6 +637,31 @@ int fslic_hip_attend_apply(int device, void* stream, int N, int C, int K, long l
 int fslic_hip_knn_graph(int device, void* stream, int N, int D, int K, int k, int loop, const float* points, const float* other,
                         const uint8_t* valid, int32_t* indices, float* dist);
 
+/* ---- Messages over neighbour lists (NEW surface; Python: fast_slic_amd/messages.py, which states the rules) ----
+ * Entries, lists, limits and the treatment of what the device arrays hold as for the aggregation above.  A per-entry array is float
+ * [C][nnz], the entries innermost, C * nnz below 2^31; the node side is float [N][C][K].  An entry p is valid when it lies inside the
+ * clamped bounds of a row and indices[p] is inside [0, K).  Every float operation is one IEEE operation rounded on its own, nothing
+ * fused, the division correctly rounded; no atomics: the same bits from run to run.  No output overlaps an input.
+ *
+ * Gather, nodes -> entries.  out[c][p] = values[n][c][node] with (n, i) = rows[p] (int32 [nnz], the row over (frame, node) of each
+ * entry) and node = i (end 0, the target) or indices[p] (end 1, the source): a copy, NaN and the sign of zero pass through.  +0.0
+ * where rows[p] is outside [0, N * K) or indices[p] outside [0, K).  Two optional arrays serve the backward of the reduce below:
+ * scale_degree (int32 [N * K], or NULL): the value is divided by (float)scale_degree[n * K + node]; argmax (int32 [N][C][K], or NULL):
+ * +0.0 unless argmax[n][c][node] == p.  One thread per (channel, entry); one launch, none for nnz == 0. */
+int fslic_hip_message_gather(int device, void* stream, int N, int C, int K, long long nnz, int end, const int32_t* rows, const int32_t* indices,
+                             const float* values, const int32_t* scale_degree, const int32_t* argmax, float* out);
+/* Reduce, entries -> nodes.  transposed 0: ia = indices, ib is not read; out[n][c][i] folds messages[c][p] over the valid entries p of
+ * row (n, i), ascending.  transposed 1: offsets, ia, ib = t_offsets, t_entries, t_rows of the transposed lists as in
+ * fslic_hip_aggregate_backward_values; out[n][c][j] folds messages[c][t_entries[q]] over the positions q of target (n, j), ascending
+ * (an entry outside [0, nnz) or a row outside frame n contributes nothing).  reduce 0 (sum): the left fold from +0.0.  1 (mean): that
+ * sum divided by (float)d, d = the terms of the fold, +0.0 for d = 0; degree (int32 [N * K], required) receives d.  2 (max), 3 (min):
+ * the extremum, +0.0 for d = 0; argmax (int32 [N][C][K], required) receives the entry p it was first met at (the smallest such p),
+ * -1 for d = 0; NaN leaves the cell unspecified.  The gather above is the gradient of this reduce (of the mean with scale_degree =
+ * degree, of the max and min with argmax), and the sum is the gradient of the gather: transposed 0 for end 0, 1 for end 1.  One
+ * launch, also for nnz == 0 (zeros, -1, 0). */
+int fslic_hip_message_reduce(int device, void* stream, int N, int C, int K, long long nnz, int reduce, int transposed, const int64_t* offsets,
+                             const int32_t* ia, const int32_t* ib, const float* messages, float* out, int32_t* argmax, int32_t* degree);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
