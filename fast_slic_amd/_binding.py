@@ -129,6 +129,13 @@ def _signatures():
         # messages over neighbour lists (fast_slic_amd/messages.py; tests/test_messages_cpu.py); device, stream, N, C, K, nnz first
         ("fslic_hip_message_gather", i32, [i32, vp, i32, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp]),
         ("fslic_hip_message_reduce", i32, [i32, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        # pixels over neighbour lists (fast_slic_amd/pixels.py; tests/test_pixels_cpu.py); device, stream, N, C, H, W, K, S, heads, nnz,
+        # label_type, labels, offsets, indices first
+        ("fslic_hip_pixel_dot", i32, [i32, vp] + [i32] * 7 + [i64, i32, vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_pixel_mix", i32, [i32, vp] + [i32] * 7 + [i64, i32, vp, vp, vp, vp, vp, vp]),
+        ("fslic_hip_pixel_softmax", i32, [i32, vp] + [i32] * 7 + [i64, i32, vp, vp, vp, i32, vp, vp, vp]),
+        ("fslic_hip_pixel_scatter_workspace_size", i32, [i32, i32, i32, P(sz)]),
+        ("fslic_hip_pixel_scatter", i32, [i32, vp] + [i32] * 7 + [i64, i32, vp, vp, vp, vp, vp, vp, vp, sz]),
         # superpixel pooling (fast_slic_amd/pool.py)
         ("fslic_hip_pool_workspace_size", i32, [i32, i32, i32, i32, P(sz)]),
         ("fslic_hip_pool", i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, sz]),

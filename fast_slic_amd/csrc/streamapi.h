@@ -1,6 +1,6 @@
 // streamapi.h -- what the stream entries share: the fslic_hip_* functions that take (device, stream, ...) and their *_workspace_size
 // companions (poolapi.cpp, ragapi.cpp, compareapi.cpp, crfapi.cpp, softapi.cpp, connectapi.cpp, mergeapi.cpp, regionapi.cpp,
-// ingestapi.cpp, aggregateapi.cpp, attendapi.cpp, knnapi.cpp, messageapi.cpp).  No engine: the caller names the device and the stream and owns every buffer.  Every
+// ingestapi.cpp, aggregateapi.cpp, attendapi.cpp, knnapi.cpp, messageapi.cpp, pixelapi.cpp).  No engine: the caller names the device and the stream and owns every buffer.  Every
 // argument is checked before the first HIP call.  An entry is its checks, in the order it refuses in (tests/test_stream_refusals_cpu.py pins the
 // order and the words), and then on_stream() around what it enqueues.  Internal to the library.
 #pragma once

@@ -662,6 +662,42 @@ int fslic_hip_message_gather(int device, void* stream, int N, int C, int K, long
 int fslic_hip_message_reduce(int device, void* stream, int N, int C, int K, long long nnz, int reduce, int transposed, const int64_t* offsets,
                              const int32_t* ia, const int32_t* ib, const float* messages, float* out, int32_t* argmax, int32_t* degree);
 
+/* ---- Pixels over neighbour lists (NEW surface; Python: fast_slic_amd/pixels.py, which states the rules) ----
+ * Entries as for pooling: a device index and a stream, no synchronisation, no allocation, every argument checked before the first HIP
+ * call (FSLIC_E_INVALID).  labels: the map of fslic_hip_pool, N x H x W of label_type, a value outside [0, K) is no label; offsets
+ * int64 [N * K + 1] and indices int32 [nnz] (NULL only with nnz == 0): the lists of the aggregation above, with its treatment of what
+ * the device arrays hold.  Every pixel has S slots, 1 <= S <= 32: slot 0 is its own label i, slot s >= 1 is entry lo + s - 1 of row
+ * (n, i), [lo, hi) the row's bounds clamped into [0, nnz]; it is empty unless that entry lies below hi and its index inside [0, K),
+ * and every slot of a pixel without a label is empty.  Pixel features are float [N][C][H][W], node features float [N][C][K], a per-slot
+ * array float [N][heads][S][H][W]; C % heads == 0, head h owns the channels h D .. h D + D - 1, D = C / heads.  Limits: N * C * K,
+ * N * C * H * W, N * heads * S * H * W and nnz below 2^31.  Every float operation is one IEEE operation rounded on its own, nothing
+ * fused, the division correctly rounded; no float atomics: the same bits from run to run.  No output overlaps an input.
+ *
+ * Dot: out[n][h][s][y][x] = the left fold from +0.0 over the head's channels c, ascending, of a[n][c][y][x] * b[n][c][j], j the node of
+ * the slot; +0.0 for an empty slot.  One launch. */
+int fslic_hip_pixel_dot(int device, void* stream, int N, int C, int H, int W, int K, int S, int heads, long long nnz, int label_type,
+                        const void* labels, const int64_t* offsets, const int32_t* indices, const float* a, const float* b, float* out);
+/* Mix: out[n][c][y][x] = the left fold from +0.0 over the pixel's non-empty slots s, ascending, of weight[n][h(c)][s][y][x] *
+ * values[n][c][j].  One launch. */
+int fslic_hip_pixel_mix(int device, void* stream, int N, int C, int H, int W, int K, int S, int heads, long long nnz, int label_type,
+                        const void* labels, const int64_t* offsets, const int32_t* indices, const float* values, const float* weight, float* out);
+/* Softmax over the non-empty slots of every (pixel, head); C is only checked (pass heads).  backward 0: in = scores; m = their maximum,
+ * e = crf_expf(s - m), Z = the left fold of e from +0.0, out = e / Z; grad is not read.  backward 1: in = the alpha of the forward,
+ * t = the left fold of alpha * grad, out = alpha * (grad - t).  +0.0 on every empty slot.  NaN or +inf leaves the pixel unspecified.
+ * One launch. */
+int fslic_hip_pixel_softmax(int device, void* stream, int N, int C, int H, int W, int K, int S, int heads, long long nnz, int label_type,
+                            const void* labels, const int64_t* offsets, const int32_t* indices, int backward, const float* in, const float* grad,
+                            float* out);
+/* Scatter: out[n][c][j] = the sum of weight[n][h(c)][s][y][x] * x[n][c][y][x] over the pixels and slots that name node j, by the
+ * contract of fslic_hip_pool's sum: one f32 partial per tile of 16 x 64 pixels, label, slot and channel (each product rounded once,
+ * the order inside a tile fixed), truncated towards zero to a multiple of 2^-96; the partials are added exactly in fixed point and
+ * the total is rounded once, ties to even, a zero total being +0.0.  Non-finite input leaves the entry unspecified.  The workspace
+ * (8-byte aligned, 56 N C K bytes: the accumulator) is zeroed on the stream; three operations on the stream. */
+int fslic_hip_pixel_scatter_workspace_size(int N, int C, int K, size_t* bytes);
+int fslic_hip_pixel_scatter(int device, void* stream, int N, int C, int H, int W, int K, int S, int heads, long long nnz, int label_type,
+                            const void* labels, const int64_t* offsets, const int32_t* indices, const float* x, const float* weight, float* out,
+                            void* workspace, size_t workspace_bytes);
+
 /* ---- SimpleCRF inference on device tensors (NEW surface, no counterpart in the reference; Python: fast_slic_amd/crf_torch.py) ----
  * The inference of fslic_hip_crf_inference (same arithmetic, bit for bit) for a caller who holds everything in device memory: no CRF
  * object, no host state.  Entries as for pooling: a device index and a stream, no synchronisation, no allocation, the caller's device
