@@ -43,7 +43,7 @@ and division below is one separately rounded float32 operation, nothing fused, t
 
 The GAT score el[i] + er[j] is a dot with two channels per head: a = [el; 1], b = [1; er] (README).
 
-Nothing of a raw pair is trusted on the device, by aggregate.h's rule: nothing a kernel reads from device memory becomes an address
+Nothing of a raw pair is trusted on the device, by csrc/lists.h's rule: nothing a kernel reads from device memory becomes an address
 before it is checked: row bounds are clamped into [0, nnz] and an end before its start is an empty row; an index outside [0, K), an
 entry outside [0, nnz) and a row outside the target's frame contribute nothing.
 
@@ -62,7 +62,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _binding as B, _tensors as T
-from .propagate import _LIMIT, NeighbourLists, _check_lists, neighbour_lists
+from .propagate import (LIMIT, NeighbourLists, as_lists, check_heads, check_lists, check_map, differentiable, lists_tensors,
+                        neighbour_lists)      # neighbour_lists: kept as attention.neighbour_lists for callers of this module
 from .rag import SuperpixelGraph, check_graph
 
 __all__ = ["neighbour_dot", "neighbour_softmax", "head_aggregate", "graph_attention"]
@@ -72,22 +73,6 @@ _LIMIT_TEXT = "N * C * K, the number of neighbour entries and heads * entries mu
 
 
 # ---- argument checks: all of them run before any device work ----
-def _check_heads(heads, Cc, what="C"):
-    if isinstance(heads, bool) or not isinstance(heads, numbers.Integral) or heads < 1:
-        raise ValueError("heads must be a positive integer, got %r" % (heads,))
-    if Cc % heads != 0:
-        raise ValueError("%s = %d is not a multiple of heads = %d" % (what, Cc, heads))
-    return int(heads)
-
-
-def _check_map(t, what):
-    """-> (N, C, K) of a float32 [N, C, K] or [C, K] tensor."""
-    T.check_float_map(t, (2, 3), what, "[C, K] or [N, C, K]")
-    Cc, K = (int(v) for v in t.shape[-2:])
-    T.check_count(K, "K, the last dimension of %s," % what)
-    return (int(t.shape[0]) if t.dim() == 3 else 1), Cc, K
-
-
 def _check_entries(t, what, nnz, heads=None):
     """-> Hd of a per-entry tensor float32 [Hd, nnz] or [nnz] (Hd = 1); `heads`: the Hd it must have."""
     text = "[Hd, nnz] or [nnz] with nnz = %d, one per head and neighbour entry" % nnz
@@ -99,20 +84,8 @@ def _check_entries(t, what, nnz, heads=None):
 
 
 def _check_limits(cells, nnz, Hd):
-    if cells >= _LIMIT or nnz >= _LIMIT or Hd * nnz >= _LIMIT:
+    if cells >= LIMIT or nnz >= LIMIT or Hd * nnz >= LIMIT:
         raise ValueError(_LIMIT_TEXT)
-
-
-def _lists_tensors(nl):
-    if isinstance(nl, NeighbourLists):
-        return [(nl.offsets, "nl.offsets"), (nl.indices, "nl.indices")]
-    if isinstance(nl, SuperpixelGraph):
-        return [(nl.edge_index, "graph.edge_index"), (nl.offsets, "graph.offsets")]
-    return [(nl[0], "graph offsets"), (nl[1], "graph indices")]
-
-
-def _lists(nl, N, K):
-    return nl if isinstance(nl, NeighbourLists) else neighbour_lists(nl, N, K)
 
 
 # ---- the launches, on contiguous tensors of one GPU; nl a NeighbourLists ----
@@ -201,25 +174,21 @@ class _Apply(torch.autograd.Function):
                 _dot(g, x, ctx.nl, int(w.shape[0])) if ctx.needs_input_grad[1] else None, None)
 
 
-def _differentiable(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-
-
 # ---- the public functions ----
 def neighbour_dot(a, b, nl, heads=1):
     """The score of every neighbour entry from the features of its two ends, by rule 1 of the module's text: `a` (read at the entry's
     row) and `b` (read at its neighbour) float32 [N, C, K] ([C, K] when N = 1) of one shape -> float32 [heads, nnz].  Differentiable
     with respect to both; one launch forward, one for each gradient, no host synchronisation."""
-    N, Cc, K = _check_map(a, "a")
+    N, Cc, K = check_map(a, "a")
     T.check_tensor(b, "b", (torch.float32,), "the shape of a, %s" % (tuple(a.shape),), lambda s: s == tuple(a.shape))
-    nnz = _check_lists(nl, N, K)
-    Hd = _check_heads(heads, Cc)
+    nnz = check_lists(nl, N, K)
+    Hd = check_heads(heads, Cc)
     _check_limits(N * Cc * K, nnz, Hd)
-    dev = T.one_device([(a, "a"), (b, "b")] + _lists_tensors(nl))
+    dev = T.one_device([(a, "a"), (b, "b")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         a3, b3 = a.reshape(N, Cc, K).contiguous(), b.reshape(N, Cc, K).contiguous()
-        return _Dot.apply(a3, b3, nl, Hd) if _differentiable(a3, b3) else _dot(a3, b3, nl, Hd)
+        return _Dot.apply(a3, b3, nl, Hd) if differentiable(a3, b3) else _dot(a3, b3, nl, Hd)
 
 
 def neighbour_softmax(scores, nl, *, num_frames=None, num_components=None):
@@ -234,14 +203,14 @@ def neighbour_softmax(scores, nl, *, num_frames=None, num_components=None):
         N, K = T.check_count(num_frames, "num_frames"), T.check_count(num_components, "num_components")
     if (num_frames, num_components) not in ((None, None), (N, K)):
         raise ValueError("the graph has %d frames of %d nodes, not %r of %r" % (N, K, num_frames, num_components))
-    nnz = _check_lists(nl, N, K)
+    nnz = check_lists(nl, N, K)
     Hd = _check_entries(scores, "scores", nnz)
     _check_limits(0, nnz, Hd)
-    dev = T.one_device([(scores, "scores")] + _lists_tensors(nl))
+    dev = T.one_device([(scores, "scores")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         s = scores.reshape(Hd, nnz).contiguous()
-        alpha = _Softmax.apply(s, nl) if _differentiable(s) else _softmax(s, None, nl)
+        alpha = _Softmax.apply(s, nl) if differentiable(s) else _softmax(s, None, nl)
     return alpha.view(scores.shape)
 
 
@@ -249,15 +218,15 @@ def head_aggregate(values, nl, weight):
     """`values` float32 [N, C, K] ([C, K] when N = 1) summed over the neighbours of every node with one weight per head and entry, by
     rule 3 -> a new tensor of the same shape.  `weight`: float32 [Hd, nnz] (or [nnz], one head) with C % Hd == 0.  Differentiable with
     respect to both; one launch forward, one for each gradient, no host synchronisation."""
-    N, Cc, K = _check_map(values, "values")
-    nnz = _check_lists(nl, N, K)
-    Hd = _check_heads(_check_entries(weight, "weight", nnz), Cc)
+    N, Cc, K = check_map(values, "values")
+    nnz = check_lists(nl, N, K)
+    Hd = check_heads(_check_entries(weight, "weight", nnz), Cc)
     _check_limits(N * Cc * K, nnz, Hd)
-    dev = T.one_device([(values, "values"), (weight, "weight")] + _lists_tensors(nl))
+    dev = T.one_device([(values, "values"), (weight, "weight")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         x, w = values.reshape(N, Cc, K).contiguous(), weight.reshape(Hd, nnz).contiguous()
-        y = _Apply.apply(x, w, nl) if _differentiable(x, w) else _apply(x, w, nl, False)
+        y = _Apply.apply(x, w, nl) if differentiable(x, w) else _apply(x, w, nl, False)
     return y.view(values.shape)
 
 
@@ -266,22 +235,22 @@ def graph_attention(query, key, values, nl, heads=1, scale=None, return_weights=
     one shape, `values` float32 with the same N and K and Cv channels, C and Cv multiples of `heads` -> [N, Cv, K] (the shape of
     `values`); with return_weights=True (y, alpha float32 [heads, nnz]).  scale: None (D ** -0.5, D = C / heads) or a finite number.
     The three launches of neighbour_dot, neighbour_softmax and head_aggregate, and their backwards."""
-    N, Cc, K = _check_map(query, "query")
+    N, Cc, K = check_map(query, "query")
     T.check_tensor(key, "key", (torch.float32,), "the shape of query, %s" % (tuple(query.shape),), lambda s: s == tuple(query.shape))
-    Nv, Cv, Kv = _check_map(values, "values")
+    Nv, Cv, Kv = check_map(values, "values")
     if (Nv, Kv) != (N, K) or values.dim() != query.dim():
         raise ValueError("values must have the frames and nodes of query, got shapes %s and %s" % (tuple(values.shape), tuple(query.shape)))
-    nnz = _check_lists(nl, N, K)
-    Hd = _check_heads(heads, Cc)
-    _check_heads(heads, Cv, "Cv")
+    nnz = check_lists(nl, N, K)
+    Hd = check_heads(heads, Cc)
+    check_heads(heads, Cv, "Cv")
     if scale is None:
         scale = float(Cc // Hd) ** -0.5
     elif isinstance(scale, bool) or not isinstance(scale, numbers.Real) or scale != scale or scale in (float("inf"), float("-inf")):
         raise ValueError("scale must be None or a finite number, got %r" % (scale,))
     _check_limits(N * max(Cc, Cv) * K, nnz, Hd)
-    dev = T.one_device([(query, "query"), (key, "key"), (values, "values")] + _lists_tensors(nl))
+    dev = T.one_device([(query, "query"), (key, "key"), (values, "values")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         alpha = neighbour_softmax(neighbour_dot(query * torch.tensor(float(scale), dtype=torch.float32).item(), key, nl, Hd), nl)
         y = head_aggregate(values, nl, alpha)
     return (y, alpha) if return_weights else y

@@ -80,7 +80,7 @@ int fslic_hip_attend_apply(int device, void* stream, int N, int C, int K, long l
     if (transposed != 0 && transposed != 1) return fail(FSLIC_E_INVALID, "transposed must be 0 or 1");
     if (!offsets || !src || !dst || (nnz > 0 && (!ia || !weight || (transposed && !ib)))) return fail(FSLIC_E_INVALID, "NULL pointer argument");
     return on_stream(device, stream, "attend launch", [&](hipStream_t st) -> int {
-        launch_attend_apply(transposed != 0, i64(offsets), ia, ib, weight, src, dst, N, C, K, nnz, heads, st);
+        launch_attend_apply(transposed != 0, attend_pack(C / heads), i64(offsets), ia, ib, weight, src, dst, N, C, K, nnz, heads, st);
         return FSLIC_OK;
     });
 }

@@ -65,6 +65,12 @@ static inline int tile_grid(unsigned long long items, unsigned long long per_blo
     const unsigned long long want = (items + per_block - 1) / per_block;
     return (int)(want < 1ull ? 1ull : want > 256ull * 32ull ? 256ull * 32ull : want);
 }
+// The grid of a grid-stride kernel that takes one element a thread and round: at most the 2048 blocks of 256 threads the chip holds at
+// once (8 a CU).
+static inline dim3 entry_grid(unsigned long long elements) {
+    const int blocks = tile_grid(elements, 256);
+    return dim3((unsigned)(blocks < 2048 ? blocks : 2048));
+}
 // The same as a dim3 (merge.hip, connect.hip): at most tile_grid's 8192 blocks, far below the 2^24 blocks past which the runtime runs
 // only a part of a grid (soft.h).
 static inline dim3 tile_grid_dim(unsigned long long items, unsigned long long per_block) {

@@ -2,25 +2,16 @@
 // the nodes, which are each other's gradients (message.hip, messageapi.cpp; fast_slic_amd/messages.py states the rules).  Internal
 // to the library.
 //
-// Lists, transposed lists and features as in aggregate.h.  A per-entry array is float [F][nnz], the entries innermost (attend.h's
-// [Hd][nnz]); the node side of a reduce is float [N][F][K].  Nothing a kernel reads from device memory becomes an address before it is
-// checked: row bounds are clamped into [0, nnz] and an end before its start is an empty row; an index outside [0, K), an entry
-// outside [0, nnz) and a row outside the target's frame contribute nothing.
+// Lists, transposed lists, features, the rule of what is trusted and the tile with its LDS window are lists.h's.  A per-entry array is
+// float [F][nnz], the entries innermost (attend.h's [Hd][nnz]); the node side of a reduce is float [N][F][K].
 //
 // Launch shapes.
 //   gather   one thread per (feature, entry), the entries innermost, grid-stride (attend.h's dot): rows[p] and indices[p] are read
 //            coalesced, the store is coalesced, a channel's K floats stay in cache.
-//   reduce   a block of 256 threads takes an item = 64 consecutive rows x 4 features (attend.h's softmax): lane l of wave w owns row
-//            64 * tile + l and feature 4 * group + w.  The block copies the first kAggStage list positions behind the tile's first row
-//            into LDS, every wave the window of its feature's messages; a lane walks its row from there, or from global memory for what
-//            lies beyond the window: a hub row longer than the window is walked in full, in order.  Direct form: the messages of the
-//            window are consecutive and the copy is coalesced.  Transposed form: position q holds entry t_entries[q], so the block
-//            stages the entries (and whether each belongs to the target's frame) coalesced, and after a barrier every wave gathers
-//            its feature's messages through the staged entries, 64 independent loads an instruction, not one dependent load a step of
-//            a lane's walk.
+//   reduce   an item is a tile x 4 features (attend.h's softmax): wave w owns feature 4 * group + w and keeps the window of its
+//            feature's messages, gathered through the staged entries in the transposed form.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "lists.h"
 
 namespace fslic {
 

@@ -2,12 +2,12 @@
 // and the per-slot dot product, softmax, mix and scatter over them, which are each other's gradients (pixel.hip, pixelapi.cpp;
 // fast_slic_amd/pixels.py states the rules).  Internal to the library.
 //
-// Label map as in pool.h (N x H x W of a LabelType, a value outside [0, K) is no label), lists as in aggregate.h (one CSR over the
+// Label map as in pool.h (N x H x W of a LabelType, a value outside [0, K) is no label), lists as in lists.h (one CSR over the
 // R = N * K rows, offsets int64 [R + 1], indices int32 [nnz]).  Pixel features float [N][C][H][W], node features float [N][C][K], a
 // per-slot array float [N][Hd][S][H][W]; Hd heads, D = C / Hd channels a head, head h owns the channels h D .. h D + D - 1.
 // The slots of a pixel of label i < K in frame f: slot 0 is node i; slot s >= 1 is entry p = lo + s - 1 of row f K + i, [lo, hi) the
 // row's bounds clamped into [0, nnz], and it is empty unless p < hi and 0 <= indices[p] < K.  A pixel without a label has empty slots
-// only.  Nothing a kernel reads from device memory becomes an address before it is checked (aggregate.h's rule).  No kernel keeps
+// only.  Nothing a kernel reads from device memory becomes an address before it is checked (lists.h's rule).  No kernel keeps
 // the S nodes of a pixel: a slot's node is read again where it is needed (label-coherent reads, served by the caches).
 //
 // Launch shapes.

@@ -14,7 +14,7 @@
 // atomics are fix_add's 64-bit integer adds: no float atomics, and no kernel waits for another block.
 #include "device_common.h"
 #include "pixel.h"
-#include "aggregate.h"   // row_bound
+#include "lists.h"   // row_bound
 #include "crf.h"         // crf_expf
 #include "fixsum.h"      // fix_add, fix_to_float
 #include <algorithm>

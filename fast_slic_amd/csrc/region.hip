@@ -89,8 +89,7 @@ void launch_region_sums(const float* values, const int32_t* mapping, const void*
 
 void launch_region_edge_weights(const long long* edge_index, const long long* offsets, const float* sums, const void* counts, int counts_type,
                                 int mode, float* weight, int N, int C, int K, long long E, hipStream_t st) {
-    // one edge a thread and round, with at most the 2048 blocks of 256 threads the chip holds at once (as merge.hip's edge kernels)
-    const dim3 grid((unsigned)std::min(tile_grid((unsigned long long)E, 256), 2048)), block(256);
+    const dim3 grid = entry_grid((unsigned long long)E), block(256);               // one edge a thread and round
     if (counts_type == kLabelI64)
         launch(k_region_weights<int64_t>, grid, block, 0, st, edge_index, offsets, sums, reinterpret_cast<const int64_t*>(counts), weight, N, C, (uint32_t)K, E, mode);
     else

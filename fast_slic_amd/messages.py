@@ -37,7 +37,7 @@ sum and division below is one separately rounded float32 operation, nothing fuse
    argmax[f, c, node] == p and +0.0 elsewhere.  Every invalid entry gets +0.0.  So two kernel families close the set -- a gather with
    an optional per-node scale and argmax mask, a reduce in direct and transposed form -- and a numpy model written operation by
    operation (tests/messages_ref.py) reproduces every result and gradient bit for bit; the same bits come out from run to run.
-5. Nothing a kernel reads from device memory becomes an address before it is checked (aggregate.h's rule): row bounds are clamped into
+5. Nothing a kernel reads from device memory becomes an address before it is checked (csrc/lists.h's rule): row bounds are clamped into
    [0, nnz] and an end before its start is an empty row; an index outside [0, K), an entry outside [0, nnz) and a row outside the
    target's frame contribute nothing.  Garbage lists give unspecified values, never an access out of bounds; knn_graph's padding
    (index -1) is simply not valid.
@@ -59,8 +59,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _binding as B, _tensors as T
-from .attention import _check_map, _lists, _lists_tensors
-from .propagate import _LIMIT, NeighbourLists, _check_lists
+from .propagate import LIMIT, NeighbourLists, as_lists, check_lists, check_map, differentiable, lists_tensors
 from .rag import SuperpixelGraph, check_graph
 
 __all__ = ["entry_gather", "entry_reduce"]
@@ -79,7 +78,7 @@ def _check_messages(t, nnz):
 
 
 def _check_limits(cells, nnz, Cc):
-    if cells >= _LIMIT or nnz >= _LIMIT or Cc * nnz >= _LIMIT:
+    if cells >= LIMIT or nnz >= LIMIT or Cc * nnz >= LIMIT:
         raise ValueError(_LIMIT_TEXT)
 
 
@@ -146,16 +145,16 @@ def entry_gather(x, nl, end="target"):
     """The features of one end of every neighbour entry, by rule 1 of the module's text: `x` float32 [N, C, K] ([C, K] when N = 1) ->
     float32 [C, nnz], x at the entry's own row (end="target") or at its neighbour indices[p] (end="source"); +0.0 for an entry that is
     not valid.  Differentiable with respect to `x`; one launch forward and one backward, no host synchronisation."""
-    N, Cc, K = _check_map(x, "x")
-    nnz = _check_lists(nl, N, K)
+    N, Cc, K = check_map(x, "x")
+    nnz = check_lists(nl, N, K)
     if not isinstance(end, str) or end not in _END:
         raise ValueError("end must be 'target' or 'source', got %r" % (end,))
     _check_limits(N * Cc * K, nnz, Cc)
-    dev = T.one_device([(x, "x")] + _lists_tensors(nl))
+    dev = T.one_device([(x, "x")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         x3 = x.reshape(N, Cc, K).contiguous()
-        if torch.is_grad_enabled() and x3.requires_grad:
+        if differentiable(x3):
             return _Gather.apply(x3, nl, _END[end])
         return _gather(x3, nl, _END[end])
 
@@ -174,7 +173,7 @@ def entry_reduce(messages, nl, reduce="sum", to="target", *, return_argmax=False
         N, K = T.check_count(num_frames, "num_frames"), T.check_count(num_components, "num_components")
     if (num_frames, num_components) not in ((None, None), (N, K)):
         raise ValueError("the graph has %d frames of %d nodes, not %r of %r" % (N, K, num_frames, num_components))
-    nnz = _check_lists(nl, N, K)
+    nnz = check_lists(nl, N, K)
     Fc = _check_messages(messages, nnz)
     if not isinstance(reduce, str) or reduce not in _REDUCE:
         raise ValueError("reduce must be 'sum', 'mean', 'max' or 'min', got %r" % (reduce,))
@@ -183,11 +182,11 @@ def entry_reduce(messages, nl, reduce="sum", to="target", *, return_argmax=False
     if return_argmax and reduce not in ("max", "min"):
         raise ValueError("return_argmax goes with reduce='max' and 'min' only, got reduce=%r" % reduce)
     _check_limits(N * Fc * K, nnz, Fc)
-    dev = T.one_device([(messages, "messages")] + _lists_tensors(nl))
+    dev = T.one_device([(messages, "messages")] + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         m = messages.reshape(Fc, nnz).contiguous()
-        if torch.is_grad_enabled() and m.requires_grad:
+        if differentiable(m):
             y, argmax = _Reduce.apply(m, nl, _REDUCE[reduce], _END[to])
         else:
             y, argmax, _ = _reduce(m, nl, _REDUCE[reduce], _END[to])

@@ -56,7 +56,7 @@ correctly rounded.  The rules:
 7. pixel_slots(labels, nl, slots) is the node of every slot as int32 [N, S, H, W], -1 where the slot is empty: plain torch on the
    device of the lists, for masks and for dense restatements; not a hot path.
 
-Nothing of a map or a raw pair is trusted on the device, by aggregate.h's rule: nothing a kernel reads from device memory becomes an
+Nothing of a map or a raw pair is trusted on the device, by csrc/lists.h's rule: nothing a kernel reads from device memory becomes an
 address before it is checked.  Garbage lists give unspecified values, never an access out of bounds.
 
 The cost of this design is the dense per-slot tensor: 4 N Hd S H W bytes for the scores and again for alpha (8 frames of 1280 x 720,
@@ -76,8 +76,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _binding as B, _tensors as T
-from .attention import _check_heads, _lists, _lists_tensors
-from .propagate import _LIMIT, NeighbourLists, _check_lists
+from .propagate import LIMIT, NeighbourLists, as_lists, check_heads, check_lists, differentiable, lists_tensors
 from .rag import SuperpixelGraph, check_graph
 
 __all__ = ["pixel_dot", "pixel_softmax", "pixel_mix", "pixel_scatter", "pixel_attention", "pixel_slots"]
@@ -150,11 +149,11 @@ def _graph_size(nl, N, num_components, K=None):
         K = check_graph(nl)[1] if K is None else K
     elif K is None:
         raise ValueError("a raw pair (offsets, indices) needs num_components")
-    return K, _check_lists(nl, N, K)
+    return K, check_lists(nl, N, K)
 
 
 def _check_limits(N, C, H, W, K, Hd, S, nnz):
-    if N * C * H * W >= _LIMIT or N * Hd * S * H * W >= _LIMIT or N * C * K >= _LIMIT or nnz >= _LIMIT:
+    if N * C * H * W >= LIMIT or N * Hd * S * H * W >= LIMIT or N * C * K >= LIMIT or nnz >= LIMIT:
         raise ValueError(_LIMIT_TEXT)
 
 
@@ -169,7 +168,7 @@ class _Geom(object):
 
     def __init__(self, labels, nl, dev, batched, N, H, W, K, S):
         self.lab, self.ltype = T.labels_on(labels, dev, batched)
-        self.nl, self.dev = _lists(nl, N, K), dev
+        self.nl, self.dev = as_lists(nl, N, K), dev
         self.N, self.H, self.W, self.K, self.S = N, H, W, K, S
         self.nnz = int(self.nl.indices.shape[0])
 
@@ -277,10 +276,6 @@ class _Scatter(torch.autograd.Function):
                 _dot(ctx.g, x, go, int(weight.shape[1])) if ctx.needs_input_grad[1] else None, None)
 
 
-def _differentiable(*tensors):
-    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
-
-
 # ---- the public functions ----
 def pixel_slots(labels, nl, slots, *, num_components=None):
     """The node of every slot of every pixel, by the terms of the module's text: int32 [N, S, H, W] ([S, H, W] for an [H, W] map),
@@ -291,7 +286,7 @@ def pixel_slots(labels, nl, slots, *, num_components=None):
     N = int(labels.shape[0]) if batched else 1
     S = _check_slots(slots)
     K, nnz = _graph_size(nl, N, num_components)
-    nl = _lists(nl, N, K)
+    nl = as_lists(nl, N, K)
     offsets, indices, dev = nl.offsets, nl.indices, nl.offsets.device
     if isinstance(labels, np.ndarray):
         labels = torch.from_numpy(np.ascontiguousarray(labels).view(np.int16) if labels.dtype == np.uint16 else np.ascontiguousarray(labels))
@@ -317,13 +312,13 @@ def pixel_dot(a, b, labels, nl, slots, heads=1):
     _, K = _check_nodes(b, "b", batched, N, Cc)
     _check_labels(labels, batched, N, H, W)
     K, nnz = _graph_size(nl, N, None, K)
-    S, Hd = _check_slots(slots), _check_heads(heads, Cc)
+    S, Hd = _check_slots(slots), check_heads(heads, Cc)
     _check_limits(N, Cc, H, W, K, Hd, S, nnz)
-    dev = T.one_device([(a, "a"), (b, "b")] + _label_tensors(labels) + _lists_tensors(nl))
+    dev = T.one_device([(a, "a"), (b, "b")] + _label_tensors(labels) + lists_tensors(nl))
     with torch.cuda.device(dev):
         g = _Geom(labels, nl, dev, batched, N, H, W, K, S)
         a4, b3 = T.batch_of(a, batched), T.batch_of(b, batched)
-        out = _Dot.apply(a4, b3, g, Hd) if _differentiable(a4, b3) else _dot(g, a4, b3, Hd)
+        out = _Dot.apply(a4, b3, g, Hd) if differentiable(a4, b3) else _dot(g, a4, b3, Hd)
     return out if batched else out[0]
 
 
@@ -335,11 +330,11 @@ def pixel_softmax(scores, labels, nl, *, num_components=None):
     _check_labels(labels, batched, N, H, W)
     K, nnz = _graph_size(nl, N, num_components)
     _check_limits(N, Hd, H, W, K, Hd, S, nnz)
-    dev = T.one_device([(scores, "scores")] + _label_tensors(labels) + _lists_tensors(nl))
+    dev = T.one_device([(scores, "scores")] + _label_tensors(labels) + lists_tensors(nl))
     with torch.cuda.device(dev):
         g = _Geom(labels, nl, dev, batched, N, H, W, K, S)
         s5 = T.batch_of(scores, batched)
-        alpha = _Softmax.apply(s5, g) if _differentiable(s5) else _softmax(g, s5, None)
+        alpha = _Softmax.apply(s5, g) if differentiable(s5) else _softmax(g, s5, None)
     return alpha if batched else alpha[0]
 
 
@@ -351,13 +346,13 @@ def pixel_mix(values, weight, labels, nl):
     Cv, K = _check_nodes(values, "values", batched, N)
     _check_labels(labels, batched, N, H, W)
     K, nnz = _graph_size(nl, N, None, K)
-    _check_heads(Hd, Cv, "Cv")
+    check_heads(Hd, Cv, "Cv")
     _check_limits(N, Cv, H, W, K, Hd, S, nnz)
-    dev = T.one_device([(values, "values"), (weight, "weight")] + _label_tensors(labels) + _lists_tensors(nl))
+    dev = T.one_device([(values, "values"), (weight, "weight")] + _label_tensors(labels) + lists_tensors(nl))
     with torch.cuda.device(dev):
         g = _Geom(labels, nl, dev, batched, N, H, W, K, S)
         v3, w5 = T.batch_of(values, batched), T.batch_of(weight, batched)
-        out = _Mix.apply(v3, w5, g) if _differentiable(v3, w5) else _mix(g, v3, w5)
+        out = _Mix.apply(v3, w5, g) if differentiable(v3, w5) else _mix(g, v3, w5)
     return out if batched else out[0]
 
 
@@ -371,13 +366,13 @@ def pixel_scatter(x, weight, labels, nl, num_components):
     Hd, S = int(weight.shape[-4]), int(weight.shape[-3])
     _check_labels(labels, batched, N, H, W)
     K, nnz = _graph_size(nl, N, T.check_count(num_components, "num_components"))
-    _check_heads(Hd, Cc)
+    check_heads(Hd, Cc)
     _check_limits(N, Cc, H, W, K, Hd, S, nnz)
-    dev = T.one_device([(x, "x"), (weight, "weight")] + _label_tensors(labels) + _lists_tensors(nl))
+    dev = T.one_device([(x, "x"), (weight, "weight")] + _label_tensors(labels) + lists_tensors(nl))
     with torch.cuda.device(dev):
         g = _Geom(labels, nl, dev, batched, N, H, W, K, S)
         x4, w5 = T.batch_of(x, batched), T.batch_of(weight, batched)
-        out = _Scatter.apply(x4, w5, g) if _differentiable(x4, w5) else _scatter(g, x4, w5)
+        out = _Scatter.apply(x4, w5, g) if differentiable(x4, w5) else _scatter(g, x4, w5)
     return out if batched else out[0]
 
 
@@ -391,16 +386,16 @@ def pixel_attention(query, key, values, labels, nl, slots, heads=1, scale=None, 
     Cv, _ = _check_nodes(values, "values", batched, N, None, K)
     _check_labels(labels, batched, N, H, W)
     K, nnz = _graph_size(nl, N, None, K)
-    S, Hd = _check_slots(slots), _check_heads(heads, Cc)
-    _check_heads(heads, Cv, "Cv")
+    S, Hd = _check_slots(slots), check_heads(heads, Cc)
+    check_heads(heads, Cv, "Cv")
     if scale is None:
         scale = float(Cc // Hd) ** -0.5
     elif isinstance(scale, bool) or not isinstance(scale, numbers.Real) or scale != scale or scale in (float("inf"), float("-inf")):
         raise ValueError("scale must be None or a finite number, got %r" % (scale,))
     _check_limits(N, max(Cc, Cv), H, W, K, Hd, S, nnz)
-    dev = T.one_device([(query, "query"), (key, "key"), (values, "values")] + _label_tensors(labels) + _lists_tensors(nl))
+    dev = T.one_device([(query, "query"), (key, "key"), (values, "values")] + _label_tensors(labels) + lists_tensors(nl))
     with torch.cuda.device(dev):
-        nl = _lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         labels = T.labels_on(labels, dev, True)[0]                             # uploaded once for the three calls
         alpha = pixel_softmax(pixel_dot(query * torch.tensor(float(scale), dtype=torch.float32).item(), key, labels, nl, S, Hd), labels, nl)
         y = pixel_mix(values, alpha, labels, nl)

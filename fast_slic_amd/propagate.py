@@ -48,6 +48,8 @@ runs on torch's current stream of the tensors' GPU, takes its results and what i
 allocator and never synchronises the host.  There is no CPU fallback.
 This module imports torch; the package itself does not import it.
 """
+import numbers
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -58,7 +60,7 @@ from .rag import SuperpixelGraph, check_graph
 __all__ = ["neighbour_lists", "graph_aggregate", "NeighbourLists"]
 
 _REDUCE = {"sum": 0, "mean": 1, "max": 2}                                  # kAggSum, kAggMean, kAggMax
-_LIMIT = 1 << 31
+LIMIT = 1 << 31                                                           # sizes and entry counts stay below it
 _ENTRY = ("fslic_hip_aggregate_forward", "aggregation entry points")
 
 
@@ -101,7 +103,7 @@ def _check_pair(graph, N, K):
     T.check_tensor(indices, "graph indices", (torch.int32,), "[nnz]", lambda s: len(s) == 1)
 
 
-def _check_lists(lists, N, K):
+def check_lists(lists, N, K):
     """-> nnz of a NeighbourLists, a SuperpixelGraph or a raw pair for N frames of K nodes, known without looking at device memory."""
     if isinstance(lists, NeighbourLists):
         n, k = lists.num_frames, lists.num_components
@@ -113,6 +115,40 @@ def _check_lists(lists, N, K):
     if (n, k) != (N, K):
         raise ValueError("the graph has %d frames of %d nodes, the values have %d of %d" % (n, k, N, K))
     return int(lists.indices.shape[0]) if isinstance(lists, NeighbourLists) else 2 * E
+
+
+def lists_tensors(nl):
+    """The tensors of `nl` (checked by check_lists) that name its device, for _tensors.one_device."""
+    if isinstance(nl, NeighbourLists):
+        return [(nl.offsets, "nl.offsets"), (nl.indices, "nl.indices")]
+    if isinstance(nl, SuperpixelGraph):
+        return [(nl.edge_index, "graph.edge_index"), (nl.offsets, "graph.offsets")]
+    return [(nl[0], "graph offsets"), (nl[1], "graph indices")]
+
+
+def as_lists(nl, N, K):
+    """`nl` itself, or the NeighbourLists of a SuperpixelGraph or a raw pair, built once per call."""
+    return nl if isinstance(nl, NeighbourLists) else neighbour_lists(nl, N, K)
+
+
+def check_map(t, what):
+    """-> (N, C, K) of a float32 [N, C, K] or [C, K] tensor."""
+    T.check_float_map(t, (2, 3), what, "[C, K] or [N, C, K]")
+    Cc, K = (int(v) for v in t.shape[-2:])
+    T.check_count(K, "K, the last dimension of %s," % what)
+    return (int(t.shape[0]) if t.dim() == 3 else 1), Cc, K
+
+
+def check_heads(heads, Cc, what="C"):
+    if isinstance(heads, bool) or not isinstance(heads, numbers.Integral) or heads < 1:
+        raise ValueError("heads must be a positive integer, got %r" % (heads,))
+    if Cc % heads != 0:
+        raise ValueError("%s = %d is not a multiple of heads = %d" % (what, Cc, heads))
+    return int(heads)
+
+
+def differentiable(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def neighbour_lists(graph, num_frames=None, num_components=None):
@@ -196,12 +232,8 @@ def graph_aggregate(values, nl, weight=None, reduce="sum", *, return_argmax=Fals
     int32 [nnz]), whose lists are then built once per call.  `weight`: None or float32 [nnz], with reduce="sum" only.  reduce: "sum",
     "mean" or "max"; with return_argmax=True and "max" the result is (y, argmax int32 of the values' shape).  Differentiable with
     respect to `values` and `weight`; one launch forward, one for each gradient, no host synchronisation."""
-    T.check_float_map(values, (2, 3), "values", "[C, K] or [N, C, K]")
-    batched = values.dim() == 3
-    N = int(values.shape[0]) if batched else 1
-    Cc, K = (int(v) for v in values.shape[-2:])
-    T.check_count(K, "K, the last dimension of values,")
-    nnz = _check_lists(nl, N, K)
+    N, Cc, K = check_map(values, "values")
+    nnz = check_lists(nl, N, K)
     if not isinstance(reduce, str) or reduce not in _REDUCE:
         raise ValueError("reduce must be 'sum', 'mean' or 'max', got %r" % (reduce,))
     if weight is not None:
@@ -210,23 +242,16 @@ def graph_aggregate(values, nl, weight=None, reduce="sum", *, return_argmax=Fals
         T.check_tensor(weight, "weight", (torch.float32,), "[nnz] with nnz = %d, one per neighbour entry" % nnz, lambda s: s == (nnz,))
     if return_argmax and reduce != "max":
         raise ValueError("return_argmax goes with reduce='max' only, got reduce=%r" % reduce)
-    if N * Cc * K >= _LIMIT or nnz >= _LIMIT:
+    if N * Cc * K >= LIMIT or nnz >= LIMIT:
         raise ValueError("N * C * K and the number of neighbour entries must be below 2^31")
-    if isinstance(nl, NeighbourLists):
-        on_lists = [(nl.offsets, "nl.offsets"), (nl.indices, "nl.indices")]
-    elif isinstance(nl, SuperpixelGraph):
-        on_lists = [(nl.edge_index, "graph.edge_index"), (nl.offsets, "graph.offsets")]
-    else:
-        on_lists = [(nl[0], "graph offsets"), (nl[1], "graph indices")]
-    dev = T.one_device([(values, "values"), (weight, "weight")] + on_lists)
+    dev = T.one_device([(values, "values"), (weight, "weight")] + lists_tensors(nl))
 
     with torch.cuda.device(dev):
-        if not isinstance(nl, NeighbourLists):
-            nl = neighbour_lists(nl, N, K)
+        nl = as_lists(nl, N, K)
         x = values.reshape(N, Cc, K).contiguous()
         w = weight.contiguous() if weight is not None else None
         mode = _REDUCE[reduce]
-        if torch.is_grad_enabled() and (x.requires_grad or (w is not None and w.requires_grad)):
+        if differentiable(x, w):
             y, argmax = _Aggregate.apply(x, w, nl, mode)
         else:
             y, argmax, _ = _forward(x, nl, w, mode)

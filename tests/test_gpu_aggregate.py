@@ -4,13 +4,14 @@ grad_values of the mean, forward, argmax and grad_values of the max with deliber
 wavefront, than a block and than the kernel's LDS window, random graphs, isolated nodes, frames without an edge, the graph of a label
 map, node counts around a block and channel counts around the 8 of a wave and the 32 of an item; non-contiguous and unbatched values,
 a raw pair with invalid entries, once round each kernel's loop, a side stream without host synchronisation, the same bits from run to
-run, and entry_values as weights end to end."""
+run, entry_values as weights end to end, and the weighted sum below 32 channels against head_aggregate's other item shape."""
 import numpy as np
 import pytest
 import torch
 
 import aggregate_ref as A
 import connect_ref
+from fast_slic_amd.attention import head_aggregate
 from fast_slic_amd.propagate import graph_aggregate, neighbour_lists
 from fast_slic_amd.rag import superpixel_graph
 from test_aggregate_cpu import make_graph, numpy_lists, path, random_pairs, star
@@ -97,8 +98,17 @@ def test_star_hubs_longer_than_a_wavefront_a_block_and_the_window(K, degree):
     """The hub's row (and, transposed, its target) is walked in full and in order, and the rows behind it in its tile start beyond the
     LDS window."""
     rng = np.random.default_rng(degree)
-    check_graph([star(K, degree)], K, 3)
+    g, nl = check_graph([star(K, degree)], K, 3)
     check_graph([star(K, degree, hub=5) + random_pairs(rng, K, 4), path(K)], K, 2, seed=1)
+    # the weight's gradient where the hub's entries share one row: every thread of many wavefronts reads the same cells of grad_out
+    offsets, indices = numpy_lists(nl)
+    hub = int(np.argmax(np.diff(offsets)))
+    assert offsets[hub + 1] - offsets[hub] == degree and (nl.rows[offsets[hub]:offsets[hub + 1]] == hub).all()
+    x, gout = rng.standard_normal((1, 3, K)).astype(F32), rng.standard_normal((1, 3, K)).astype(F32)
+    w = rng.standard_normal(len(indices)).astype(F32)
+    gw = run(x, nl, w, "sum", gout)[3]
+    want = A.backward_weight(x, gout, offsets, indices)
+    assert same(gw, want) and want[offsets[hub]:offsets[hub + 1]].all()
 
 
 def test_no_edges():
@@ -115,6 +125,25 @@ def test_no_edges():
 def test_channels_around_an_item(Cc):
     rng = np.random.default_rng(Cc)
     check_graph([random_pairs(rng, 257, 6), random_pairs(rng, 257, 3), path(257)], 257, Cc, seed=Cc)
+
+
+@pytest.mark.parametrize("Cc", [1, 3])
+def test_weighted_sum_is_head_aggregate_at_one_head(Cc):
+    """Below 32 channels the weighted sum runs the apply kernel's item of 32 channels of one head and head_aggregate its packed item:
+    both are the model's bytes, and so each other's, forward and for both gradients."""
+    rng = np.random.default_rng(Cc)
+    nl = neighbour_lists(make_graph([random_pairs(rng, 257, 6), random_pairs(rng, 257, 3), path(257)], 257, DEV, Cc))
+    offsets, indices = numpy_lists(nl)
+    x, gout = rng.standard_normal((3, Cc, 257)).astype(F32), rng.standard_normal((3, Cc, 257)).astype(F32)
+    w = rng.standard_normal(len(indices)).astype(F32)
+    y, _, gx, gw = run(x, nl, w, "sum", gout)
+    assert same(y, A.forward(x, offsets, indices, w)[0]) and same(gx, A.backward_values(gout, offsets, indices, w))
+    assert same(gw, A.backward_weight(x, gout, offsets, indices))
+    xt, wt = dev(x).requires_grad_(), dev(w).requires_grad_()
+    yh = head_aggregate(xt, nl, wt)                                        # [nnz]: one head
+    yh.backward(dev(gout))
+    for a, b in ((y, yh), (gx, xt.grad), (gw, wt.grad)):
+        assert a.shape == b.shape and torch.equal(a.detach().view(torch.int32), b.detach().view(torch.int32))
 
 
 @pytest.mark.parametrize("connectivity", [4, 8])
